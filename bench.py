@@ -21,6 +21,12 @@ spatial prior and RCCL halo exchange), ``multisensor`` (S2 13-band + OLCI-like
 Multi-GPU: tile-DP over row strips, one process per GPU (torchrun), RCCL for
 the global convergence norm (and halos); the tile is fixed, so scaling is
 strong.  Prints ONE JSON line on rank 0.
+
+A plain run (``--gpus 1 --steps N --warmup W``) sets up, warms up, times the N
+steps and prints the record; everything in the record is read from those
+steps.  ``--dump-outputs DIR`` also writes what the last timed step returned
+(``dump_outputs``).  Measurements that need runs of their own belong behind
+``--full`` (off by default).
 """
 from __future__ import annotations
 
@@ -80,6 +86,43 @@ def socket_name():
 
 def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+# --dump-outputs: pixels sampled over the whole job.  The widest state (PROSAIL:
+# 10 mean + 55 packed-P + 10 + 10 raster rows) is 85 float32 rows: 45 MB.
+DUMP_PIXELS = 131072
+
+
+def dump_outputs(path, kf, state, part, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step -- the returned state (mean x [n_p, n], packed P [n_p (n_p + 1) / 2, n];
+    rows of P that the analysis did not store are written as zeros) and the
+    output's mean / uncertainty rasters at the same pixels -- as float32 .npy
+    files.  Strips larger than their share of DUMP_PIXELS are sampled at fixed,
+    seeded pixels (``pixel_index``: their global raster indices), so two builds
+    run with the same arguments write comparable arrays."""
+    os.makedirs(path, exist_ok=True)
+    N, n_s = int(state.N), max(1, DUMP_PIXELS // world)
+    pix = np.arange(N) if N <= n_s else np.sort(np.random.default_rng(1234 + rank).choice(N, n_s, replace=False))
+    tag = "" if world == 1 else f".strip{rank}"
+
+    def save(name, arr):
+        if torch.is_tensor(arr):
+            arr = arr.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, f"{name}{tag}.npy"), arr)
+    sel = torch.from_numpy(pix).to(state.x.device)
+    save("state_x", state.x[:, sel])
+    P = state.P[:, sel]
+    if state.p_valid is not None:
+        stored = torch.tensor([bool((state.p_valid >> t) & 1) for t in range(P.shape[0])], device=P.device)
+        P = torch.where(stored[:, None], P, torch.zeros_like(P))
+    save("state_P", P)
+    mean, unc = getattr(kf.output, "mean", None), getattr(kf.output, "unc", None)
+    if torch.is_tensor(mean) and torch.is_tensor(unc):
+        ras = torch.from_numpy(np.asarray(part.local_idx, dtype=np.int64)[pix]).to(mean.device)
+        save("output_mean", mean[:, ras])
+        save("output_unc", unc[:, ras])
+    save("pixel_index", np.asarray(part.global_index(), dtype=np.float64)[pix])
 
 
 def build(cfg_name, a, mask, part, dev, comm):
@@ -203,6 +246,14 @@ def main():
     ap.add_argument("--dump-state", default=None, metavar="PREFIX",
                     help="after the timed region, write each strip's final state x [n_p, N] to "
                          "PREFIX.strip<r>.npy (band slot 0 only; rehearsal checks against one rank)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (state mean and packed "
+                         "P, output mean/uncertainty rasters) to DIR/<name>.npy (float32; tiles over "
+                         f"{DUMP_PIXELS} pixels: a fixed seeded pixel sample, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks that need runs of their own, beyond the headline "
+                         "figure (none at present: the record's health fields and per-rank telemetry come from "
+                         "the timed steps themselves)")
     ap.add_argument("--output", default=None, metavar="DIR",
                     help="write every timestep's mean/unc GeoTIFFs here (KafkaOutput; the timed region ends "
                          "after the writer has drained); default: device rasters only")
@@ -396,6 +447,8 @@ def main():
     ok_local = bool(torch.isfinite(state.x[:, :state.N]).all().item())
     if a.dump_state and (comm.band is None or comm.band.rank == 0):
         np.save(f"{a.dump_state}.strip{rank}.npy", state.x[:, :state.N].cpu().numpy())
+    if a.dump_outputs and (comm.band is None or comm.band.rank == 0):
+        dump_outputs(a.dump_outputs, kf, state, part, rank, world)
     st_last = getattr(kf, "last_status", None)
     n_fb = 0 if st_last is None or not state.N else int(((st_last[:state.N] & K.ST_FALLBACK) > 0).sum().item())
     # GP inputs outside the emulators' training box (models/operators.py GP_DOMAIN_MARGIN) at the last date

@@ -58,6 +58,39 @@ def test_cli_resume_without_checkpoint_fails_clearly(tmp_path):
     assert r.returncode != 0 and "no committed checkpoint" in r.stderr
 
 
+def test_bench_steps_dump_outputs_and_full(tmp_path):
+    """bench.py: --steps is the number of timed steps, the record carries
+    ms_per_step, and --dump-outputs writes the last step's arrays as float32
+    .npy -- a fixed pixel sample on a tile larger than the sample, the same
+    from run to run -- with or without --full."""
+    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="4")
+    dumps = []
+    for extra in ([], ["--full"]):
+        d = tmp_path / f"dump{len(dumps)}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup",
+                            "1", "--device", "cpu", "--size", "384", "--n-train", "40", "--dump-outputs", str(d),
+                            *extra], capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.strip().splitlines()
+        assert len(lines) == 1                                   # one JSON result line
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 3 and len(rec["config"]["gn_iterations"]) == 3 and rec["ms_per_step"] > 0
+        assert abs(rec["value"] - 384 * 384 / (rec["ms_per_step"] * 1e-3)) < 1e-3 * rec["value"]
+        assert rec["higher_is_better"] and rec["dtype"] == "fp32" and rec["unit"] == "pixel-state updates/s"
+        dumps.append({p.stem: np.load(p) for p in sorted(d.iterdir())})
+    a, b = dumps
+    assert sorted(a) == ["output_mean", "output_unc", "pixel_index", "state_P", "state_x"]
+    n = a["pixel_index"].size
+    assert 0 < n < 384 * 384 and np.all(np.diff(a["pixel_index"]) > 0) and a["pixel_index"].max() < 384 * 384
+    assert a["state_x"].shape == (7, n) and a["state_P"].shape == (28, n) and a["output_unc"].shape == (7, n)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), name
+        assert np.array_equal(v, b[name]), name
+    assert np.array_equal(a["output_mean"], a["state_x"])        # the mean raster of a dense tile is the state
+    assert (a["output_unc"] > 0).all()
+
+
 def test_cli_chunks_matches_reference_golden():
     out = _run("chunks", "235", "204", "--block", "128", "128")
     assert out.split("\n")[:4] == ["0 0 128 128 1", "0 128 128 76 2", "128 0 107 128 3", "128 128 107 76 4"]

@@ -18,29 +18,9 @@ from kafka_inferenceengine_amd.input_output import sentinel as S
 from kafka_inferenceengine_amd.input_output.tiff import read_tiff, tiff_info
 from kafka_inferenceengine_amd.input_output.utils import GridWarp, reproject_image
 
-REF_MASK = "/root/reference/Barrax_pivots.tif"
 UTM30N = "WGS 84 / UTM zone 30N|WGS 84"
-BARRAX_GT = [576452.584549, 10.0, 0.0, 4324696.153353, 0.0, -10.0]
-
-
-def _mask_file():
-    """The reference's Barrax_pivots.tif where the reference tree exists (this
-    container); on a GPU box a stand-in on the same grid (235 x 204, 10 m,
-    EPSG:32630) with five disc-shaped pivots."""
-    if os.path.exists(REF_MASK):
-        return REF_MASK
-    import tempfile
-    p = os.path.join(tempfile.gettempdir(), "kafka_barrax_grid_mask.tif")
-    if not os.path.exists(p):
-        yy, xx = np.mgrid[0:204, 0:235]
-        m = np.zeros((204, 235), np.uint8)
-        for cy, cx in ((50, 60), (60, 170), (150, 50), (140, 150), (100, 110)):
-            m[(yy - cy) ** 2 + (xx - cx) ** 2 < 40 ** 2] = 1
-        k.write_tiff(p, m, BARRAX_GT, UTM30N)
-    return p
-
-
-MASK = _mask_file()
+# the reference's Barrax_pivots.tif (235 x 204, 10 m, EPSG:32630), stored with the tests
+MASK = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "Barrax_pivots.tif")
 
 
 def _granule_grid():
