@@ -158,6 +158,8 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
       .def_readwrite("fast_obs", &GainArgs::fast_obs)
       .def_readwrite("out_plane", &GainArgs::out_plane)
       .def_readwrite("gpm_frags", &GainArgs::gpm_frags)
+      .def_readwrite("gpm_global", &GainArgs::gpm_global)
+      .def_readwrite("band_layout", &GainArgs::band_layout)
       .def_readwrite("gn_fused", &GainArgs::gn_fused)
       .def_readwrite("n_visit", &GainArgs::n_visit)
       .PTR_FIELD(GainArgs, n_visit_dev, const int32_t*)

@@ -1452,11 +1452,17 @@ struct GainArgs {
   // fused forecast with PropArgs.pa_pdiag reads: the propagated parameters'
   // entries); 0: the full analysis covariance
   uint32_t pdiag_rows;
-  int32_t pad_;
+  // 1: every band has an MFMA table, read from global memory (too large for
+  // LDS: ten PROSAIL bands, the multi-sensor state); gain_mfma_g_kernel
+  int32_t gpm_global;
   // line tables of the first iteration at the fused forecast (as AnalysisArgs.line_*)
   const float* line_tab;
   float line_t0, line_inv_h;
   int32_t line_n, line_j;
+  // host hint as AnalysisArgs.band_layout (BAND_LAYOUT_SHARED_X: one exponent
+  // operand per iteration in the global-table kernel); 0: runtime
+  int32_t band_layout;
+  int32_t pad_;
 };
 
 KF_HD int64_t visit_count(const GainArgs& a) { return visit_bounded(a.n_visit, a.N, a.n_visit_dev); }

@@ -1,6 +1,6 @@
 // kf_device.h — gfx950 (MI355X) kernel templates for the KaFKA engine, shared by
-// the translation units kf_kernels.hip, kf_analysis7.hip and kf_analysis10.hip
-// (split so the heavy analysis instantiations compile in parallel, _build.py).
+// the translation units kf_kernels.hip, kf_analysis7.hip, kf_analysis10.hip and
+// kf_gain10.hip (split so the heavy instantiations compile in parallel, _build.py).
 //
 // Design: every matrix the reference builds is block
 // diagonal with n_p x n_p per-pixel blocks, so the whole Gauss-Newton
@@ -260,6 +260,37 @@ __global__ __launch_bounds__(BLOCK, 3) void gain_mfma_kernel(GainArgs a) {
 #endif
 }
 
+// K1g on the matrix cores with every band's table read from global memory
+// (the gain form's analysis_mfma_g_kernel): ten PROSAIL bands and the
+// multi-sensor state, whose tables exceed the LDS.  2 waves per SIMD by the
+// launch bound (the 55-float packed covariance per lane, as the information
+// form's packed A; 256 VGPRs, 112 B of scratch per lane).  Both column
+// blocks' exponent MFMAs are issued first (gpm_chunk IL, as gpm_il_default for
+// 10 parameters): the same register and scratch counts as block by block, and
+// 1.2 % (prosail10) and 1.9 % (multisensor) faster in an alternating A/B on
+// one box (BENCHMARKS.md).
+template <int NP, int D, int FOBS>
+__global__ __launch_bounds__(BLOCK, 2) void gain_mfma_g_kernel(GainArgs a) {
+  static_assert(BLOCK / 64 == GPM_G_WAVES, "per-wave LDS transpose buffers of gp_mfma_sums_g_xb");
+#if defined(__HIP_DEVICE_COMPILE__)
+  double acc = 0.0, acc1 = 0.0;
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * BLOCK;
+  const int64_t nv = visit_count(a);
+  for (int64_t base = (int64_t)blockIdx.x * BLOCK + (threadIdx.x - lane); base < nv; base += stride) {
+    const int64_t q = base + lane;
+    const bool act = q < nv;
+    const int64_t p = visit_px(a.order, act ? q : nv - 1);
+    float dn1;
+    const float dn = pixel_gain_mfma<NP, D, FOBS, true, true>(a, p, act, nullptr, dn1);
+    acc += act ? (double)dn : 0.0;
+    acc1 += act ? (double)dn1 : 0.0;
+  }
+  if (a.partials_first) block_partials2<BLOCK>(acc, acc1, a.partials, a.partials_first);
+  else if (a.partials) block_partial(acc, a.partials);
+#endif
+}
+
 template <int NP, int FD = 0, int FOBS = 0>
 __global__ __launch_bounds__(BLOCK) void gain_kernel(GainArgs a) {
   double acc = 0.0, acc1 = 0.0;
@@ -303,6 +334,15 @@ static void l_gain(const GainArgs& a, int grid, hipStream_t s) {
     }
     KF_GAIN_FAST(4)
   } else if constexpr (NP == 10) {
+    // full-state GP bands with global tables (ops/kernels.py:gain sets
+    // gpm_global unless the VALU oracle is selected)
+    if (a.gpm_global && a.fast_d == NP && (a.fast_obs == OBS_DN16 || a.fast_obs == OBS_F32)) {
+      if (a.fast_obs == OBS_DN16)
+        hipLaunchKernelGGL((gain_mfma_g_kernel<NP, NP, OBS_DN16>), dim3(grid), dim3(BLOCK), 0, s, a);
+      else
+        hipLaunchKernelGGL((gain_mfma_g_kernel<NP, NP, OBS_F32>), dim3(grid), dim3(BLOCK), 0, s, a);
+      return;
+    }
     KF_GAIN_FAST(10)
   }
 #undef KF_GAIN_FAST

@@ -801,13 +801,26 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
 // (kf_core.h) with lane = pixel, each band's GP sums wave-cooperative as in
 // pixel_analysis_mfma (every lane of the wave takes part, act = false lanes
 // included), then the same scalar-band update and tail.
-template <int NP, int D, int FOBS>
+//
+// GT: every band's table read from global memory (gp_mfma_sums_g: ten PROSAIL
+// bands, the multi-sensor state; lds unused).  With BAND_LAYOUT_SHARED_X
+// (GainArgs.band_layout) the linearisation point's exponent operand is built
+// once per Gauss-Newton iteration -- by the first band of the iteration that
+// runs the GP sums -- and every band patches its own constant in
+// (gpm_patch_c), as pixel_analysis_mfma; the centred inputs are recomputed per
+// band from x0 (the same subtraction: bit-identical, ten registers fewer
+// across the band updates).
+template <int NP, int D, int FOBS, bool GT = false, bool IL = false>
 __device__ __forceinline__ float pixel_gain_mfma(const GainArgs& a, int64_t p, bool act, const kf_h8* lds,
                                                  float& dn1) {
+  constexpr bool SXC = GT && D == NP && D % 2 == 0;
+  kf_h8 sxb[2][gpm_k_steps(D)];
+  int sx_it = -1;   // the iteration sxb was built for (wave-uniform)
   return gain_pixel<NP>(a, p, act, dn1, [&](int bi, int it, const float (&x0)[NP], float& y, float& w, float& H0,
                                             float (&h)[NP], bool& ok) -> bool {
     int off = 0;
-    for (int bj = 0; bj < bi; ++bj) off += cptr(a.bands)[bj].gpm_nchunk * gpm_frags_per_chunk(D);
+    if constexpr (!GT)
+      for (int bj = 0; bj < bi; ++bj) off += cptr(a.bands)[bj].gpm_nchunk * gpm_frags_per_chunk(D);
     const KF_CONST_AS BandDesc* bdp = cptr(a.bands) + bi;
     decode_obs<FOBS>(*bdp, p, y, w);
     const bool use = act && (w > 0.f);
@@ -846,7 +859,31 @@ __device__ __forceinline__ float pixel_gain_mfma(const GainArgs& a, int64_t p, b
       gpm_inputs<NP, D>(bdp, x0, xi, c);
       c *= -0.5f * LOG2E;
       float S[D + 1];
-      gp_mfma_sums<D>(lds + off, lds + a.gpm_frags - 1, nch, xi, c, S);
+      if constexpr (GT) {
+        bool sx = false;
+        if constexpr (SXC) sx = la->band_layout == BAND_LAYOUT_SHARED_X;
+        if constexpr (SXC) {
+          if (sx) {
+            if (sx_it != it) {
+              // every band of the layout has this band's centre and the identity map
+              float c0;
+              gpm_operands<D>(xi, 0.f, sxb, c0);
+              sx_it = it;
+            }
+            kf_h8 xb[2][gpm_k_steps(D)];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+              for (int kk = 0; kk < gpm_k_steps(D); ++kk) xb[i][kk] = sxb[i][kk];
+            float cl;
+            gpm_patch_c<D>(xb, c, cl);
+            gp_mfma_sums_g_xb<D, false, IL>(bdp->gpm, nch, xb, cl, S);
+          }
+        }
+        if (!sx) gp_mfma_sums_g<D, false, IL>(bdp->gpm, nch, xi, c, S);
+      } else {
+        gp_mfma_sums<D>(lds + off, lds + a.gpm_frags - 1, nch, xi, c, S);
+      }
       const KF_CONST_AS BandDesc* q = opaque(bdp);
       const float sc = q->gpm_scale;
       float Sd[D];

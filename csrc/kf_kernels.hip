@@ -608,7 +608,15 @@ hipError_t dev_analysis(int np, const AnalysisArgs& a, int grid, hipStream_t s, 
 }
 
 hipError_t dev_gain(int np, const GainArgs& a, int grid, hipStream_t s) {
-  KF_NP_SWITCH(np, l_gain, a, grid, s);
+  if (np == 10) return dev_gain_np10(a, grid, s);   // kf_gain10.hip
+  switch (np) {
+    case 1: l_gain<1>(a, grid, s); break;
+    case 2: l_gain<2>(a, grid, s); break;
+    case 3: l_gain<3>(a, grid, s); break;
+    case 4: l_gain<4>(a, grid, s); break;
+    case 7: l_gain<7>(a, grid, s); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 hipError_t dev_jacobi(int np, const JacobiArgs& a, int grid, hipStream_t s) {

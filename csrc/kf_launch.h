@@ -32,6 +32,7 @@ hipError_t phase_clocks_np7(unsigned long long* out, bool reset);
 hipError_t phase_clocks_np10(unsigned long long* out, bool reset);
 #endif
 hipError_t dev_gain(int np, const GainArgs& a, int grid, hipStream_t s);
+hipError_t dev_gain_np10(const GainArgs& a, int grid, hipStream_t s);
 hipError_t dev_jacobi(int np, const JacobiArgs& a, int grid, hipStream_t s);
 hipError_t dev_propagate(int np, const PropArgs& a, hipStream_t s);
 hipError_t dev_invert(int np, const float* src, float* dst, int64_t N, int64_t ld, uint8_t* st, hipStream_t s);

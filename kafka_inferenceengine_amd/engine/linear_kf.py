@@ -960,6 +960,12 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin):
             # advance_state's lazy_cov); other forecasts invert the full covariance
             prop = self._state_propagator
             spec = getattr(prop, "device_spec", None) if prop is not None else None
+            if prop is None and self.prior is not None and cfg.fuse_propagation:
+                # prior reset (the S2 driver: no propagator, a constant prior): the
+                # next forecast is PROP_PRIOR through advance_state's lazy_cov and
+                # reads nothing of this analysis -- store nothing, as the information form
+                pd = self.prior.device_prior(None) if hasattr(self.prior, "device_prior") else None
+                return set() if (pd is not None and pd.constant) else None
             if self.prior is not None or spec is None or not K.prop_is_light(spec.mode):
                 return None
         return self._next_forecast_rows()

@@ -146,6 +146,7 @@ OP_GP = 2
 GPM_MAX_LDS = 160 * 1024
 GPM_MAX_BANDS = 4          # kf_gp_mfma.h: bands of the LDS-staged matrix-core path
 GPM_GLOBAL_D = (7, 10)     # full-state GP input counts with a global-table instantiation
+GAIN_GLOBAL_D = (10,)      # ... of the gain form (kf_device.h:gain_mfma_g_kernel)
 
 # kf_core.h BAND_LAYOUT_TIP: exactly two GP bands with the JRC-TIP VIS then NIR maps
 # (BandDesc.map_kind 2, 3), 4 inputs each: the matrix-core kernel unrolls the band loop
@@ -714,6 +715,12 @@ def gain(n_params, bands: BandTable, x_prev, x_f, p_f, x_out, p_out=None, status
         a.fast_d, a.fast_obs = 0, 0
     # GP on the matrix cores with LDS tables (kf_device.h:gain_mfma_kernel, JRC-TIP)
     a.gpm_frags = bands.gpm_frags if (fast and DEFAULT_VARIANT != Variant.VALU_ORACLE) else 0
+    # ... with the tables in global memory (gain_mfma_g_kernel: ten PROSAIL bands, the
+    # multi-sensor state); PER_BAND_OPERAND: the shared exponent operand's oracle
+    a.gpm_global = int(bool(bands.gpm_global) and fast and bands.fast_d == n_params
+                       and n_params in GAIN_GLOBAL_D and DEFAULT_VARIANT != Variant.VALU_ORACLE)
+    if a.gpm_global and bands.layout == BAND_LAYOUT_SHARED_X and DEFAULT_VARIANT != Variant.PER_BAND_OPERAND:
+        a.band_layout = BAND_LAYOUT_SHARED_X
     a.bands = bands.ptr
     a.x_prev, a.x_f, a.p_f, a.x_out, a.p_out = map(_ptr, (x_prev, x_f, p_f, x_out, p_out))
     a.status, a.partials = _ptr(status), _ptr(partials)
@@ -762,7 +769,7 @@ def gain(n_params, bands: BandTable, x_prev, x_f, p_f, x_out, p_out=None, status
         if int(pdiag_rows) >> n_params:
             raise ValueError(f"pdiag_rows has bits past the {n_params} parameters")
         a.pdiag_rows = int(pdiag_rows)
-    if a.gpm_frags > 0:
+    if a.gpm_frags > 0 or a.gpm_global:
         _set_line(a, bands, prop, n_params, dev, x_prev, line)
     grid = grid_for(nv)
     ext().gain(n_params, a, grid, _dev(ref), _stream(ref))
