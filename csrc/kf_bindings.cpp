@@ -146,6 +146,7 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
       .def_readwrite("line_inv_h", &AnalysisArgs::line_inv_h)
       .def_readwrite("line_n", &AnalysisArgs::line_n)
       .def_readwrite("line_j", &AnalysisArgs::line_j)
+      .def_readwrite("a_struct", &AnalysisArgs::a_struct)
       .GEO_FIELDS(AnalysisArgs, reg_geo);
 
   py::class_<GainArgs>(m, "GainArgs")

@@ -124,6 +124,41 @@ constexpr int FD_LINEAR = -2;     // AnalysisArgs.fast_d: all bands OP_LINEAR (i
 KF_HD constexpr int tri(int n, int i, int j) { return i * n - (i * (i - 1)) / 2 + (j - i); }
 template <int NP> KF_HD constexpr int sym(int i, int j) { return i <= j ? tri(NP, i, j) : tri(NP, j, i); }
 
+// Compile-time structure of a packed symmetric matrix: on(i, j) == false marks
+// an entry that is exactly zero in the forecast precision and in every
+// analysis precision of the launch, and stays zero through the Cholesky
+// factorisation (struct_closed: the elimination creates no fill there).
+// chol_packed / chol_solve / symv skip the operations on such entries: each is
+// an FMA or a product with an exact zero factor, so the kept entries get the
+// bits of the dense code in the same operand order.  The masked-out slots of
+// the packed array are never read or written (no registers).
+struct StructDense {
+  static constexpr bool on(int, int) { return true; }
+};
+// JRC-TIP: the VIS band reads the states {0, 1, 6, 2}, the NIR band {3, 4, 6, 5}
+// (kf_tools.py:19-23), and the prior couples (2, 5) (models/priors.py:tip_prior),
+// so the VIS / NIR blocks only meet in row 2 - column 5 and in the TLAI
+// row / column 6: 8 of the 21 off-diagonal entries are zero.  The host checks
+// the prior precision against this mask (ops/kernels.py:tip_structure).
+struct StructTip {
+  static constexpr bool on(int i, int j) {
+    const int a = i < j ? i : j, b = i < j ? j : i;
+    return !((a <= 1 && b >= 3 && b <= 5) || (a == 2 && (b == 3 || b == 4)));
+  }
+};
+// No fill: a masked-out (j, i) has no eliminated column k < j with both (k, j)
+// and (k, i) kept (natural order).
+template <int NP, class M>
+constexpr bool struct_closed() {
+  for (int j = 0; j < NP; ++j)
+    for (int i = j + 1; i < NP; ++i) {
+      if (M::on(j, i)) continue;
+      for (int k = 0; k < j; ++k)
+        if (M::on(k, j) && M::on(k, i)) return false;
+    }
+  return true;
+}
+
 // ---------------------------------------------------------------------------
 // enums shared with Python (kafka_inferenceengine_amd/ops/_abi.py)
 enum ObsKind : int32_t { OBS_NONE = 0, OBS_F32 = 1, OBS_DN16 = 2, OBS_BF16 = 3, OBS_BF16Y = 4 };
@@ -243,6 +278,23 @@ constexpr int SPEC_ANY = 0, SPEC_PROP = 1, SPEC_PROP_REG = 2;
 // SPEC_PROP_PF: SPEC_PROP whose grid loop also loads the next pixel group's
 // forecast inputs ahead (small emulators, kf_device.h:analysis_mfma_kernel)
 constexpr int SPEC_PROP_PF = 3;
+// The same three launches for the JRC-TIP layout with the structure-aware solve
+// (StructTip: AnalysisArgs.a_struct, checked on the host).  spec_base: the
+// launch kind without the structure.
+constexpr int SPEC_PROP_TIP = 4, SPEC_PROP_REG_TIP = 5, SPEC_PROP_PF_TIP = 6;
+KF_HD constexpr bool spec_sparse(int spec) { return spec >= SPEC_PROP_TIP; }
+KF_HD constexpr int spec_base(int spec) { return spec_sparse(spec) ? spec - 3 : spec; }
+// AnalysisArgs.a_struct bits.  A_STRUCT_TIP: the fused forecast's constant
+// precision (PropArgs.reset_cinv) is exactly zero outside StructTip and the
+// bands have the JRC-TIP layout.  A_STRUCT_TIP_PRIOR: it is moreover diagonal
+// plus the (2, 5) pair and finite, and the reset means are finite (the
+// unobserved-wave shortcut of kf_gp_mfma.h:pixel_analysis_mfma).
+constexpr int A_STRUCT_TIP = 1, A_STRUCT_TIP_PRIOR = 2;
+template <int SPEC>
+struct SpecMask { typedef StructDense type; };
+template <> struct SpecMask<SPEC_PROP_TIP> { typedef StructTip type; };
+template <> struct SpecMask<SPEC_PROP_REG_TIP> { typedef StructTip type; };
+template <> struct SpecMask<SPEC_PROP_PF_TIP> { typedef StructTip type; };
 
 // AnalysisArgs.variant: the production kernel (AV_DEFAULT) or an alternate
 // device path kept as a test oracle -- each is bit-identical to the default or
@@ -255,7 +307,8 @@ enum AnalysisVariant : int32_t {
   AV_RUNTIME_LAYOUT = 10,    // JRC-TIP bands through the runtime-layout kernel (BAND_LAYOUT_TIP's oracle)
   AV_PER_BAND_OPERAND = 14,  // BAND_LAYOUT_SHARED_X: exponent operand rebuilt per band
   AV_BLOCK_ORDER = 16,       // exponent MFMAs block by block (gpm_il_default's other order)
-  AV_GENERIC_SPEC = 18       // fused forecast through the generic launch instead of SPEC_PROP
+  AV_GENERIC_SPEC = 18,      // fused forecast through the generic launch instead of SPEC_PROP
+  AV_DENSE_SOLVE = 20        // the dense solve where a_struct would select the structure-aware kernels / host path
 };
 
 struct AnalysisArgs {
@@ -337,6 +390,11 @@ struct AnalysisArgs {
   const float* line_tab;
   float line_t0, line_inv_h;
   int32_t line_n, line_j;
+  // A_STRUCT_* bits (host-checked, ops/kernels.py:tip_structure): the fused
+  // forecast's precision has the JRC-TIP zero structure, so the launch takes
+  // the structure-aware solve (SPEC_*_TIP kernels, the host runner's StructTip
+  // path); 0: dense
+  int32_t a_struct;
 };
 
 // slots visited by a launch: n_visit (0: N), or the device count (<= that bound)
@@ -496,23 +554,29 @@ KF_HD const T* pxp(const T* row, int64_t p) {
 // In-place packed Cholesky A = U^T U (U upper, stored in A's packed slots).
 // Convention: the diagonal slots hold 1 / U_jj (what the solves multiply by);
 // only chol_solve / chol_inverse read a factor.
-template <int NP>
+// M (StructDense / StructTip): entries outside the mask are exact zeros of A
+// and of U and are skipped, the kept operations in the dense order.
+template <int NP, class M = StructDense>
 KF_HD bool chol_packed(float (&A)[ntri(NP)]) {
+  static_assert(struct_closed<NP, M>(), "the elimination must create no fill outside the structure mask");
   bool ok = true;
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
     float s = A[tri(NP, j, j)];
 #pragma unroll
-    for (int k = 0; k < j; ++k) s = fmaf(-A[tri(NP, k, j)], A[tri(NP, k, j)], s);
+    for (int k = 0; k < j; ++k)
+      if (M::on(k, j)) s = fmaf(-A[tri(NP, k, j)], A[tri(NP, k, j)], s);
     ok = ok && (s > 0.f) && finitef(s);
     s = s > 0.f ? s : 1.f;
     const float inv = kf_rsqrt(s);
     A[tri(NP, j, j)] = inv;
 #pragma unroll
     for (int i = j + 1; i < NP; ++i) {
+      if (!M::on(j, i)) continue;
       float t = A[tri(NP, j, i)];
 #pragma unroll
-      for (int k = 0; k < j; ++k) t = fmaf(-A[tri(NP, k, j)], A[tri(NP, k, i)], t);
+      for (int k = 0; k < j; ++k)
+        if (M::on(k, j) && M::on(k, i)) t = fmaf(-A[tri(NP, k, j)], A[tri(NP, k, i)], t);
       A[tri(NP, j, i)] = t * inv;
     }
   }
@@ -520,20 +584,22 @@ KF_HD bool chol_packed(float (&A)[ntri(NP)]) {
 }
 
 // Solve U^T U x = b with U from chol_packed (b overwritten by x).
-template <int NP>
+template <int NP, class M = StructDense>
 KF_HD void chol_solve(const float (&U)[ntri(NP)], float (&b)[NP]) {
 #pragma unroll
   for (int i = 0; i < NP; ++i) {  // U^T z = b
     float t = b[i];
 #pragma unroll
-    for (int k = 0; k < i; ++k) t = fmaf(-U[tri(NP, k, i)], b[k], t);
+    for (int k = 0; k < i; ++k)
+      if (M::on(k, i)) t = fmaf(-U[tri(NP, k, i)], b[k], t);
     b[i] = t * U[tri(NP, i, i)];
   }
 #pragma unroll
   for (int i = NP - 1; i >= 0; --i) {  // U x = z
     float t = b[i];
 #pragma unroll
-    for (int k = i + 1; k < NP; ++k) t = fmaf(-U[tri(NP, i, k)], b[k], t);
+    for (int k = i + 1; k < NP; ++k)
+      if (M::on(i, k)) t = fmaf(-U[tri(NP, i, k)], b[k], t);
     b[i] = t * U[tri(NP, i, i)];
   }
 }
@@ -552,13 +618,14 @@ KF_HD void chol_inverse(const float (&U)[ntri(NP)], float (&Ainv)[ntri(NP)]) {
   }
 }
 
-template <int NP>
+template <int NP, class M = StructDense>
 KF_HD void symv(const float (&A)[ntri(NP)], const float (&x)[NP], float (&y)[NP]) {
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     float t = 0.f;
 #pragma unroll
-    for (int j = 0; j < NP; ++j) t = fmaf(A[sym<NP>(i, j)], x[j], t);
+    for (int j = 0; j < NP; ++j)
+      if (M::on(i, j)) t = fmaf(A[sym<NP>(i, j)], x[j], t);
     y[i] = t;
   }
 }
@@ -869,11 +936,16 @@ KF_HD void forecast_partial_mean(const KF_CONST_AS PropArgs* a, int64_t p, float
     xf[j] = ((a->prop_mask >> j) & 1u) ? a->m[j] * KF_PX(a->x_a, j * a->ld, p) : a->reset_mean[j];
 }
 
-template <int NP>
+// M: the entries outside the structure mask (exact zeros of reset_cinv,
+// AnalysisArgs.a_struct) are not loaded.
+template <int NP, class M = StructDense>
 KF_HD void forecast_partial_precision(const KF_CONST_AS PropArgs* a, int64_t p, float (&P)[ntri(NP)]) {
   const int64_t ld = a->ld;
 #pragma unroll
-  for (int t = 0; t < ntri(NP); ++t) P[t] = a->reset_cinv[t];
+  for (int i = 0; i < NP; ++i)
+#pragma unroll
+    for (int j = i; j < NP; ++j)
+      if (M::on(i, j)) P[tri(NP, i, j)] = a->reset_cinv[tri(NP, i, j)];
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
     if ((a->prop_mask >> j) & 1u) {
@@ -883,9 +955,9 @@ KF_HD void forecast_partial_precision(const KF_CONST_AS PropArgs* a, int64_t p, 
   }
 }
 
-template <int NP>
+template <int NP, class M = StructDense>
 KF_HD void forecast_partial(const KF_CONST_AS PropArgs* a, int64_t p, float (&xf)[NP], float (&P)[ntri(NP)]) {
-  forecast_partial_precision<NP>(a, p, P);
+  forecast_partial_precision<NP, M>(a, p, P);
   forecast_partial_mean<NP>(a, p, xf);
 }
 
@@ -894,12 +966,15 @@ KF_HD int prop_single(uint32_t mask) { return (mask && !(mask & (mask - 1u))) ? 
 
 // forecast_partial with that parameter's x_a and P_a,jj already loaded (the
 // SPEC_PROP_PF kernels load the next pixel group's ahead): the same arithmetic.
-template <int NP>
+template <int NP, class M = StructDense>
 KF_HD void forecast_partial_pre(const KF_CONST_AS PropArgs* a, int64_t p, int j1, float xa1, float pa1,
                                 float (&xf)[NP], float (&P)[ntri(NP)]) {
   const int64_t ld = a->ld;
 #pragma unroll
-  for (int t = 0; t < ntri(NP); ++t) P[t] = a->reset_cinv[t];
+  for (int i = 0; i < NP; ++i)
+#pragma unroll
+    for (int j = i; j < NP; ++j)
+      if (M::on(i, j)) P[tri(NP, i, j)] = a->reset_cinv[tri(NP, i, j)];
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
     if (j == j1) {
@@ -1028,12 +1103,29 @@ KF_HD void pixel_propagate(const PropArgs& a, int64_t p) {
 }
 
 // Full-form right-hand side b = r + A x0 from the correction form r (DELTA).
-template <int NP>
+template <int NP, class M = StructDense>
 KF_HD void delta_to_full(const float (&A)[ntri(NP)], const float (&x0)[NP], float (&b)[NP]) {
   float t[NP];
-  symv<NP>(A, x0, t);
+  symv<NP, M>(A, x0, t);
 #pragma unroll
   for (int j = 0; j < NP; ++j) b[j] += t[j];
+}
+
+// The packed precision rows selected by AnalysisArgs.a_rows.  A masked-out row
+// is not held in A: its value is the forecast's constant (an exact zero).
+template <int NP, class M, typename AP>
+KF_HD void store_a_rows(AP a, int64_t p, const float (&A)[ntri(NP)]) {
+  const int64_t ld = a->ld;
+#pragma unroll
+  for (int i = 0; i < NP; ++i)
+#pragma unroll
+    for (int j = i; j < NP; ++j) {
+      const int t = tri(NP, i, j);
+      if (a_row_on(a->a_rows, t)) {
+        if (M::on(i, j)) KF_PXS(a->a_out, t * ld, p) = A[t];
+        else KF_PXS(a->a_out, t * ld, p) = opaque(cptr(a->prop))->reset_cinv[t];
+      }
+    }
 }
 
 // K1 epilogue: store (A, b) if requested, factor and solve, health fallback
@@ -1054,8 +1146,10 @@ KF_HD void delta_to_full(const float (&A)[ntri(NP)], const float (&x0)[NP], floa
 // (two inlined copies of the solve may be scheduled / contracted differently).
 // SPEC (kf_device.h SPEC_*): the launch's forecast / regulariser known at
 // compile time -- SPEC_PROP: fused forecast, no regulariser; SPEC_PROP_REG:
-// fused forecast and regulariser; SPEC_ANY: decided from the arguments.
-template <int NP, bool DELTA = false, int SPEC = SPEC_ANY, typename AP>
+// fused forecast and regulariser; SPEC_ANY: decided from the arguments; the
+// SPEC_*_TIP twins with the structure-aware solve.  M: the structure mask of A
+// (the host runner passes StructTip with SPEC_ANY).
+template <int NP, bool DELTA = false, int SPEC = SPEC_ANY, class M = typename SpecMask<SPEC>::type, typename AP>
 KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[NP], const float (&x0)[NP],
                               uint8_t st, bool store = true, bool final_it = true) {
   constexpr int NT = ntri(NP);
@@ -1065,8 +1159,8 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
 #pragma unroll
     for (int j = 0; j < NP; ++j) KF_PXS(a->x0_out, j * ld, p) = x0[j];
   }
-  const bool reg = (SPEC == SPEC_PROP_REG || (SPEC == SPEC_ANY && a->reg_v)) && final_it;
-  if (DELTA && (reg || a->b_out)) delta_to_full<NP>(A, x0, b);
+  const bool reg = (spec_base(SPEC) == SPEC_PROP_REG || (SPEC == SPEC_ANY && a->reg_v)) && final_it;
+  if (DELTA && (reg || a->b_out)) delta_to_full<NP, M>(A, x0, b);
   if (reg) {
     int deg = 0;
     if (a->reg_geo.w > 0) {
@@ -1080,16 +1174,12 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
 #pragma unroll
     for (int j = 0; j < NP; ++j)
       if ((a->reg_mask >> j) & 1u) A[tri(NP, j, j)] += gd;
-    if (store && a->a_out) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-          if (a_row_on(a->a_rows, t)) KF_PXS(a->a_out, t * ld, p) = A[t];
-    }
+    if (store && a->a_out) store_a_rows<NP, M>(a, p, A);
     float dA[NP];   // output uncertainty: 1/sqrt(diag) of the regularised precision
 #pragma unroll
     for (int j = 0; j < NP; ++j) dA[j] = A[tri(NP, j, j)];
-    const bool spd = chol_packed<NP>(A);
-    chol_solve<NP>(A, b);
+    const bool spd = chol_packed<NP, M>(A);
+    chol_solve<NP, M>(A, b);
     bool fin = true;
 #pragma unroll
     for (int j = 0; j < NP; ++j) fin = fin && finitef(b[j]);
@@ -1102,18 +1192,14 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
       st |= (!spd ? ST_NONSPD : 0) | (!fin ? ST_NONFINITE : 0) | ST_FALLBACK;
       float Af[NT];
       if (has_prop) {
-        forecast_partial<NP>(opaque(cptr(a->prop)), p, b, Af);
+        forecast_partial<NP, M>(opaque(cptr(a->prop)), p, b, Af);
       } else {
 #pragma unroll
         for (int j = 0; j < NP; ++j) b[j] = KF_PXS(a->x_f, j * ld, p);
 #pragma unroll
         for (int t = 0; t < NT; ++t) Af[t] = KF_PXS(a->pf_inv, t * ld, p);
       }
-      if (store && a->a_out) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          if (a_row_on(a->a_rows, t)) KF_PXS(a->a_out, t * ld, p) = Af[t];
-      }
+      if (store && a->a_out) store_a_rows<NP, M>(a, p, Af);
 #pragma unroll
       for (int j = 0; j < NP; ++j) dA[j] = Af[tri(NP, j, j)];
     }
@@ -1136,7 +1222,7 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
         float e[NP];
 #pragma unroll
         for (int j = 0; j < NP; ++j) e[j] = (j == r) ? 1.f : 0.f;
-        chol_solve<NP>(A, e);
+        chol_solve<NP, M>(A, e);
 #pragma unroll
         for (int j = 0; j < NP; ++j) KF_PXS(a->reg_v, ((int64_t)c * NP + j) * ld, p) = bad ? 0.f : e[j];
         ++c;
@@ -1145,11 +1231,7 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
     if (a->status) KF_PXS(a->status, 0, p) = st;
     return 0.f;
   }
-  if (store && a->a_out) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-          if (a_row_on(a->a_rows, t)) KF_PXS(a->a_out, t * ld, p) = A[t];
-  }
+  if (store && a->a_out) store_a_rows<NP, M>(a, p, A);
   if (store && a->b_out) {
 #pragma unroll
     for (int j = 0; j < NP; ++j) KF_PXS(a->b_out, j * ld, p) = b[j];
@@ -1159,8 +1241,8 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
     float dA[NP];   // analysis precision diagonal (output uncertainty) before the in-place factorisation
 #pragma unroll
     for (int j = 0; j < NP; ++j) dA[j] = A[tri(NP, j, j)];
-    const bool spd = chol_packed<NP>(A);
-    chol_solve<NP>(A, b);
+    const bool spd = chol_packed<NP, M>(A);
+    chol_solve<NP, M>(A, b);
     if (DELTA && !a->b_out) {
 #pragma unroll
       for (int j = 0; j < NP; ++j) b[j] += x0[j];
@@ -1172,7 +1254,7 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
       // Health fallback: keep the forecast (prior) for this pixel.
       st |= (!spd ? ST_NONSPD : 0) | (!fin ? ST_NONFINITE : 0) | ST_FALLBACK;
       if (has_prop) {
-        forecast_partial<NP>(opaque(cptr(a->prop)), p, b, A);   // rare path: recompute instead of keeping it live
+        forecast_partial<NP, M>(opaque(cptr(a->prop)), p, b, A);   // rare path: recompute instead of keeping it live
       } else {
 #pragma unroll
         for (int j = 0; j < NP; ++j) b[j] = KF_PXS(a->x_f, j * ld, p);
@@ -1181,11 +1263,7 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
       }
 #pragma unroll
       for (int j = 0; j < NP; ++j) dA[j] = A[tri(NP, j, j)];
-      if (store && a->a_out) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          if (a_row_on(a->a_rows, t)) KF_PXS(a->a_out, t * ld, p) = A[t];
-      }
+      if (store && a->a_out) store_a_rows<NP, M>(a, p, A);
     }
     if (store) {
 #pragma unroll
@@ -1224,22 +1302,24 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
 // FD == FD_PRECOMP: every band has a precomputed operator (split GP path).
 // Prior part of the right-hand side: P_f^-1 x_f (full form) or P_f^-1 (x_f - x0)
 // (correction form, DELTA; 0 when linearising at the forecast).
-template <int NP, bool DELTA>
+template <int NP, bool DELTA, class M = StructDense>
 KF_HD void prior_rhs(const float (&A)[ntri(NP)], const float (&xf)[NP], const float (&x0)[NP], float (&b)[NP]) {
   if (DELTA) {
     float d[NP];
 #pragma unroll
     for (int j = 0; j < NP; ++j) d[j] = xf[j] - x0[j];
-    symv<NP>(A, d, b);
+    symv<NP, M>(A, d, b);
   } else {
-    symv<NP>(A, xf, b);
+    symv<NP, M>(A, xf, b);
   }
 }
 
 // DELTA (correction form, analysis_epilogue) for the GP and precomputed
 // operators; the linear operators keep the full form, whose y' = y - offset
 // makes a repeated iteration exact (static convergence, linear_kf.py).
-template <int NP, int FD = 0, int FOBS = 0, int UNR = 4, bool FOLD = false>
+// M: the structure of A under a fused forecast (AnalysisArgs.a_struct; the host
+// runner's StructTip path): the bands' Jacobians are exact zeros outside it.
+template <int NP, int FD = 0, int FOBS = 0, int UNR = 4, bool FOLD = false, class M = StructDense>
 KF_HD float pixel_analysis(const AnalysisArgs& a, int64_t p, float& dn_first) {
   constexpr bool DELTA = FD > 0 || FD == FD_PRECOMP;
   constexpr int NT = ntri(NP);
@@ -1257,7 +1337,7 @@ KF_HD float pixel_analysis(const AnalysisArgs& a, int64_t p, float& dn_first) {
     // fused propagation: forecast of this pixel from the previous analysis,
     // never written to HBM (saves the propagate pass and its 2 x 140 B/px)
     float xf[NP];
-    forecast_partial<NP>(opaque(cptr(a.prop)), p, xf, A);
+    forecast_partial<NP, M>(opaque(cptr(a.prop)), p, xf, A);
     if (!a.x_prev && it == 0) {
 #pragma unroll
       for (int j = 0; j < NP; ++j) x0[j] = xf[j];
@@ -1267,7 +1347,7 @@ KF_HD float pixel_analysis(const AnalysisArgs& a, int64_t p, float& dn_first) {
 #pragma unroll
       for (int j = 0; j < NP; ++j) b[j] = 0.f;
     } else {
-      prior_rhs<NP, DELTA>(A, xf, x0, b);
+      prior_rhs<NP, DELTA, M>(A, xf, x0, b);
     }
   } else if (a.a_in) {
     // band-chunked accumulation: continue from a previous chunk's (A, b)
@@ -1354,7 +1434,8 @@ KF_HD float pixel_analysis(const AnalysisArgs& a, int64_t p, float& dn_first) {
       const float wh = w * h[i];
       b[i] = fmaf(h[i], wy, b[i]);
 #pragma unroll
-      for (int j = i; j < NP; ++j) A[tri(NP, i, j)] = fmaf(wh, h[j], A[tri(NP, i, j)]);
+      for (int j = i; j < NP; ++j)
+        if (M::on(i, j)) A[tri(NP, i, j)] = fmaf(wh, h[j], A[tri(NP, i, j)]);
     }
   }
   if (nobs == 0) st |= ST_NO_OBS;
@@ -1373,7 +1454,7 @@ KF_HD float pixel_analysis(const AnalysisArgs& a, int64_t p, float& dn_first) {
     // (outputs stored, its norm the first one, the second's exactly 0)
     const bool lin2 = FD == FD_LINEAR && it + 1 < ka->gn_fused && !ka->reg_v && !ka->x0_out;
     const bool last = it + 1 >= ka->gn_fused || lin2;
-    dn = analysis_epilogue<NP, DELTA>(ka, p, A, b, x0, st, last, last);
+    dn = analysis_epilogue<NP, DELTA, SPEC_ANY, M>(ka, p, A, b, x0, st, last, last);
     if (lin2) {
       dn_first = dn;
       return 0.f;
@@ -1384,7 +1465,7 @@ KF_HD float pixel_analysis(const AnalysisArgs& a, int64_t p, float& dn_first) {
   {
     const bool lin2 = FD == FD_LINEAR && it + 1 < a.gn_fused && !a.reg_v && !a.x0_out;
     const bool last = it + 1 >= a.gn_fused || lin2;
-    dn = analysis_epilogue<NP, DELTA>(&a, p, A, b, x0, st, last, last);
+    dn = analysis_epilogue<NP, DELTA, SPEC_ANY, M>(&a, p, A, b, x0, st, last, last);
     if (lin2) {
       dn_first = dn;
       return 0.f;

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(BS, MINW) void analysis_mfma_kernel(AnalysisArgs a)
   const int lane = threadIdx.x & 63;
   const int64_t stride = (int64_t)gridDim.x * BS;
   const int64_t nv = visit_count(a);
-  if constexpr (SPEC == SPEC_PROP_PF) {
+  if constexpr (spec_base(SPEC) == SPEC_PROP_PF) {
     // small emulators (short GP loops): the next pixel group's index and its
     // single propagated parameter's x_a / P_a,jj are loaded before this group's
     // analysis, so the forecast starts from registers instead of a dependent
@@ -587,14 +587,21 @@ static bool l_analysis_fast(const AnalysisArgs& a, int grid, hipStream_t s, int*
   }
       // JRC-TIP layout with the forecast fused (every date after the first):
       // the launch's paths fixed at compile time (SPEC_PROP / SPEC_PROP_REG,
-      // kf_core.h); AV_GENERIC_SPEC: the generic kernel
+      // kf_core.h); AV_GENERIC_SPEC: the generic kernel.  With the JRC-TIP zero
+      // structure of the forecast precision (AnalysisArgs.a_struct, checked on
+      // the host) their SPEC_*_TIP twins with the structure-aware solve;
+      // AV_DENSE_SOLVE: the dense kernels all the same
 #define KF_MFMA_GO_SPEC(OBS_, BS_, MINW_, LAY_)                                                      \
   {                                                                                                 \
     constexpr bool IL_ = gpm_il_default<NP, LAY_>();                                                \
+    const bool tips = (a.a_struct & A_STRUCT_TIP) && a.variant != AV_DENSE_SOLVE;                   \
     if (!a.prop || a.variant == AV_BLOCK_ORDER || a.variant == AV_GENERIC_SPEC)                     \
       KF_MFMA_GO(OBS_, BS_, MINW_, LAY_)                                                            \
+    else if (a.reg_v && tips) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_REG_TIP)          \
     else if (a.reg_v) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_REG)                      \
+    else if (small && tips) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_PF_TIP)              \
     else if (small) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_PF)                          \
+    else if (tips) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_TIP)                          \
     else KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP)                                        \
   }
       // Launch bound of 3 workgroups per CU (MINW = 3, as the LDS tables

@@ -100,6 +100,18 @@ __device__ __forceinline__ float gpm_partner32(float x) {
   return __builtin_bit_cast(float, (threadIdx.x & 32) ? r[0] : r[1]);
 }
 
+// Both results of one v_permlane32_swap of the pair (a, b): the swap exchanges
+// the upper wave half of a with the lower wave half of b, so
+//   lo: lanes h = 0 their own a, lanes h = 1 their partner's b
+//   hi: lanes h = 0 their partner's a, lanes h = 1 their own b
+// which is what a select of own / gpm_partner32 values would give, with no
+// select.  Called unconditionally from every lane, as gpm_partner32.
+__device__ __forceinline__ void gpm_swap32(uint32_t a, uint32_t b, uint32_t& lo, uint32_t& hi) {
+  const auto r = __builtin_amdgcn_permlane32_swap(a, b, true, false);
+  lo = r[0];
+  hi = r[1];
+}
+
 __device__ __forceinline__ void gpm_split16(float v, _Float16& h, _Float16& l) {
   h = (_Float16)v;
   l = (_Float16)(v - (float)h);
@@ -107,15 +119,15 @@ __device__ __forceinline__ void gpm_split16(float v, _Float16& h, _Float16& l) {
 
 // Both 32-pixel column blocks' exponent B operands: the lane splits and packs
 // its OWN pixel's values into both K halves (F0: slots 16kk..+7, F1:
-// 16kk+8..+15) and sends the half its partner l ^ 32 needs, so each value is
-// split once and one dword per fragment register crosses the wave halves.
+// 16kk+8..+15) and exchanges the half its partner l ^ 32 needs, so each value
+// is split once and one v_permlane32_swap of the dword pair (F0, F1) per
+// fragment register yields both blocks' operands (gpm_swap32: no selects).
 //   block 0 (pixels 0..31):  lanes h = 0 own F0, lanes h = 1 the partner's F1
 //   block 1 (pixels 32..63): lanes h = 0 the partner's F0, lanes h = 1 own F1
 // cl: the lane's own c - f16(c), applied to its sums afterwards.
 template <int D>
 __device__ __forceinline__ void gpm_operands(const float (&xi)[D], float c, kf_h8 (&xb)[2][gpm_k_steps(D)],
                                              float& cl) {
-  const bool h1 = (threadIdx.x & 32) != 0;
   _Float16 xh[D], xl[D];
 #pragma unroll
   for (int d = 0; d < D; ++d) gpm_split16(fminf(fmaxf(xi[d], -6.0e4f), 6.0e4f), xh[d], xl[d]);
@@ -128,11 +140,12 @@ __device__ __forceinline__ void gpm_operands(const float (&xi)[D], float c, kf_h
     kf_u4 b0, b1;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      // h = 0 sends F1 (its partner's half), h = 1 sends F0
-      const uint32_t send = h1 ? f0[q] : f1[q];
-      const uint32_t recv = __builtin_bit_cast(uint32_t, gpm_partner32(__builtin_bit_cast(float, send)));
-      b0[q] = h1 ? recv : f0[q];
-      b1[q] = h1 ? f1[q] : recv;
+      // h = 0 keeps F0 and receives its partner's F0 for block 1, h = 1 keeps
+      // F1 and receives its partner's F1 for block 0: one swap of (F0, F1)
+      uint32_t lo, hi;
+      gpm_swap32(f0[q], f1[q], lo, hi);
+      b0[q] = lo;
+      b1[q] = hi;
     }
     xb[0][kk] = __builtin_bit_cast(kf_h8, b0);
     xb[1][kk] = __builtin_bit_cast(kf_h8, b1);
@@ -141,21 +154,26 @@ __device__ __forceinline__ void gpm_operands(const float (&xi)[D], float c, kf_h
 
 // The lane's own pixel (32 h + col) is column col of block h.  Field f of
 // that column sits in register (f&3) + 4(f>>3) of lane 32 ((f>>2)&1) + col,
-// the lane itself or its partner l ^ 32, so each lane sends the OTHER block's
-// value (the one its partner's pixel needs): one exchange per field.  The lo
-// row LO + f of the same field is register + LO/2 of the same lane.
+// the lane itself or its partner l ^ 32, so each lane hands over the OTHER
+// block's value (the one its partner's pixel needs): one swap of the two blocks'
+// sums per register, which delivers fields f and f + 4 at once (4 swaps for the
+// five JRC-TIP fields).  The lo row LO + f of the same field is register + LO/2
+// of the same lane.
 template <int D>
 __device__ __forceinline__ void gpm_extract2(const kf_f16v (&acc)[2], float (&S)[D + 1]) {
   constexpr int LR = gpm_lo_row(D) / 2;
-  const bool h1 = (threadIdx.x & 32) != 0;
+  // Register r holds field f of the lanes h = 0 and field f + 4 of the lanes
+  // h = 1, for both blocks: one swap of the pair (block 0 sum, block 1 sum)
+  // hands every lane its own pixel's field f (lo) and field f + 4 (hi).
 #pragma unroll
   for (int f = 0; f <= D; ++f) {
+    if ((f >> 2) & 1) continue;   // delivered with field f - 4
     const int r = (f & 3) + 4 * (f >> 3);
     const float a0 = acc[0][r] + acc[0][r + LR], a1 = acc[1][r] + acc[1][r + LR];
-    const float own = h1 ? a1 : a0;
-    const float send = h1 ? a0 : a1;
-    const float recv = gpm_partner32(send);
-    S[f] = (((f >> 2) & 1) == (h1 ? 1 : 0)) ? own : recv;
+    uint32_t lo, hi;
+    gpm_swap32(__builtin_bit_cast(uint32_t, a0), __builtin_bit_cast(uint32_t, a1), lo, hi);
+    S[f] = __builtin_bit_cast(float, lo);
+    if (f + 4 <= D) S[f + 4] = __builtin_bit_cast(float, hi);
   }
 }
 
@@ -580,6 +598,13 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
   // band loop unrolled with both maps compile-time (no runtime map branches
   // and no register copies at their joins)
   static_assert(LAYOUT == BAND_LAYOUT_RUNTIME || (NP == 7 && D == 4 && !GT), "JRC-TIP layout: 7 params, 4 inputs");
+  // SPEC_*_TIP: A has the JRC-TIP zero structure (StructTip, host-checked:
+  // AnalysisArgs.a_struct); the masked-out entries are neither loaded nor held,
+  // and the two compile-time band maps update kept entries only
+  typedef typename SpecMask<SPEC>::type M;
+  constexpr int SB = spec_base(SPEC);
+  constexpr bool SPARSE = spec_sparse(SPEC);
+  static_assert(!SPARSE || LAYOUT == BAND_LAYOUT_TIP, "the structure mask is the JRC-TIP layout's");
   const int64_t ld = a.ld;
   float x0[NP], A[NT], b[NP];
   if (a.x_prev) {
@@ -597,10 +622,10 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
     float xf[NP];
     // SPEC_PROP_PF: the single propagated parameter's x_a / P_a,jj of the first
     // iteration were loaded ahead by the kernel's loop (pre_j >= 0)
-    if (SPEC == SPEC_PROP_PF && pre_j >= 0 && it == 0)
-      forecast_partial_pre<NP>(opaque(cptr(a.prop)), p, pre_j, pre_x, pre_p, xf, A);
+    if (SB == SPEC_PROP_PF && pre_j >= 0 && it == 0)
+      forecast_partial_pre<NP, M>(opaque(cptr(a.prop)), p, pre_j, pre_x, pre_p, xf, A);
     else
-      forecast_partial<NP>(opaque(cptr(a.prop)), p, xf, A);
+      forecast_partial<NP, M>(opaque(cptr(a.prop)), p, xf, A);
     if (!a.x_prev && it == 0) {
       // linearised at the forecast: the prior part P_f^-1 (x_f - x0) is 0
 #pragma unroll
@@ -609,7 +634,7 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
         b[j] = 0.f;
       }
     } else {
-      prior_rhs<NP, true>(A, xf, x0, b);
+      prior_rhs<NP, true, M>(A, xf, x0, b);
     }
   } else if (a.a_in) {
 #pragma unroll
@@ -630,6 +655,7 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
   }
   int nobs = 0;
   int off = 0;
+  bool wave_obs = false;   // wave-uniform: some lane has an observation of some band
   // BAND_LAYOUT_SHARED_X (global tables, full-state GPs around one centre):
   // the exponent operand of the centred inputs once per iteration, each band
   // patches its constant in (gpm_patch_c).  AV_PER_BAND_OPERAND: per band (oracle).
@@ -654,6 +680,14 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
   // first date's launch, without one, and the generic oracle, variant 18)
   const bool line = SPEC != SPEC_ANY && it == 0 && !a.x_prev &&
                     opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->line_tab;
+  // the lane's table interval is the same for every band: the structure-aware
+  // kernels find it once per iteration instead of once per band
+  LinePos lp_it{nullptr, 0.f, false};
+  if constexpr (SPARSE) {
+    if (line)
+      lp_it = line_pos<NP>(opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr()), x0,
+                           a.n_bands * (D + 1) * 4);
+  }
   // one band: GP sums on the matrix cores, value and Jacobian, normal equations.
   // MKC: the band's map kind when known at compile time (LAYOUT), else -1
   auto band = [&](int bi, auto mkc) {
@@ -671,18 +705,28 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
     constexpr bool TIPK = NP == 7 && D == 4;
     const int mk = MKC >= 0 ? MKC : (TIPK ? bdp->map_kind : GPM_MAP_RUNTIME);
     const bool any = __any(use);
+    wave_obs = wave_obs || any;
     bool tabled = false;
     if (any && line) {
       // wave-uniform: every observed lane's x_f,j inside the table
-      const KF_CONST_AS AnalysisArgs* la =
-          opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr());
-      const LinePos lp = line_pos<NP>(la, x0, a.n_bands * (D + 1) * 4);
+      LinePos lp = lp_it;
+      if constexpr (!SPARSE) {
+        const KF_CONST_AS AnalysisArgs* la =
+            opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr());
+        lp = line_pos<NP>(la, x0, a.n_bands * (D + 1) * 4);
+      }
       if (__all(lp.in || !use)) {
         line_eval<D>(lp.row + bi * (D + 1) * 4, lp.s, H0, g);
         tabled = true;
-        ok = finitef(H0);
+        // the table's coefficients are finite and bounded (checked where the
+        // host builds it, models/gp.py:line_table) and s is in [0, 1], so the
+        // cubics are finite: the structure-aware kernels drop the class tests
+        ok = true;
+        if constexpr (!SPARSE) {
+          ok = finitef(H0);
 #pragma unroll
-        for (int d = 0; d < D; ++d) ok = ok && finitef(g[d]);
+          for (int d = 0; d < D; ++d) ok = ok && finitef(g[d]);
+        }
       }
     }
     if (any && !tabled) {
@@ -780,9 +824,66 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
   if (nobs == 0) st |= ST_NO_OBS;
   const KF_CONST_AS AnalysisArgs* ka =
       opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr());
+  if constexpr (SPEC == SPEC_PROP_TIP || SPEC == SPEC_PROP_PF_TIP) {
+    // Unobserved wave (the cloudy pixels fill whole waves under the observed-
+    // first order) linearised at the forecast: A = P_f^-1 and b = 0, so every
+    // fused iteration solves to x = x_f + 0 with norm 0 and the analysis
+    // precision is the forecast's.  Written directly, without the factor-and-
+    // solve of each iteration, when every lane is healthy -- the pivots the
+    // factorisation would test, which for a prior precision that is diagonal
+    // plus (2, 5) (A_STRUCT_TIP_PRIOR) are the diagonal entries and the (5, 5)
+    // pivot below, in its operations -- so that no lane would take the health
+    // fallback or set a status bit other than these.  Any other wave takes the
+    // full path.
+    if (it == 0 && !a.x_prev && !wave_obs && (ka->a_struct & A_STRUCT_TIP_PRIOR) && ka->solve && !ka->b_out) {
+      bool healthy = true;
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        float s = A[tri(NP, j, j)];
+        if (j == 5) {
+          const float s2 = A[tri(NP, 2, 2)];
+          const float u25 = A[tri(NP, 2, 5)] * kf_rsqrt(s2 > 0.f ? s2 : 1.f);
+          s = fmaf(-u25, u25, s);
+        }
+        healthy = healthy && (s > 0.f) && finitef(s) && finitef(x0[j]);
+      }
+      if (__all(healthy)) {
+        st = ST_NO_OBS;
+        float x1[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) x1[j] = x0[j] + 0.f;   // the solve's x0 + A^-1 0
+        if (state_out_of_domain<NP>(ka, x1)) st |= ST_OUT_OF_DOMAIN;
+        if (act) {
+          if (ka->x0_out) {
+#pragma unroll
+            for (int j = 0; j < NP; ++j) KF_PXS(ka->x0_out, j * ld, p) = ka->gn_fused > 1 ? x1[j] : x0[j];
+          }
+          if (ka->a_out) store_a_rows<NP, M>(ka, p, A);
+#pragma unroll
+          for (int j = 0; j < NP; ++j) KF_PXS(ka->x_out, j * ld, p) = x1[j];
+          if (ka->out_unc) {
+            const int64_t r = ka->out_idx ? KF_PXS(ka->out_idx, 0, p) : p;
+            const int64_t pl = ka->out_plane;
+            if (ka->out_mean) {
+#pragma unroll
+              for (int j = 0; j < NP; ++j) KF_PXS(ka->out_mean, j * pl, r) = x1[j];
+            }
+#pragma unroll
+            for (int j = 0; j < NP; ++j) KF_PXS(ka->out_unc, j * pl, r) = kf_rsqrt(A[tri(NP, j, j)]);
+          }
+          if (ka->status) KF_PXS(ka->status, 0, p) = st;
+        }
+        KF_PHASE(KF_PH_SOLVE)
+        return 0.f;
+      }
+    }
+  }
   // the linearisation point outside the GP bands' domain box (state space, one
-  // test for every band: AnalysisArgs.dom_*)
-  if (state_out_of_domain<NP>(ka, x0)) st |= ST_OUT_OF_DOMAIN;
+  // test for every band: AnalysisArgs.dom_*); an intermediate fused iteration's
+  // status is not stored, so the structure-aware kernels test the last one only
+  if (!SPARSE || it + 1 >= ka->gn_fused) {
+    if (state_out_of_domain<NP>(ka, x0)) st |= ST_OUT_OF_DOMAIN;
+  }
   // one epilogue call site for the fused intermediate and the final iteration
   // (bit-identical intermediate x, kf_core.h); tail lanes (act = false) solve
   // too but store nothing: their x0 only feeds the next iteration's MFMA

@@ -43,6 +43,9 @@ template <int NP>
 static int h_analysis(const AnalysisArgs& a, int grid) {
   const int64_t stride = (int64_t)grid * HBLOCK;
   const int64_t nv = visit_count(a);
+  // JRC-TIP structure of the fused forecast's precision (AnalysisArgs.a_struct,
+  // checked by the caller): the structure-aware solve, as the SPEC_*_TIP kernels
+  const bool tip = NP == 7 && (a.a_struct & A_STRUCT_TIP) && a.prop && a.variant != AV_DENSE_SOLVE;
 #pragma omp parallel for schedule(dynamic, 4)
   for (int b = 0; b < grid; ++b) {
     double acc = 0.0, acc1 = 0.0;
@@ -50,7 +53,12 @@ static int h_analysis(const AnalysisArgs& a, int grid) {
       for (int64_t q = (int64_t)b * HBLOCK + t; q < nv; q += stride) {
         float dn1;
         const int64_t p = visit_px(a.order, q);
-        const float dn = pixel_analysis<NP>(a, p, dn1);
+        float dn;
+        if constexpr (NP == 7) {
+          dn = tip ? pixel_analysis<NP, 0, 0, 4, false, StructTip>(a, p, dn1) : pixel_analysis<NP>(a, p, dn1);
+        } else {
+          dn = pixel_analysis<NP>(a, p, dn1);
+        }
         if (a.dn_out) a.dn_out[p] = dn;
         acc += (double)dn;
         acc1 += (double)dn1;

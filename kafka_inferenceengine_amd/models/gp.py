@@ -457,6 +457,17 @@ def line_range(specs, j: int, margin: float = 0.5):
     return lo - margin * w, hi + margin * w
 
 
+LINE_COEF_MAX = 1e30   # |coefficient| bound: a cubic in s in [0, 1] of four such terms is finite in float32
+
+
+def _line_coef_ok(coef) -> bool:
+    """The kernels evaluate a tabled band without testing the value and the
+    gradient for finiteness (kf_gp_mfma.h, structure-aware kernels), so a table
+    is handed out only when its float32 coefficients are finite and bounded."""
+    c = np.asarray(coef, dtype=np.float64).astype(np.float32)
+    return bool(np.isfinite(c).all() and (np.abs(c) < LINE_COEF_MAX).all())
+
+
 def line_table(specs, fixed, j: int):
     """Cubic Hermite line tables of every band of ``specs`` (all GP with the same
     input count D) for the kernels' first iteration at a partial-reset forecast:
@@ -472,7 +483,7 @@ def line_table(specs, fixed, j: int):
         cols = [line_functions(sp, fixed, -1, np.zeros(1))[0][0] for sp in specs]
         out = np.zeros((1, len(specs), D + 1, 4))
         out[0, :, :, 0] = np.stack(cols)
-        return out.astype(np.float32), 0.0, 1.0, 1
+        return (out.astype(np.float32), 0.0, 1.0, 1) if _line_coef_ok(out) else None
     rng = line_range(specs, j)
     if rng is None:
         return None
@@ -500,7 +511,7 @@ def line_table(specs, fixed, j: int):
             pm = c[..., 0] + 0.5 * c[..., 1] + 0.25 * c[..., 2] + 0.125 * c[..., 3]
             worst = max(worst, float((np.abs(pm - Fm) / np.maximum(scale, 1e-300)[:, None]).max()))
         if worst <= LINE_RTOL:
-            return coef.astype(np.float32), t0, float(1.0 / h), n
+            return (coef.astype(np.float32), t0, float(1.0 / h), n) if _line_coef_ok(coef) else None
         h *= 0.5
 
 

@@ -63,7 +63,7 @@ def _table_key(bands) -> tuple:
     if k is None:
         dom = None if bands.dom is None else (tuple(bands.dom[0]), tuple(bands.dom[1]))
         k = bands.__dict__["_memo_key"] = (bands.ptr, bands.n, bands.fast_d, bands.fast_obs, bands.gpm_frags,
-                                           bool(bands.gpm_global), bands.layout, dom)
+                                           bool(bands.gpm_global), bands.layout, dom, bool(bands.tip_maps))
     return k
 
 
@@ -131,6 +131,7 @@ class BandTable:
     layout: int = 0         # BAND_LAYOUT_*: a band layout the kernels know at compile time (0: runtime)
     dom: tuple | None = None  # GP domain box in state space (lo, hi lists; ST_OUT_OF_DOMAIN)
     specs: tuple = ()       # the bands' OperatorSpecs (line tables of the first iteration at the forecast)
+    tip_maps: bool = False  # exactly two 4-input GP bands with the JRC-TIP VIS then NIR state maps
 
     @property
     def ptr(self) -> int:
@@ -169,6 +170,7 @@ class Variant(IntEnum):
     PER_BAND_OPERAND = 14    # BAND_LAYOUT_SHARED_X: exponent operand rebuilt per band
     BLOCK_ORDER = 16         # exponent MFMAs block by block
     GENERIC_SPEC = 18        # fused forecast through the generic launch instead of SPEC_PROP
+    DENSE_SOLVE = 20         # the dense solve where the JRC-TIP structure would select the structure-aware one
 
 
 # analysis variant of launches that pass none (tests switch it to an oracle path;
@@ -256,8 +258,10 @@ def make_band_table(descs: list, device, keepalive=(), specs=()) -> BandTable:
     elif (gpm_global and fast_d % 2 == 0 and all(d.map_identity for d in descs)
           and len({tuple(d.center[:fast_d]) for d in descs}) == 1):
         layout = BAND_LAYOUT_SHARED_X
+    tip_maps = len(descs) == 2 and all(d.op == OP_GP and d.d == 4 for d in descs) and \
+        [d.map_kind for d in descs] == [2, 3]
     return BandTable(buf, len(descs), tuple(keepalive), fast_d, fast_obs, gpm_frags, gpm_global, layout,
-                     _state_domain(descs), tuple(specs))
+                     _state_domain(descs), tuple(specs), tip_maps)
 
 
 def _state_domain(descs):
@@ -330,6 +334,43 @@ def _set_line(a, bands, prop, n_params, dev, x_prev, line):
     lf = line_fields(bands, prop, n_params, dev)
     if lf is not None:
         a.line_tab, a.line_t0, a.line_inv_h, a.line_n, a.line_j = _ptr(lf[0]), lf[1], lf[2], lf[3], lf[4]
+
+
+# ------------------------------------------------------ JRC-TIP structure
+# kf_core.h A_STRUCT_*: the analysis precision's zero structure under a fused forecast
+A_STRUCT_TIP = 1
+A_STRUCT_TIP_PRIOR = 2
+# packed entries (i, j) the two JRC-TIP bands and the prior's (2, 5) pair never touch (kf_core.h StructTip)
+TIP_ZERO_ENTRIES = ((0, 3), (0, 4), (0, 5), (1, 3), (1, 4), (1, 5), (2, 3), (2, 4))
+# what the last analysis() launches took: "tip" the structure-aware solve, "dense" the dense one
+STRUCT_LAUNCHES = {"tip": 0, "dense": 0}
+
+
+def _tri(n, i, j):
+    return i * n - (i * (i - 1)) // 2 + (j - i)
+
+
+def tip_structure(n_params, bands: BandTable, prop, variant=None) -> int:
+    """``AnalysisArgs.a_struct`` of a launch with the fused forecast ``prop``:
+    ``A_STRUCT_TIP`` when the bands are the two JRC-TIP maps and the forecast's
+    constant precision (``reset_cinv``) is exactly 0.0 in the eight entries of
+    ``TIP_ZERO_ENTRIES`` -- every analysis precision then keeps those zeros, and
+    so does its Cholesky factor, which the structure-aware solve skips.
+    ``A_STRUCT_TIP_PRIOR`` in addition when that precision is diagonal plus the
+    (2, 5) pair and finite with finite reset means (the kernels' unobserved-wave
+    shortcut).  0 (the dense solve) otherwise and for every oracle variant."""
+    v = DEFAULT_VARIANT if variant is None else variant
+    if prop is None or n_params != 7 or not bands.tip_maps or int(v) != int(Variant.DEFAULT):
+        return 0
+    c = [float(x) for x in list(prop.args.reset_cinv)[:ntri(7)]]
+    if any(c[_tri(7, i, j)] != 0.0 for i, j in TIP_ZERO_ENTRIES):
+        return 0
+    flags = A_STRUCT_TIP
+    off = [c[_tri(7, i, j)] for i in range(7) for j in range(i + 1, 7) if (i, j) != (2, 5)]
+    mean = [float(x) for x in list(prop.args.reset_mean)[:7]]
+    if all(x == 0.0 for x in off) and all(np.isfinite(x) for x in c) and all(np.isfinite(x) for x in mean):
+        flags |= A_STRUCT_TIP_PRIOR
+    return flags
 
 
 # ------------------------------------------------------------------ ops
@@ -416,6 +457,8 @@ def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=
         hit = _ANALYSIS_MEMO.get(key)
         if hit is not None:
             a, grid = hit
+            if a.prop:
+                STRUCT_LAUNCHES["tip" if getattr(a, "a_struct", 0) else "dense"] += 1
             n_part = ext().analysis(n_params, a, grid, _dev(ref), _stream(ref))
             _set_valid(partials, n_part)
             _set_valid(partials_first if gn_fused == 2 else None, n_part)
@@ -546,6 +589,13 @@ def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=
         a.a_rows = int(a_rows)
     if fast:
         _set_line(a, bands, prop, n_params, dev, x_prev, line)
+    # the structure-aware solve: the matrix-core JRC-TIP layout kernels, or the host runner
+    # (an A/B module built from sources without the field, _build.py --exp: dense)
+    if prop is not None and a_in is None and hasattr(a, "a_struct") and (
+            dev.type != "cuda" or (fast and a.band_layout == BAND_LAYOUT_TIP and bands.fast_obs == OBS_DN16)):
+        a.a_struct = tip_structure(n_params, bands, prop, v)
+    if prop is not None:
+        STRUCT_LAUNCHES["tip" if getattr(a, "a_struct", 0) else "dense"] += 1
     grid = grid_for(nv)
     if partials is not None and partials.numel() < grid:
         raise ValueError("partials must hold one entry per workgroup (partials_buffer)")
