@@ -961,6 +961,21 @@ KF_HD void forecast_partial(const KF_CONST_AS PropArgs* a, int64_t p, float (&xf
   forecast_partial_mean<NP>(a, p, xf);
 }
 
+// Health of the fused forecast's precision P where it varies per pixel: every
+// propagated diagonal positive and finite (the rest is the launch's constant
+// reset precision).  Observations can lift an indefinite forecast precision to
+// an SPD analysis precision, which the factorisation of A alone cannot tell
+// from a healthy pixel's: the analysis sets ST_NONSPD ahead of the epilogue,
+// which then takes the health fallback.
+template <int NP>
+KF_HD bool forecast_partial_spd(const KF_CONST_AS PropArgs* a, const float (&P)[ntri(NP)]) {
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < NP; ++j)
+    if ((a->prop_mask >> j) & 1u) ok = ok && (P[tri(NP, j, j)] > 0.f) && finitef(P[tri(NP, j, j)]);
+  return ok;
+}
+
 // The propagated parameter when exactly one is (the LAI propagator: TLAI), else -1.
 KF_HD int prop_single(uint32_t mask) { return (mask && !(mask & (mask - 1u))) ? __builtin_ctz(mask) : -1; }
 
@@ -1178,7 +1193,8 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
     float dA[NP];   // output uncertainty: 1/sqrt(diag) of the regularised precision
 #pragma unroll
     for (int j = 0; j < NP; ++j) dA[j] = A[tri(NP, j, j)];
-    const bool spd = chol_packed<NP, M>(A);
+    // ST_NONSPD on entry: the caller found the fused forecast's precision unhealthy (forecast_partial_spd)
+    const bool spd = chol_packed<NP, M>(A) && !(st & ST_NONSPD);
     chol_solve<NP, M>(A, b);
     bool fin = true;
 #pragma unroll
@@ -1241,7 +1257,8 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
     float dA[NP];   // analysis precision diagonal (output uncertainty) before the in-place factorisation
 #pragma unroll
     for (int j = 0; j < NP; ++j) dA[j] = A[tri(NP, j, j)];
-    const bool spd = chol_packed<NP, M>(A);
+    // ST_NONSPD on entry: the caller found the fused forecast's precision unhealthy (forecast_partial_spd)
+    const bool spd = chol_packed<NP, M>(A) && !(st & ST_NONSPD);
     chol_solve<NP, M>(A, b);
     if (DELTA && !a->b_out) {
 #pragma unroll
@@ -1274,6 +1291,9 @@ KF_HD float analysis_epilogue(AP a, int64_t p, float (&A)[ntri(NP)], float (&b)[
       const float d = b[j] - x0[j];
       dn = fmaf(d, d, dn);
     }
+    // a fallback pixel whose forecast or linearisation point is not finite
+    // (NaN - NaN) counts 0: one dead pixel must not make the date's norm NaN
+    if ((st & ST_FALLBACK) && !finitef(dn)) dn = 0.f;
     if (store && a->out_unc) {
       // fused output dump: the unpack pass's work without re-reading x and A.
       // out_mean null: the state's x is the mean raster (dense strip, identity
@@ -1338,6 +1358,7 @@ KF_HD float pixel_analysis(const AnalysisArgs& a, int64_t p, float& dn_first) {
     // never written to HBM (saves the propagate pass and its 2 x 140 B/px)
     float xf[NP];
     forecast_partial<NP, M>(opaque(cptr(a.prop)), p, xf, A);
+    if (!forecast_partial_spd<NP>(opaque(cptr(a.prop)), A)) st |= ST_NONSPD;
     if (!a.x_prev && it == 0) {
 #pragma unroll
       for (int j = 0; j < NP; ++j) x0[j] = xf[j];
@@ -1737,6 +1758,7 @@ KF_HD float gain_pixel(const GA& a, int64_t p, bool act, float& dn1, EVAL&& eval
         dn1 = fmaf(d, d, dn1);
         x0[j] = x[j];
       }
+      if (!finitef(dn1)) dn1 = 0.f;   // a pixel on its way to the fallback (gain_finish) counts 0
       // through an opaque pixel index: recomputed, not kept live across iteration 1 (CSE)
       gain_load_forecast<NP>(a, opaque_lane(p), xf, P, cd, cd_ok);
       st = st_fc;
@@ -1824,6 +1846,8 @@ KF_HD float gain_finish(const GA& a, int64_t p, float (&x)[NP], float (&P)[ntri(
     const float d = x[j] - x0[j];
     dn = fmaf(d, d, dn);
   }
+  // as analysis_epilogue: a fallback pixel with a non-finite difference counts 0
+  if (!fin && !finitef(dn)) dn = 0.f;
   const bool need_pi = a.out_unc || (a.p_out && a.pdiag_rows);
   float pid[NP];
   if (need_pi) {

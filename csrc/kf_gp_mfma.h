@@ -626,6 +626,8 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
       forecast_partial_pre<NP, M>(opaque(cptr(a.prop)), p, pre_j, pre_x, pre_p, xf, A);
     else
       forecast_partial<NP, M>(opaque(cptr(a.prop)), p, xf, A);
+    // an unhealthy forecast precision: the epilogue takes the health fallback
+    if (!forecast_partial_spd<NP>(opaque(cptr(a.prop)), A)) st |= ST_NONSPD;
     if (!a.x_prev && it == 0) {
       // linearised at the forecast: the prior part P_f^-1 (x_f - x0) is 0
 #pragma unroll

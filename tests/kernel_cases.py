@@ -239,3 +239,268 @@ def dense_finish(device, h_total=30, w=44, ranks=3, rank=1, n=7, j0=6, out=True,
                  out=(mean, None if out == "mean" else unc, None) if out else None,
                  a_prec=a_prec if out is True else None)
     return xo[:, :N].cpu(), mean.cpu(), unc.cpu(), float(part_buf.sum())
+
+
+# --------------------------------------------------------------------------
+# Per-pixel fault containment (tests/test_gpu_containment.py): one corrupted
+# run "A" and its clean twin "B" over the same pixels, and a float64 model of
+# the forecast, the analysis and the status byte.
+CONTAIN_N = 6 * 64 + 27      # six whole waves and a tail wave of 27 lanes, natural order
+CONTAIN_Q = 0.04
+
+
+def px(wave, lane):
+    return 64 * wave + lane
+
+
+def _tip_dn_bands(prob, dn):
+    """prob["raw"] / prob["bands"] of the DN16 encoding for the DN arrays ``dn`` (0: no observation)."""
+    raw, bands = [], []
+    for d in dn:
+        yy = d * 1e-4
+        sig = np.maximum(0.05 * yy, 2.5e-3)
+        raw.append(dict(dn=np.where(d > 32767, d - 65536, d).astype(np.int16)))
+        bands.append((np.where(d > 0, yy, 0.0), np.where(d > 0, 1 / sig ** 2, 0.0)))
+    return dict(prob, raw=raw, bands=bands)
+
+
+def containment_spec(n=7, mask=1 << 6):
+    from kafka_inferenceengine_amd.utils.blocks import pack_matrix
+    mu, _, Pi = k.tip_prior()
+    return {"mode": 1, "m": np.ones(n), "q": np.full(n, CONTAIN_Q), "prop_mask": mask, "reset_mean": mu,
+            "reset_cinv": pack_matrix(Pi)}
+
+
+def containment_problem(n_train, seed=17, spatial=False):
+    """The JRC-TIP state of ``tip_problem(dn16=True)`` under the fused LAI
+    forecast (tests/test_gpu_line.py), CONTAIN_N pixels; wave w is pixels
+    64 w .. 64 w + 63.  Returns runs ``A`` (corrupted), ``B`` (its clean twin)
+    and ``M`` (A with the two pixels whose forecast mean is not finite replaced
+    by healthy unobserved ones, which contribute exactly 0 to the norm), each a
+    dict(prob, xa [N, 7], pa [N, 7, 7]); ``corrupt``: the pixels whose inputs
+    differ between A and B and are read; ``table``: the line table's range of
+    the propagated parameter.
+
+    wave 0  observed, clean
+    wave 1  observed; lane 3 x_a[6] = NaN, lane 9 p_a = -I, lane 17 p_a[6, 6] =
+            NaN, lane 33 x_a[6] = +inf, lane 40 both DN = 0, lane 63 x_a[2] =
+            NaN (the forecast does not read it: healthy)
+    wave 2  no lane observed, all healthy (the unobserved-wave shortcut)
+    wave 3  no lane observed, lane 35 p_a = -I (the shortcut declined)
+    wave 4  observed, lanes 5 and 44 finite outside the line table (A and B)
+    wave 5  lanes 0-31 observed inside the table, 32-63 unobserved, lanes 37 and
+            58 of those outside the table (A and B)
+    wave 6  27 lanes, observed; lane 26 (which the tail lanes repeat) p_a = -I
+
+    ``spatial``: seven whole waves (the rows of a raster 64 wide) and of A's
+    corruptions only lanes 9 and 17 of wave 1."""
+    from kafka_inferenceengine_amd.models.gp import line_table
+    N, n = (7 * 64 if spatial else CONTAIN_N), 7
+    prob = tip_problem(N=N, seed=seed, n_train=n_train, dn16=True, mask_frac=0.0)
+    rng = np.random.default_rng(seed + 1)
+    mu = k.tip_prior()[0]
+    pa = spd_blocks(rng, N, n, 5.0) * 0.2 + prob["Pf"]
+    xa = prob["x"].astype(np.float32).astype(np.float64)
+    dn = [np.where(r["dn"] < 0, r["dn"].astype(np.int32) + 65536, r["dn"]).astype(np.int32) for r in prob["raw"]]
+    assert all((d > 0).all() for d in dn)
+    special = [px(1, l) for l in (3, 9, 17, 33, 40, 63)] + [px(3, 35), px(4, 5), px(4, 44), px(6, 26)]
+    # observed waves: one band of every fifth ordinary pixel is missing
+    drop = rng.random(N) < 0.2
+    drop[special] = False
+    which = rng.integers(0, 2, N)
+    for b in range(2):
+        dn[b][drop & (which == b)] = 0
+    dark = np.zeros(N, bool)
+    dark[px(2, 0):px(4, 0)] = True
+    dark[px(5, 32):px(6, 0)] = True
+    for b in range(2):
+        dn[b][dark] = 0
+    tab = line_table(prob["specs"], np.asarray(mu, dtype=np.float32).astype(np.float64), 6)
+    assert tab is not None
+    t_lo, t_hi = tab[1], tab[1] + tab[3] / tab[2]
+    for p, v in ((px(4, 5), t_hi + 0.25), (px(4, 44), t_lo - 0.25), (px(5, 37), t_hi + 0.25),
+                 (px(5, 58), t_lo - 0.25)):
+        xa[p, 6] = np.float32(v)
+    inside = (xa[:, 6] >= t_lo) & (xa[:, 6] <= t_hi)
+    assert inside[px(5, 0):px(5, 32)].all() and inside[px(1, 0):px(2, 0)].all()
+    B = dict(prob=_tip_dn_bands(prob, dn), xa=xa, pa=pa)
+    xa_a, pa_a, dn_a = xa.copy(), pa.copy(), [d.copy() for d in dn]
+    corrupt = np.zeros(N, bool)
+    pa_a[px(1, 9)] = -np.eye(n)
+    pa_a[px(1, 17), 6, 6] = np.nan
+    corrupt[[px(1, 9), px(1, 17)]] = True
+    if not spatial:
+        xa_a[px(1, 3), 6] = np.nan
+        xa_a[px(1, 33), 6] = np.inf
+        xa_a[px(1, 63), 2] = np.nan
+        for p in (px(3, 35), px(6, 26)):
+            pa_a[p] = -np.eye(n)
+        for b in range(2):
+            dn_a[b][px(1, 40)] = 0
+        corrupt[[px(1, 3), px(1, 33), px(1, 40), px(3, 35), px(6, 26)]] = True
+    A = dict(prob=_tip_dn_bands(prob, dn_a), xa=xa_a, pa=pa_a)
+    xa_m, dn_m = xa_a.copy(), [d.copy() for d in dn_a]
+    for p in (px(1, 3), px(1, 33)):
+        xa_m[p] = xa[p]
+        for b in range(2):
+            dn_m[b][p] = 0
+    M = dict(prob=_tip_dn_bands(prob, dn_m), xa=xa_m, pa=pa_a)
+    # B with one NaN state in the unobserved wave 2: its only reason to decline the shortcut
+    xa_c = xa.copy()
+    xa_c[px(2, 20), 6] = np.nan
+    C = dict(prob=B["prob"], xa=xa_c, pa=pa)
+    return dict(A=A, B=B, M=M, C=C, corrupt=corrupt, table=(t_lo, t_hi), N=N, n=n)
+
+
+def chol_model(A, b):
+    """float64 model of the kernels' factor-and-solve (kf_core.h chol_packed,
+    chol_solve): a pivot that is not positive and finite fails the SPD test,
+    and one that is not positive is replaced by 1.  Returns (spd [N], x [N, n])."""
+    N, n, _ = A.shape
+    U = np.zeros_like(A)
+    spd = np.ones(N, bool)
+    with np.errstate(all="ignore"):
+        for j in range(n):
+            s = A[:, j, j] - (U[:, :j, j] ** 2).sum(1)
+            spd &= (s > 0) & np.isfinite(s)
+            d = np.sqrt(np.where(s > 0, s, 1.0))
+            U[:, j, j] = d
+            for i in range(j + 1, n):
+                U[:, j, i] = (A[:, j, i] - (U[:, :j, j] * U[:, :j, i]).sum(1)) / d
+        z = np.zeros_like(b)
+        for i in range(n):
+            z[:, i] = (b[:, i] - (U[:, :i, i] * z[:, :i]).sum(1)) / U[:, i, i]
+        x = np.zeros_like(b)
+        for i in reversed(range(n)):
+            x[:, i] = (z[:, i] - (U[:, i, i + 1:] * x[:, i + 1:]).sum(1)) / U[:, i, i]
+    return spd, x
+
+
+def info_model(x0, xf, Pf, evals, dom=None, reg_gd=None, reg_j=6, prior_product=True):
+    """float64 model of the information-form analysis of every pixel and of
+    the status byte it must carry.  ``evals``: per band (H0 [N], h [N, n], y,
+    w) at the linearisation point x0.
+
+    ST_BAD_OP         a used band whose value or Jacobian is not finite
+    ST_NO_OBS         no band left
+    ST_OUT_OF_DOMAIN  x0 outside the box ``dom`` (BandTable.dom)
+    ST_NONSPD         the Cholesky factorisation of the forecast precision or of
+                      the analysis precision fails
+    ST_NONFINITE      the solution is not finite
+    ST_FALLBACK       either of the last two: the pixel keeps the forecast
+
+    ``reg_gd`` [N]: gamma * degree on the regularised parameter's diagonal (the
+    spatial twin, which solves the full form b = r + A x0).  ``prior_product``:
+    the prior part of the right-hand side is a product with P_f^-1, so a NaN in
+    it reaches the solution (the host runner's full form P_f^-1 x_f); False: at
+    the forecast the correction form's P_f^-1 (x_f - x0) is written as the 0 it
+    is (the matrix-core kernels' first iteration).  Returns the status, the fallback
+    mask, the analysis (x, A) by ``analysis_blocks`` on the pixels that keep it
+    (the forecast elsewhere) and the norm sum |x - x0|^2 over them."""
+    from kafka_inferenceengine_amd.inference import analysis_blocks
+    N, n = xf.shape
+    st = np.zeros(N, np.uint8)
+    with np.errstate(all="ignore"):
+        Aa = Pf.copy()
+        r = np.einsum("nij,nj->ni", Pf, xf - x0) if prior_product else np.zeros((N, n))
+        nobs = np.zeros(N, int)
+        used = []
+        for H, h, y, w in evals:
+            use = w > 0
+            ok = np.isfinite(H) & np.isfinite(h).all(1)
+            st[use & ~ok] |= K.ST_BAD_OP
+            u = use & ok
+            nobs += u
+            hu, wu, Hu = np.where(u[:, None], h, 0.0), np.where(u, w, 0.0), np.where(u, H, 0.0)
+            Aa += wu[:, None, None] * hu[:, :, None] * hu[:, None, :]
+            r += (wu * (y - Hu))[:, None] * hu
+            used.append((Hu, hu, y, wu))
+        st[nobs == 0] |= K.ST_NO_OBS
+        if dom is not None:
+            lo, hi = (np.asarray(d[:n], dtype=np.float32).astype(np.float64) for d in dom)
+            st[~((x0 >= lo) & (x0 <= hi)).all(1)] |= K.ST_OUT_OF_DOMAIN
+        spd_f, _ = chol_model(Pf, np.zeros((N, n)))
+        if reg_gd is None:
+            spd, dx = chol_model(Aa, r)
+            sol = x0 + dx
+        else:
+            r = r + np.einsum("nij,nj->ni", Aa, x0)
+            Aa[:, reg_j, reg_j] += reg_gd
+            spd, sol = chol_model(Aa, r)
+        spd &= spd_f
+        fin = np.isfinite(sol).all(1)
+    st[~spd] |= K.ST_NONSPD
+    st[~fin] |= K.ST_NONFINITE
+    fb = ~spd | ~fin
+    st[fb] |= K.ST_FALLBACK
+    x, A = xf.copy(), Pf.copy()
+    keep = ~fb
+    xr, Ar = analysis_blocks(x0[keep], xf[keep], Pf[keep], [tuple(a[keep] for a in bd) for bd in used])
+    norm = float(((xr - x0[keep]) ** 2).sum())
+    if reg_gd is not None:
+        # the regulariser's prepare: u = A_reg^-1 b with the unregularised b = A x_a
+        b = np.einsum("nij,nj->ni", Ar, xr)
+        Ar[:, reg_j, reg_j] += reg_gd[keep]
+        xr = np.linalg.solve(Ar, b[..., None])[..., 0]
+    x[keep], A[keep] = xr, Ar
+    return dict(xf=xf, Pf=Pf, x=x, A=A, status=st, fallback=fb, observed=nobs > 0, norm=norm)
+
+
+def containment_model(run, dom=None, reg_gd=None, prior_product=False):
+    """``info_model`` of one launch of a containment run linearised at its
+    fused forecast: the forecast from the reference-API propagator
+    (inference/kf_tools.py) over the float32 inputs, the bands from the
+    emulators' ``predict``."""
+    from kafka_inferenceengine_amd.inference import kf_tools as T
+    from kafka_inferenceengine_amd.utils.blocks import sparse_to_blocks
+    prob, N, n = run["prob"], run["prob"]["N"], 7
+    xa32 = run["xa"].astype(np.float32).astype(np.float64)
+    da = np.einsum("nii->ni", run["pa"]).astype(np.float32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        xf, _, Pr = T.propagate_information_filter_LAI(xa32.ravel(), None, da.ravel(), None,
+                                                       np.full(N * n, CONTAIN_Q))
+        xf = xf.reshape(N, n).astype(np.float32).astype(np.float64)
+        Pf = sparse_to_blocks(Pr, n, check=False).astype(np.float64)
+        evals = []
+        for b, (y, w) in enumerate(prob["bands"]):
+            mp = k.TIP_BAND_MAPPER[b]
+            H, dH = prob["ems"][b].predict(xf[:, mp])
+            h = np.zeros((N, n))
+            h[:, mp] = dH
+            evals.append((H, h, y, w))
+    m = info_model(xf, xf, Pf, evals, dom, reg_gd, 6, prior_product)
+    m["H"] = [e[0] for e in evals]
+    return m
+
+
+def containment_launch(run, device, variant=None, line=None, reg=None):
+    """One information-form launch of ``run`` linearised at the fused forecast
+    with every output the kernel can write; returns CPU arrays."""
+    prob = run["prob"]
+    n, N = prob["n"], prob["N"]
+    nt = n * (n + 1) // 2
+    h0 = [torch.zeros(N, dtype=torch.float32, device=device) for _ in range(2)]
+    tab = table(prob, device, h0_outs=h0)
+    xo = torch.zeros((n, N), device=device)
+    ao = torch.zeros((nt, N), device=device)
+    st = torch.zeros(N, dtype=torch.uint8, device=device)
+    unc = torch.zeros((n, N), device=device)
+    h = K.prop_args(n, containment_spec(n), soa(run["xa"], device), packed(run["pa"], device), fused=True)
+    K.STRUCT_LAUNCHES.update(tip=0, dense=0)
+    res = dict(dom=tab.dom)
+    if reg is None:
+        mean = torch.zeros((n, N), device=device)
+        part = K.partials_buffer(N, device)
+        K.analysis(n, tab, None, None, None, xo, ao, None, st, part, prop=h, out=(mean, unc, None), variant=variant,
+                   line=line)
+        res.update(mean=mean.cpu().numpy(), norm=float(K.reduce_partials(part).cpu()))
+    else:
+        v = torch.full((n, N), 7.0, device=device)
+        K.analysis(n, tab, None, None, None, xo, ao, None, st, None, prop=h, out=(None, unc, None), variant=variant,
+                   line=line, reg=dict(reg, v_out=v, nbr=None))
+        res.update(v=v.cpu().numpy())
+    if torch.device(device).type == "cuda":
+        torch.cuda.synchronize()
+    res.update(x=xo.cpu().numpy(), a=ao.cpu().numpy(), status=st.cpu().numpy(), unc=unc.cpu().numpy(),
+               h0=[t.cpu().numpy() for t in h0], launches=dict(K.STRUCT_LAUNCHES))
+    return res
