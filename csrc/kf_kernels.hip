@@ -25,24 +25,38 @@ __global__ __launch_bounds__(RED_BLOCK) void reduce_partials_kernel(const double
   }
 }
 
-// K7: nearest LUT entry (utils.py:225-234); LUT staged in LDS.
+// K7: nearest LUT entry (utils.py:225-234).  The LUT goes through LDS in
+// chunks of whole rows (LUT_LDS_FLOATS floats, 48 KiB static: any M, no
+// function attribute), in ascending row order; each pixel carries its running
+// best across the chunks and the strict `<` keeps the lowest index of equal
+// distances, so the result is the host runner's (kf_host.cpp, same fmaf order).
+// The pixel loop is per workgroup (every thread reaches the barriers).
+constexpr int LUT_LDS_FLOATS = 12 * 1024;
+static_assert(LUT_LDS_FLOATS * sizeof(float) < 64 * 1024 && LUT_LDS_FLOATS >= MAX_D, "static LDS, >= one row");
 __global__ __launch_bounds__(BLOCK) void lut_nearest_kernel(const float* lut, int M, int D, const float* x,
                                                            int64_t N, int64_t ld, int32_t* out) {
-  extern __shared__ __attribute__((aligned(16))) float slut[];
-  for (int i = threadIdx.x; i < M * D; i += BLOCK) slut[i] = lut[i];
-  __syncthreads();
+  __shared__ __attribute__((aligned(16))) float slut[LUT_LDS_FLOATS];
+  const int rows = LUT_LDS_FLOATS / D;   // LUT rows per chunk (D <= MAX_D: the launcher)
   const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < N; p += stride) {
+  for (int64_t p0 = (int64_t)blockIdx.x * BLOCK; p0 < N; p0 += stride) {
+    const int64_t p = p0 + threadIdx.x;
+    const bool live = p < N;
     float xv[MAX_D];
-    for (int d = 0; d < D; ++d) xv[d] = x[d * ld + p];
+    for (int d = 0; d < D; ++d) xv[d] = live ? x[d * ld + p] : 0.f;
     float best = 3.4e38f;
     int bi = 0;
-    for (int m = 0; m < M; ++m) {
-      float s = 0.f;
-      for (int d = 0; d < D; ++d) { const float t = slut[m * D + d] - xv[d]; s = fmaf(t, t, s); }
-      if (s < best) { best = s; bi = m; }
+    for (int m0 = 0; m0 < M; m0 += rows) {
+      const int nr = M - m0 < rows ? M - m0 : rows;
+      __syncthreads();   // the previous chunk has been read
+      for (int i = threadIdx.x; i < nr * D; i += BLOCK) slut[i] = lut[(int64_t)m0 * D + i];
+      __syncthreads();
+      for (int m = 0; m < nr; ++m) {
+        float s = 0.f;
+        for (int d = 0; d < D; ++d) { const float t = slut[m * D + d] - xv[d]; s = fmaf(t, t, s); }
+        if (s < best) { best = s; bi = m0 + m; }
+      }
     }
-    out[p] = bi;
+    if (live) out[p] = bi;
   }
 }
 
@@ -688,9 +702,9 @@ hipError_t dev_gather(int elem_bytes, const void* src, const int64_t* idx, void*
 }
 hipError_t dev_lut_nearest(const float* lut, int M, int D, const float* x, int64_t N, int64_t ld, int32_t* out,
                            hipStream_t s) {
-  const size_t lds = (size_t)M * D * sizeof(float);
-  if (lds > 160 * 1024 || D > MAX_D) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(lut_nearest_kernel, dim3(grid_for(N, KF_MAX_BLOCKS)), dim3(BLOCK), lds, s, lut, M, D, x, N,
+  if (M < 0 || D < 1 || D > MAX_D) return hipErrorInvalidValue;
+  if (N <= 0) return hipSuccess;
+  hipLaunchKernelGGL(lut_nearest_kernel, dim3(grid_for(N, KF_MAX_BLOCKS)), dim3(BLOCK), 0, s, lut, M, D, x, N,
                      ld, out);
   return hipGetLastError();
 }

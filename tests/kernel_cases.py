@@ -504,3 +504,265 @@ def containment_launch(run, device, variant=None, line=None, reg=None):
     res.update(x=xo.cpu().numpy(), a=ao.cpu().numpy(), status=st.cpu().numpy(), unc=unc.cpu().numpy(),
                h0=[t.cpu().numpy() for t in h0], launches=dict(K.STRUCT_LAUNCHES))
     return res
+
+
+# --------------------------------------------------------------------------
+# Auxiliary kernels at every compiled state size (tests/test_gpu_aux.py):
+# inputs rounded to float32 first, a float64 NumPy model over exactly those
+# values, operands whose leading dimension exceeds N with a sentinel in the
+# padding columns.
+AUX_NP = (1, 2, 3, 4, 7, 10)
+AUX_N = (1, 63, 64, 65, 257 + 256)     # below a wave, around one, two workgroups
+AUX_PAD = (5, 64)
+SENTINEL = 12345.0
+
+
+def aux_shape(i):
+    """(N, pad) of the i-th case of a kernel: every N and both pads come up."""
+    return AUX_N[i % len(AUX_N)], AUX_PAD[i % len(AUX_PAD)]
+
+
+def f32(a):
+    """``a`` rounded to float32, as float64."""
+    return np.asarray(a, dtype=np.float32).astype(np.float64)
+
+
+def sym32(blocks):
+    """[N, n, n] symmetric blocks as the kernels read them: the packed upper
+    triangle rounded to float32."""
+    from kafka_inferenceengine_amd.utils.blocks import unpack_blocks
+    return unpack_blocks(f32(pack_blocks(blocks)), blocks.shape[-1])
+
+
+def padded(rows, ld, device, fill=SENTINEL, dtype=torch.float32):
+    """[R, N] array -> [R, ld] tensor on ``device``, columns N.. hold ``fill``."""
+    rows = np.atleast_2d(np.asarray(rows))
+    t = torch.full((rows.shape[0], ld), fill, dtype=dtype)
+    t[:, :rows.shape[1]] = torch.from_numpy(np.ascontiguousarray(rows)).to(dtype)
+    return t.to(device)
+
+
+def sentinel(rows, ld, device, fill=SENTINEL, dtype=torch.float32):
+    return torch.full((rows, ld), fill, dtype=dtype, device=device)
+
+
+PROP_BLENDS = ("off", "on", "quirk")
+
+
+def propagate_case(n, N, mode, blend="off", seed=0):
+    """Inputs of one propagate launch with per-pixel trajectory uncertainty
+    (and, with ``blend``, per-pixel prior mean and precision), and the float64
+    model of its result over the formulas of inference/kf_tools.py:
+
+    mode 0  reset:       x_f = reset mean, P_f^-1 = reset precision
+    mode 1  partial:     as 0, but x_f[j] = m_j x_a[j] and (P_f^-1)_jj =
+                         1 / (1 / A_jj + q_j) for the propagated j
+    mode 2  approximate: x_f = m x_a, P_f^-1 = diag(d / (1 + d q)), d = diag A
+    mode 3  exact:       x_f = m x_a, P_f^-1 = (A^-1 + Q)^-1
+    mode 4  standard:    x_f = m x_a, P_f = A + Q   (A a covariance)
+    mode 5  identity:    x_f = m x_a, P unchanged
+    blend   the Gaussian product with the prior (mu, C^-1): P + C^-1 and its
+            solve of P x_f + C^-1 mu ("on") or P mu + C^-1 x_f ("quirk")
+
+    The propagated parameters are the lowest and the highest.  The constant
+    fields of ``spec`` that the per-pixel operands replace hold values that
+    would be visibly wrong if read.  Every matrix the kernel factorises is SPD
+    (a diagonally dominant reset precision keeps it so under the diagonal
+    replacement of mode 1)."""
+    from kafka_inferenceengine_amd.utils.blocks import pack_matrix, unpack_matrix
+    rng = np.random.default_rng([seed, n, N, mode, PROP_BLENDS.index(blend)])
+    A = sym32(spd_blocks(rng, N, n, 5.0))
+    xa = f32(rng.normal(size=(N, n)))
+    m = f32(rng.uniform(0.9, 1.1, n))
+    q = f32(rng.uniform(0.01, 0.2, (N, n)))
+    mask = 1 | (1 << (n - 1))
+    prop = np.array([(mask >> j) & 1 for j in range(n)], bool)
+    mu0 = f32(rng.normal(size=n))
+    R = rng.uniform(-0.15, 0.15, (n, n))
+    R = 0.5 * (R + R.T)
+    np.fill_diagonal(R, 0.0)
+    R += np.diag(2.0 + np.abs(R).sum(1))
+    R = unpack_matrix(f32(pack_matrix(R)), n)
+    mu = f32(mu0[None] + 0.3 * rng.normal(size=(N, n)))
+    Ci = sym32(0.5 * spd_blocks(rng, N, n, 3.0))
+    d = np.einsum("nii->ni", A)
+    mx = m[None] * xa
+    if mode == 0:
+        xf, P = np.tile(mu0, (N, 1)), np.tile(R, (N, 1, 1))
+    elif mode == 1:
+        xf, P = np.where(prop[None], mx, mu0[None]), np.tile(R, (N, 1, 1))
+        for j in np.nonzero(prop)[0]:
+            P[:, j, j] = 1.0 / (1.0 / d[:, j] + q[:, j])
+    elif mode == 2:
+        xf, P = mx, np.zeros((N, n, n))
+        P[:, np.arange(n), np.arange(n)] = d / (1.0 + d * q)
+    elif mode == 3:
+        Q = np.zeros((N, n, n))
+        Q[:, np.arange(n), np.arange(n)] = q
+        xf, P = mx, np.linalg.inv(np.linalg.inv(A) + Q)
+    elif mode == 4:
+        xf, P = mx, A.copy()
+        P[:, np.arange(n), np.arange(n)] += q
+    else:
+        xf, P = mx, A.copy()
+    if blend != "off":
+        if blend == "quirk":
+            b = np.einsum("nij,nj->ni", P, mu) + np.einsum("nij,nj->ni", Ci, xf)
+        else:
+            b = np.einsum("nij,nj->ni", P, xf) + np.einsum("nij,nj->ni", Ci, mu)
+        P = P + Ci
+        xf = np.linalg.solve(P, b[..., None])[..., 0]
+    assert np.linalg.eigvalsh(A).min() > 0 and np.linalg.eigvalsh(P).min() > 0
+    spec = {"mode": mode, "m": m, "q": np.full(n, 50.0), "prop_mask": mask, "reset_mean": mu0,
+            "reset_cinv": pack_matrix(R), "blend": blend != "off", "quirk_blend": blend == "quirk",
+            "blend_mean": np.full(n, 1e3), "blend_cinv": pack_matrix(100.0 * np.eye(n))}
+    return dict(n=n, N=N, mode=mode, blend=blend, spec=spec, xa=xa, A=A, q=q, mu=mu, Ci=Ci, xf=xf, P=P)
+
+
+def propagate_launch(c, device, pad, A=None, Ci=None, status=False):
+    """One launch of ``propagate_case`` ``c`` with ld = N + pad and sentinel-filled
+    outputs (``A`` / ``Ci`` replace the case's precision / prior precision);
+    returns the CPU tensors (x_f, p_f, status or None), all [*, ld]."""
+    n, N = c["n"], c["N"]
+    ld = N + pad
+    nt = n * (n + 1) // 2
+    xf, pf = sentinel(n, ld, device), sentinel(nt, ld, device)
+    st = torch.zeros(ld, dtype=torch.uint8, device=device) if status else None
+    if st is not None:
+        st[N:] = 0xA5
+    bl = c["blend"] != "off"
+    K.propagate(n, c["spec"], padded(c["xa"].T, ld, device),
+                padded(pack_blocks(c["A"] if A is None else A), ld, device), xf, pf, N=N, status=st,
+                q_pix=padded(c["q"].T, ld, device),
+                blend_mean_pix=padded(c["mu"].T, ld, device) if bl else None,
+                blend_cinv_pix=padded(pack_blocks(c["Ci"] if Ci is None else Ci), ld, device) if bl else None)
+    return xf.cpu(), pf.cpu(), None if st is None else st.cpu()
+
+
+def invert_case(n, N, seed=0):
+    """SPD blocks and their float64 inverses; ``bad``: about a tenth of the
+    pixels (always the last), whose last diagonal entry changes sign in the
+    ``B_bad`` copy (not positive definite: the last pivot fails)."""
+    rng = np.random.default_rng([seed, n, N])
+    B = sym32(spd_blocks(rng, N, n))
+    bad = rng.random(N) < 0.1
+    bad[N - 1] = True
+    B_bad = B.copy()
+    B_bad[bad, n - 1, n - 1] *= -1.0
+    return dict(n=n, N=N, B=B, inv=np.linalg.inv(B), bad=bad, B_bad=B_bad)
+
+
+HESSIAN_LAYOUTS = ("tip", "prosail", 2, 3, 4)
+
+
+def hessian_case(layout, N, seed=0):
+    """GP bands for the K6 Hessian correction and its float64 reference
+    (``emulator.predict`` / ``emulator.hessian``): "tip" two 4-input bands of
+    the 7-parameter state, "prosail" three full-state bands of the
+    10-parameter state, 2 / 3 / 4 two full-state bands of a small fitted
+    emulator.  A fifth of the pixels is masked (w = 0 in every band); ``a0`` is
+    the packed matrix the correction is subtracted from, ``corr`` the
+    correction, ``ref`` = a0 - corr (unpacked)."""
+    from kafka_inferenceengine_amd.models.gp import GaussianProcessEmulator
+    from kafka_inferenceengine_amd.utils.blocks import unpack_blocks
+    rng = np.random.default_rng([seed, N, HESSIAN_LAYOUTS.index(layout)])
+    if layout == "tip":
+        n, ems, maps = 7, k.make_tip_emulators(n_train=64, seed=seed), [list(m) for m in k.TIP_BAND_MAPPER[:2]]
+        mu, P, _ = k.tip_prior()
+        x = mu[None, :] + rng.normal(size=(N, 7)) * np.sqrt(np.diag(P)) * 0.3
+        x[:, 6] = np.clip(x[:, 6], 0.05, 0.95)
+    elif layout == "prosail":
+        n, ems = 10, k.make_prosail_emulators(n_bands=3, n_train=40, seed=seed)
+        maps = [list(range(10))] * 3
+        lo = np.min([em.inputs.min(0) for em in ems], 0)
+        hi = np.max([em.inputs.max(0) for em in ems], 0)
+        x = lo + (hi - lo) * (0.2 + 0.6 * rng.random((N, 10)))
+    else:
+        n = int(layout)
+        v = rng.normal(size=(2, n))
+        ems = [GaussianProcessEmulator.synthetic(lambda X, b=b: 0.4 + 0.2 * np.sin(X @ v[b]), np.zeros(n), np.ones(n),
+                                                 n_train=30, seed=seed + b) for b in range(2)]
+        maps = [list(range(n))] * 2
+        x = rng.uniform(0.1, 0.9, (N, n))
+    x = f32(x)
+    masked = rng.random(N) < 0.2
+    masked[0] = False
+    if N > 1:
+        masked[N // 2] = True
+    obs, corr = [], np.zeros((N, n, n))
+    for em, mp in zip(ems, maps):
+        f, _ = em.predict(x[:, mp])
+        y = f32(f + 0.01 * rng.normal(size=N))
+        w = f32(np.where(masked, 0.0, 1.0 / 0.02 ** 2))
+        obs.append((y, w))
+        corr[np.ix_(np.arange(N), mp, mp)] += (w * (y - f))[:, None, None] * em.hessian(x[:, mp])
+    nt = n * (n + 1) // 2
+    a0 = f32(rng.normal(size=(nt, N)))
+    specs = [k.gp_spec(em, mp) for em, mp in zip(ems, maps)]
+    return dict(n=n, N=N, x=x, obs=obs, specs=specs, masked=masked, a0=a0, corr=corr,
+                ref=unpack_blocks(a0, n) - corr)
+
+
+def hessian_launch(c, device, pad):
+    """K6 on ``hessian_case`` ``c`` in place on a copy of a0 with ld = N + pad;
+    returns the CPU tensor [nt, ld]."""
+    n, N = c["n"], c["N"]
+    ld = N + pad
+    db = [DeviceBand(K.OBS_F32, y=torch.from_numpy(y.astype(np.float32)).to(device),
+                     w=torch.from_numpy(w.astype(np.float32)).to(device)) for y, w in c["obs"]]
+    tab = build_table(c["specs"], db, n, RecordCache(), device)
+    a = padded(c["a0"], ld, device)
+    K.hessian(n, tab, padded(c["x"].T, ld, device), a, N=N)
+    return a.cpu()
+
+
+def unpack_case(n, N, seed=0):
+    """State, SPD precision and a sorted index map into a raster of 2 N + 7
+    cells, of which the last is named by no pixel."""
+    rng = np.random.default_rng([seed, n, N])
+    plane = 2 * N + 7
+    return dict(n=n, N=N, x=f32(rng.normal(size=(N, n))), A=sym32(spd_blocks(rng, N, n)), plane=plane,
+                idx=np.sort(rng.choice(plane - 1, N, replace=False)).astype(np.int64))
+
+
+# K7: (M, D) of the LUT; 4096 x 4 floats are exactly 64 KiB, 5000 x 10 the
+# reference's default LUT over a full PROSAIL state
+LUT_SIZES = ((1, 3), (50, 3), (4096, 4), (4097, 4), (5000, 4), (5000, 7), (5000, 10))
+LUT_N = (1, 63, 65, 4096 + 37)
+_LUT_CASES: dict = {}
+
+
+def lut_case(M, D, seed=0):
+    """4133 multivariate-normal points and an M-row LUT drawn from their mean
+    and covariance (as run_emulator draws it), both rounded to float32, with
+    the float64 nearest row of every point over those values: ``near`` its
+    index, ``dmin`` its squared distance.  Built once per (M, D)."""
+    key = (M, D, seed)
+    if key not in _LUT_CASES:
+        rng = np.random.default_rng([seed, M, D])
+        G = rng.normal(size=(D, D))
+        pts = f32(rng.multivariate_normal(np.full(D, 0.5), 0.01 * (G @ G.T / D + 0.5 * np.eye(D)), LUT_N[-1]))
+        lut = f32(rng.multivariate_normal(pts.mean(0), np.cov(pts, rowvar=False), M))
+        near = np.empty(len(pts), np.int64)
+        l2 = (lut * lut).sum(1)
+        for s in range(0, len(pts), 512):
+            near[s:s + 512] = (l2[None, :] - 2.0 * pts[s:s + 512] @ lut.T).argmin(1)
+        _LUT_CASES[key] = dict(M=M, D=D, pts=pts, lut=lut, near=near, dmin=lut_dist(lut, pts, near))
+    return _LUT_CASES[key]
+
+
+def lut_dist(lut, pts, idx):
+    """float64 squared distance of every point to its LUT row ``idx``."""
+    t = lut[np.asarray(idx, dtype=np.int64)] - pts
+    return (t * t).sum(1)
+
+
+def lut_launch(lut, pts, N, device):
+    """K7 over the first N points given as [D, ld], ld = N + 11; the padding
+    holds points far from the LUT and the output a sentinel past N.  Returns
+    the CPU int32 tensor [ld]."""
+    ld = N + 11
+    out = torch.full((ld,), -7, dtype=torch.int32, device=device)
+    x = padded(np.asarray(pts)[:N].T, ld, device, fill=1e6)
+    K.lut_nearest(torch.from_numpy(np.asarray(lut, dtype=np.float32)).to(device), x, out=out, N=N)
+    return out.cpu()

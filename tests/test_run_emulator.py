@@ -50,6 +50,52 @@ def test_run_emulator_lut_branch_device_equals_host(device):
     assert dHt.shape == (4000, 4) and np.isfinite(dHt.cpu().numpy()).all()
 
 
+@pytest.mark.parametrize("D", [4, 7, 10])
+@pytest.mark.parametrize("device", DEVICES)
+def test_run_emulator_default_lut_size_device_equals_host(device, D, monkeypatch):
+    """The LUT branch at the reference's own LUT size (the default, 5000 rows;
+    200,000 bytes of float32 for a full PROSAIL state) on 4096 + 37 rows.  The
+    K7 assignment the tensor path makes is held to float64 over the float32 LUT
+    and points it was given: every pixel's chosen row within (1 + 1e-5) of the
+    smallest squared distance, the float64 argmin on at least 99.9 % of the
+    pixels; the tensor path returns that row's emulator value, which is the
+    host NumPy path's on at least 99.9 % of the pixels (float32 against float64
+    distances may resolve a near tie differently)."""
+    from kafka_inferenceengine_amd.ops import kernels as K
+
+    gp = _gp(D=D)
+    rng = np.random.default_rng(10 + D)
+    G = rng.normal(size=(D, D))
+    x = rng.multivariate_normal(np.full(D, 0.5), 0.01 * (G @ G.T / D + 0.5 * np.eye(D)), 4096 + 37).astype(np.float32)
+    seen = {}
+    k7 = K.lut_nearest
+
+    def recording(lut, pts, *a, **kw):
+        out = k7(lut, pts, *a, **kw)
+        seen.update(lut=lut.cpu().numpy().astype(np.float64), pts=pts.cpu().numpy().astype(np.float64).T,
+                    idx=out.cpu().numpy().astype(np.int64))
+        return out
+
+    monkeypatch.setattr(K, "lut_nearest", recording)
+    H, dH = run_emulator(gp, x.astype(np.float64), lut_threshold=100, seed=7)
+    Ht, dHt = run_emulator(gp, torch.as_tensor(x, device=device), lut_threshold=100, seed=7)
+    assert seen["lut"].shape == (5000, D) and seen["idx"].shape == (len(x),)
+    lut, pts, idx = seen["lut"], seen["pts"], seen["idx"]
+    near = np.empty(len(pts), np.int64)
+    for s in range(0, len(pts), 512):
+        near[s:s + 512] = ((lut * lut).sum(1)[None, :] - 2.0 * pts[s:s + 512] @ lut.T).argmin(1)
+    dist = lambda j: ((lut[j] - pts) ** 2).sum(1)  # noqa: E731
+    assert idx.min() >= 0 and idx.max() < 5000
+    assert np.all(dist(idx) <= (1.0 + 1e-5) * dist(near))
+    assert (idx == near).mean() >= 0.999
+    pred, dpred = gp.predict(lut, do_unc=False)
+    assert Ht.device.type == device and Ht.shape == (len(x),) and dHt.shape == (len(x), D)
+    np.testing.assert_allclose(Ht.cpu().numpy(), pred[idx], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(dHt.cpu().numpy(), dpred[idx], rtol=1e-5, atol=1e-5)
+    same = np.isclose(Ht.cpu().numpy(), H, rtol=1e-4, atol=1e-5)
+    assert same.mean() >= 0.999, same.mean()
+
+
 @pytest.mark.parametrize("device", DEVICES)
 def test_run_emulator_float64_rows_that_collide_in_float32(device):
     """float64 rows that differ only below float32 precision stay
