@@ -161,6 +161,7 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
       .def_readwrite("gpm_frags", &GainArgs::gpm_frags)
       .def_readwrite("gpm_global", &GainArgs::gpm_global)
       .def_readwrite("band_layout", &GainArgs::band_layout)
+      .def_readwrite("split_mixlo", &GainArgs::split_mixlo)
       .def_readwrite("gn_fused", &GainArgs::gn_fused)
       .def_readwrite("n_visit", &GainArgs::n_visit)
       .PTR_FIELD(GainArgs, n_visit_dev, const int32_t*)
@@ -288,6 +289,11 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
                                        P<float>(h), h_ld, P<uint8_t>(ok), (hipStream_t)stream), "operator_eval");
     else check_host(host_operator(np, P<const BandDesc>(bands), band, P<const float>(x), N, ld, P<float>(h0),
                                   P<float>(h), h_ld, P<uint8_t>(ok)), "operator_eval");
+  });
+  m.def("exp_split_probe", [](uintptr_t e, uintptr_t mh, uintptr_t ml, uintptr_t mv, int64_t n8, bool mixlo,
+                              uintptr_t stream) {
+    check_hip(dev_exp_split_probe(P<const float>(e), P<uint16_t>(mh), P<uint16_t>(ml), P<float>(mv), n8, mixlo,
+                                  (hipStream_t)stream), "exp_split_probe");
   });
   m.def("gp_operator_supported", [](int np, int d) { return gp_operator_supported(np, d); });
   m.def("gp_operator", [](int np, int d, uintptr_t bands, int nb, uintptr_t x, int64_t N, int64_t ld, uintptr_t h0,

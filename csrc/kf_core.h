@@ -308,7 +308,8 @@ enum AnalysisVariant : int32_t {
   AV_PER_BAND_OPERAND = 14,  // BAND_LAYOUT_SHARED_X: exponent operand rebuilt per band
   AV_BLOCK_ORDER = 16,       // exponent MFMAs block by block (gpm_il_default's other order)
   AV_GENERIC_SPEC = 18,      // fused forecast through the generic launch instead of SPEC_PROP
-  AV_DENSE_SOLVE = 20        // the dense solve where a_struct would select the structure-aware kernels / host path
+  AV_DENSE_SOLVE = 20,       // the dense solve where a_struct would select the structure-aware kernels / host path
+  AV_MIXLO_SPLIT = 22        // lo half of m by v_fma_mixlo/mixhi_f16 (gpm_exp_split MIXLO; kf_device.h mixlo_split_analysis)
 };
 
 struct AnalysisArgs {
@@ -1564,7 +1565,7 @@ struct GainArgs {
   // host hint as AnalysisArgs.band_layout (BAND_LAYOUT_SHARED_X: one exponent
   // operand per iteration in the global-table kernel); 0: runtime
   int32_t band_layout;
-  int32_t pad_;
+  int32_t split_mixlo;   // 1: AV_MIXLO_SPLIT's kernels (kf_device.h mixlo_split_gain)
 };
 
 KF_HD int64_t visit_count(const GainArgs& a) { return visit_bounded(a.n_visit, a.N, a.n_visit_dev); }

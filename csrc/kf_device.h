@@ -94,9 +94,12 @@ __global__ __launch_bounds__(BLOCK) void analysis_kernel(AnalysisArgs a) {
 // MINW = 4 waves per SIMD (<= 128 VGPRs, 2 workgroups per CU for two bands'
 // tables) lets the HBM phases (state loads, result stores) of some waves run
 // under the record loops of others; BS = 256 gives 3 waves per SIMD.
-template <int NP, int D, int FOBS, int BS = BLOCK, int MINW = 1, int LAYOUT = BAND_LAYOUT_RUNTIME, bool IL = false,
-          int SPEC = SPEC_ANY>
-__global__ __launch_bounds__(BS, MINW) void analysis_mfma_kernel(AnalysisArgs a) {
+// The kernel's body is a function of its own with gpm_exp_split's MIXLO flag:
+// analysis_mfma_kernel (the default split; its template signature is what
+// tests/test_isa_lint.py names) and analysis_mfma_mixlo_kernel
+// (AV_MIXLO_SPLIT) are the two kernels around it.
+template <int NP, int D, int FOBS, int BS, int LAYOUT, bool IL, int SPEC, bool MIXLO>
+__device__ __forceinline__ void analysis_mfma_body(const AnalysisArgs& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ kf_h8 gpm_lds[];
   KF_PHASE_KERNEL_BEGIN
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(BS, MINW) void analysis_mfma_kernel(AnalysisArgs a)
         }
       }
       float dn1;
-      const float dn = pixel_analysis_mfma<NP, D, FOBS, false, false, LAYOUT, IL, SPEC>(
+      const float dn = pixel_analysis_mfma<NP, D, FOBS, false, false, LAYOUT, IL, SPEC, MIXLO>(
           a, p, act, gpm_lds, dn1 KF_PHASE_ARG, pj, px, pp);
       {
         float* dno = opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->dn_out;
@@ -164,8 +167,8 @@ __global__ __launch_bounds__(BS, MINW) void analysis_mfma_kernel(AnalysisArgs a)
       const bool act = q < nv;
       const int64_t p = visit_px(a.order, act ? q : nv - 1);
       float dn1;
-      const float dn = pixel_analysis_mfma<NP, D, FOBS, false, false, LAYOUT, IL, SPEC>(a, p, act, gpm_lds,
-                                                                                       dn1 KF_PHASE_ARG);
+      const float dn = pixel_analysis_mfma<NP, D, FOBS, false, false, LAYOUT, IL, SPEC, MIXLO>(a, p, act, gpm_lds,
+                                                                                              dn1 KF_PHASE_ARG);
       {
         // re-read through the opaque kernarg pointer: not pinned in SGPRs across the GP loop
         float* dno = opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->dn_out;
@@ -180,12 +183,25 @@ __global__ __launch_bounds__(BS, MINW) void analysis_mfma_kernel(AnalysisArgs a)
 #endif
 }
 
+template <int NP, int D, int FOBS, int BS = BLOCK, int MINW = 1, int LAYOUT = BAND_LAYOUT_RUNTIME, bool IL = false,
+          int SPEC = SPEC_ANY>
+__global__ __launch_bounds__(BS, MINW) void analysis_mfma_kernel(AnalysisArgs a) {
+  analysis_mfma_body<NP, D, FOBS, BS, LAYOUT, IL, SPEC, false>(a);
+}
+
+template <int NP, int D, int FOBS, int BS = BLOCK, int MINW = 1, int LAYOUT = BAND_LAYOUT_RUNTIME, bool IL = false,
+          int SPEC = SPEC_ANY>
+__global__ __launch_bounds__(BS, MINW) void analysis_mfma_mixlo_kernel(AnalysisArgs a) {
+  analysis_mfma_body<NP, D, FOBS, BS, LAYOUT, IL, SPEC, true>(a);
+}
+
 // K1 on the matrix cores with every band's table read from global memory
 // (gp_mfma_sums_g): many-band GP states (PROSAIL: ten bands, 358-716 KiB of
 // tables) whose tables exceed the LDS.  No LDS, so the waves per SIMD follow
 // the VGPR count alone.
-template <int NP, int D, int FOBS, bool PF = false, bool IL = false, int SPEC = SPEC_ANY>
-__global__ __launch_bounds__(BLOCK, 2) void analysis_mfma_g_kernel(AnalysisArgs a) {
+// (body and the two kernels around it as analysis_mfma_kernel)
+template <int NP, int D, int FOBS, bool PF, bool IL, int SPEC, bool MIXLO>
+__device__ __forceinline__ void analysis_mfma_g_body(const AnalysisArgs& a) {
   static_assert(BLOCK / 64 == GPM_G_WAVES, "per-wave LDS transpose buffers of gp_mfma_sums_g_xb");
 #if defined(__HIP_DEVICE_COMPILE__)
   KF_PHASE_KERNEL_BEGIN
@@ -198,7 +214,7 @@ __global__ __launch_bounds__(BLOCK, 2) void analysis_mfma_g_kernel(AnalysisArgs 
     const bool act = q < nv;
     const int64_t p = visit_px(a.order, act ? q : nv - 1);
     float dn1;
-    const float dn = pixel_analysis_mfma<NP, D, FOBS, true, PF, BAND_LAYOUT_RUNTIME, IL, SPEC>(
+    const float dn = pixel_analysis_mfma<NP, D, FOBS, true, PF, BAND_LAYOUT_RUNTIME, IL, SPEC, MIXLO>(
         a, p, act, nullptr, dn1 KF_PHASE_ARG);
     {
       // re-read through the opaque kernarg pointer: not pinned in SGPRs across the GP loop
@@ -211,6 +227,16 @@ __global__ __launch_bounds__(BLOCK, 2) void analysis_mfma_g_kernel(AnalysisArgs 
   analysis_partials(a, acc, acc1);
   KF_PHASE_KERNEL_END
 #endif
+}
+
+template <int NP, int D, int FOBS, bool PF = false, bool IL = false, int SPEC = SPEC_ANY>
+__global__ __launch_bounds__(BLOCK, 2) void analysis_mfma_g_kernel(AnalysisArgs a) {
+  analysis_mfma_g_body<NP, D, FOBS, PF, IL, SPEC, false>(a);
+}
+
+template <int NP, int D, int FOBS, bool PF = false, bool IL = false, int SPEC = SPEC_ANY>
+__global__ __launch_bounds__(BLOCK, 2) void analysis_mfma_g_mixlo_kernel(AnalysisArgs a) {
+  analysis_mfma_g_body<NP, D, FOBS, PF, IL, SPEC, true>(a);
 }
 
 // dynamic LDS above the 64 KiB default (tables of several bands, up to the
@@ -226,8 +252,9 @@ static void gpm_lds_attr(K kernel, size_t bytes) {
 // workgroup, as analysis_mfma_kernel).  3 workgroups per CU (168 VGPRs, 80 B
 // of scratch per lane) run 6 % faster than 2 (201 VGPRs, 64 B): tip7 gain
 // 24.05 vs 25.52 ms/step (profiles/r6_v25_gain_three_waves_ab.jsonl).
-template <int NP, int D, int FOBS>
-__global__ __launch_bounds__(BLOCK, 3) void gain_mfma_kernel(GainArgs a) {
+// (body and the two kernels around it as analysis_mfma_kernel)
+template <int NP, int D, int FOBS, bool MIXLO>
+__device__ __forceinline__ void gain_mfma_body(const GainArgs& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ kf_h8 gpm_lds[];
   {
@@ -251,13 +278,23 @@ __global__ __launch_bounds__(BLOCK, 3) void gain_mfma_kernel(GainArgs a) {
     const bool act = q < nv;
     const int64_t p = visit_px(a.order, act ? q : nv - 1);
     float dn1;
-    const float dn = pixel_gain_mfma<NP, D, FOBS>(a, p, act, gpm_lds, dn1);
+    const float dn = pixel_gain_mfma<NP, D, FOBS, false, false, MIXLO>(a, p, act, gpm_lds, dn1);
     acc += act ? (double)dn : 0.0;
     acc1 += act ? (double)dn1 : 0.0;
   }
   if (a.partials_first) block_partials2<BLOCK>(acc, acc1, a.partials, a.partials_first);
   else if (a.partials) block_partial(acc, a.partials);
 #endif
+}
+
+template <int NP, int D, int FOBS>
+__global__ __launch_bounds__(BLOCK, 3) void gain_mfma_kernel(GainArgs a) {
+  gain_mfma_body<NP, D, FOBS, false>(a);
+}
+
+template <int NP, int D, int FOBS>
+__global__ __launch_bounds__(BLOCK, 3) void gain_mfma_mixlo_kernel(GainArgs a) {
+  gain_mfma_body<NP, D, FOBS, true>(a);
 }
 
 // K1g on the matrix cores with every band's table read from global memory
@@ -269,8 +306,9 @@ __global__ __launch_bounds__(BLOCK, 3) void gain_mfma_kernel(GainArgs a) {
 // 10 parameters): the same register and scratch counts as block by block, and
 // 1.2 % (prosail10) and 1.9 % (multisensor) faster in an alternating A/B on
 // one box (BENCHMARKS.md).
-template <int NP, int D, int FOBS>
-__global__ __launch_bounds__(BLOCK, 2) void gain_mfma_g_kernel(GainArgs a) {
+// (body and the two kernels around it as analysis_mfma_kernel)
+template <int NP, int D, int FOBS, bool MIXLO>
+__device__ __forceinline__ void gain_mfma_g_body(const GainArgs& a) {
   static_assert(BLOCK / 64 == GPM_G_WAVES, "per-wave LDS transpose buffers of gp_mfma_sums_g_xb");
 #if defined(__HIP_DEVICE_COMPILE__)
   double acc = 0.0, acc1 = 0.0;
@@ -282,13 +320,23 @@ __global__ __launch_bounds__(BLOCK, 2) void gain_mfma_g_kernel(GainArgs a) {
     const bool act = q < nv;
     const int64_t p = visit_px(a.order, act ? q : nv - 1);
     float dn1;
-    const float dn = pixel_gain_mfma<NP, D, FOBS, true, true>(a, p, act, nullptr, dn1);
+    const float dn = pixel_gain_mfma<NP, D, FOBS, true, true, MIXLO>(a, p, act, nullptr, dn1);
     acc += act ? (double)dn : 0.0;
     acc1 += act ? (double)dn1 : 0.0;
   }
   if (a.partials_first) block_partials2<BLOCK>(acc, acc1, a.partials, a.partials_first);
   else if (a.partials) block_partial(acc, a.partials);
 #endif
+}
+
+template <int NP, int D, int FOBS>
+__global__ __launch_bounds__(BLOCK, 2) void gain_mfma_g_kernel(GainArgs a) {
+  gain_mfma_g_body<NP, D, FOBS, false>(a);
+}
+
+template <int NP, int D, int FOBS>
+__global__ __launch_bounds__(BLOCK, 2) void gain_mfma_g_mixlo_kernel(GainArgs a) {
+  gain_mfma_g_body<NP, D, FOBS, true>(a);
 }
 
 template <int NP, int FD = 0, int FOBS = 0>
@@ -323,7 +371,10 @@ static void l_gain(const GainArgs& a, int grid, hipStream_t s) {
     if (a.fast_d == 4 && a.gpm_frags > 0 && a.n_bands <= GPM_MAX_BANDS &&
         (a.fast_obs == OBS_DN16 || a.fast_obs == OBS_F32)) {
       const size_t lds = (size_t)a.gpm_frags * sizeof(kf_h8);
-      if (a.fast_obs == OBS_DN16) {
+      if (a.fast_obs == OBS_DN16 && a.split_mixlo) {   // AV_MIXLO_SPLIT (mixlo_split_gain)
+        gpm_lds_attr(gain_mfma_mixlo_kernel<NP, 4, OBS_DN16>, lds);
+        hipLaunchKernelGGL((gain_mfma_mixlo_kernel<NP, 4, OBS_DN16>), dim3(grid), dim3(BLOCK), lds, s, a);
+      } else if (a.fast_obs == OBS_DN16) {
         gpm_lds_attr(gain_mfma_kernel<NP, 4, OBS_DN16>, lds);
         hipLaunchKernelGGL((gain_mfma_kernel<NP, 4, OBS_DN16>), dim3(grid), dim3(BLOCK), lds, s, a);
       } else {
@@ -337,7 +388,9 @@ static void l_gain(const GainArgs& a, int grid, hipStream_t s) {
     // full-state GP bands with global tables (ops/kernels.py:gain sets
     // gpm_global unless the VALU oracle is selected)
     if (a.gpm_global && a.fast_d == NP && (a.fast_obs == OBS_DN16 || a.fast_obs == OBS_F32)) {
-      if (a.fast_obs == OBS_DN16)
+      if (a.fast_obs == OBS_DN16 && a.split_mixlo)   // AV_MIXLO_SPLIT (mixlo_split_gain)
+        hipLaunchKernelGGL((gain_mfma_g_mixlo_kernel<NP, NP, OBS_DN16>), dim3(grid), dim3(BLOCK), 0, s, a);
+      else if (a.fast_obs == OBS_DN16)
         hipLaunchKernelGGL((gain_mfma_g_kernel<NP, NP, OBS_DN16>), dim3(grid), dim3(BLOCK), 0, s, a);
       else
         hipLaunchKernelGGL((gain_mfma_g_kernel<NP, NP, OBS_F32>), dim3(grid), dim3(BLOCK), 0, s, a);
@@ -550,6 +603,29 @@ constexpr bool gpm_il_default() {
   return (NP == 7 && LAYOUT == BAND_LAYOUT_TIP) || NP >= 10;
 }
 
+// AV_MIXLO_SPLIT (gpm_exp_split's MIXLO flag: the split of m before
+// profiles/split_issue_probe.jsonl) is instantiated for the kernels its test
+// and its A/B run, DN16 observations only: the JRC-TIP LDS-table kernel (the
+// first date's generic launch and the structure-aware fused forecast without a
+// regulariser) and the 10-parameter global-table kernel, in both analysis
+// forms.  Any other launch with it is an error (dev_analysis / dev_gain), not
+// another kernel.
+inline bool mixlo_split_analysis(int np, const AnalysisArgs& a) {
+  if (a.fast_obs != OBS_DN16) return false;
+  const bool lds = a.gpm_frags > 0 && a.n_bands <= GPM_MAX_BANDS;
+  if (np == 7)
+    return lds && a.fast_d == 4 && a.band_layout == BAND_LAYOUT_TIP && a.n_bands == 2 &&
+           (!a.prop || ((a.a_struct & A_STRUCT_TIP) && !a.reg_v));
+  if (np == 10) return !lds && a.fast_d == 10 && a.gpm_global;
+  return false;
+}
+inline bool mixlo_split_gain(int np, const GainArgs& a) {
+  if (a.fast_obs != OBS_DN16) return false;
+  if (np == 7) return a.fast_d == 4 && a.gpm_frags > 0 && a.n_bands <= GPM_MAX_BANDS;
+  if (np == 10) return a.fast_d == 10 && a.gpm_global;
+  return false;
+}
+
 // Launch of a matrix-core analysis kernel on the static grid-stride mapping
 // (partials per workgroup; the hardware dispatcher hands a finished
 // workgroup's slot to the next one, which balances the cloud-skip load).
@@ -576,6 +652,11 @@ static bool l_analysis_fast(const AnalysisArgs& a, int grid, hipStream_t s, int*
     gpm_lds_attr(analysis_mfma_kernel<NP, FD, OBS_, BS_, MINW_, LAY_, IL_, SPEC_>, lds);                      \
     launch_tiles(analysis_mfma_kernel<NP, FD, OBS_, BS_, MINW_, LAY_, IL_, SPEC_>, BS_, lds, a, grid, s, n_part); \
   }
+#define KF_MFMA_GO1M(OBS_, BS_, MINW_, LAY_, IL_, SPEC_)                                                        \
+  {                                                                                                           \
+    gpm_lds_attr(analysis_mfma_mixlo_kernel<NP, FD, OBS_, BS_, MINW_, LAY_, IL_, SPEC_>, lds);                \
+    launch_tiles(analysis_mfma_mixlo_kernel<NP, FD, OBS_, BS_, MINW_, LAY_, IL_, SPEC_>, BS_, lds, a, grid, s, n_part); \
+  }
       // Both column blocks' exponent MFMAs issued before the first block's
       // exponentials (gpm_chunk IL) where that costs no occupancy
       // (gpm_il_default); AV_BLOCK_ORDER: the other order
@@ -595,7 +676,12 @@ static bool l_analysis_fast(const AnalysisArgs& a, int grid, hipStream_t s, int*
   {                                                                                                 \
     constexpr bool IL_ = gpm_il_default<NP, LAY_>();                                                \
     const bool tips = (a.a_struct & A_STRUCT_TIP) && a.variant != AV_DENSE_SOLVE;                   \
-    if (!a.prop || a.variant == AV_BLOCK_ORDER || a.variant == AV_GENERIC_SPEC)                     \
+    if (a.variant == AV_MIXLO_SPLIT) { /* mixlo_split_analysis: no prop, or tips and no reg_v */    \
+      if (!a.prop) KF_MFMA_GO1M(OBS_, BS_, MINW_, LAY_, IL_, SPEC_ANY)                              \
+      else if (small) KF_MFMA_GO1M(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_PF_TIP)                   \
+      else KF_MFMA_GO1M(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_TIP)                                 \
+    }                                                                                               \
+    else if (!a.prop || a.variant == AV_BLOCK_ORDER || a.variant == AV_GENERIC_SPEC)                \
       KF_MFMA_GO(OBS_, BS_, MINW_, LAY_)                                                            \
     else if (a.reg_v && tips) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_REG_TIP)          \
     else if (a.reg_v) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_REG)                      \
@@ -643,6 +729,7 @@ static bool l_analysis_fast(const AnalysisArgs& a, int grid, hipStream_t s, int*
 #undef KF_MFMA_GO_SPEC
 #undef KF_MFMA_GO
 #undef KF_MFMA_GO1
+#undef KF_MFMA_GO1M
       return true;
     }
     if constexpr (FD == NP && NP >= 7) {
@@ -653,6 +740,14 @@ static bool l_analysis_fast(const AnalysisArgs& a, int grid, hipStream_t s, int*
         constexpr bool IL = gpm_il_default<NP, BAND_LAYOUT_RUNTIME>();
         if (a.fast_obs == OBS_DN16 && a.variant == AV_GT_PREFETCH)
           launch_tiles(analysis_mfma_g_kernel<NP, FD, OBS_DN16, true>, BLOCK, 0, a, grid, s, n_part);
+        else if (NP == 10 && a.fast_obs == OBS_DN16 && a.variant == AV_MIXLO_SPLIT && a.prop && !a.reg_v) {
+          if constexpr (NP == 10)
+            launch_tiles(analysis_mfma_g_mixlo_kernel<NP, FD, OBS_DN16, false, true, SPEC_PROP>, BLOCK, 0, a, grid, s,
+                         n_part);
+        } else if (NP == 10 && a.fast_obs == OBS_DN16 && a.variant == AV_MIXLO_SPLIT) {
+          if constexpr (NP == 10)
+            launch_tiles(analysis_mfma_g_mixlo_kernel<NP, FD, OBS_DN16, false, true>, BLOCK, 0, a, grid, s, n_part);
+        }
         else if (a.fast_obs == OBS_DN16 && a.prop && !a.reg_v && a.variant == AV_DEFAULT && IL)
           // fused forecast, no regulariser: the launch's paths fixed at compile time (SPEC_PROP)
           launch_tiles(analysis_mfma_g_kernel<NP, FD, OBS_DN16, false, true, SPEC_PROP>, BLOCK, 0, a, grid, s, n_part);

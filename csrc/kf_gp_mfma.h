@@ -27,10 +27,12 @@
 // 8(j>>2) + 16q, i.e. exactly accumulator registers 8q .. 8q+7 of the
 // exponent MFMA (no shuffles between the two GEMMs).
 //
-// The hi/lo split of m is plain C++ (hipcc selects v_cvt_pkrtz_f16_f32 +
-// v_fma_mixlo/mixhi_f16 and inserts the VALU -> MFMA SrcB wait states
-// itself; the analysis TUs are built with -fno-slp-vectorize, _build.py, so
-// the f32 subtraction is not packed into v_pk_fma_f32 first).
+// The hi/lo split of m is plain C++ (gpm_exp_split: hipcc selects
+// v_cvt_pkrtz_f16_f32 for hi and, per pair, two v_fma_mix_f32 + one
+// v_cvt_pk_f16_f32 for lo -- v_fma_mixlo/mixhi_f16 under the MIXLO flag, the
+// same bits -- and inserts the VALU -> MFMA SrcB wait states itself; the
+// analysis TUs are built with -fno-slp-vectorize, _build.py, so the two f32
+// residuals are not packed into v_pk_fma_f32 first).
 //
 // Host tables (models/gp.py: mfma_tables), per 32-point chunk: the exponent A
 // fragments of every lane (NK x 64), then for q = 0, 1 and h = 0, 1 the sums
@@ -220,8 +222,20 @@ __device__ __forceinline__ void gpm_extract_lds(const kf_f16v (&acc)[2], float (
 // m = 2^e for 8 accumulator registers, split into f16 hi (round toward zero)
 // and lo = f16(m - hi).  lo is fma(hi, -1, m) with the -1 in an SGPR the
 // optimiser cannot see through, so it stays an FMA with an f16-extended
-// operand and a rounded f16 result: v_fma_mixlo/mixhi_f16, one instruction
-// per element (a visible -1 folds to an f32 subtraction plus conversions).
+// operand (a visible -1 folds to an f32 subtraction plus conversions).
+// hi is m truncated, so m - hi is a suffix of m's significand and exact in
+// f32 (tests/test_split_model.py): rounding the f32 residual to f16 gives the
+// bits of the single-rounding FMA.  The default keeps the residual of a pair
+// in f32 (v_fma_mix_f32) and rounds both at once (v_cvt_pk_f16_f32, round to
+// nearest even): 6 instructions per pair instead of 5, and 10 % (alone) / 6 %
+// (beside MFMAs) fewer SIMD cycles at 3 waves per SIMD
+// (profiles/split_issue_probe.jsonl).  MIXLO: the rounded f16 result straight
+// from the FMA (v_fma_mixlo/mixhi_f16, one instruction per element), the
+// split before that measurement (AV_MIXLO_SPLIT).
+typedef float kf_f2 __attribute__((ext_vector_type(2)));
+typedef _Float16 kf_h2 __attribute__((ext_vector_type(2)));
+
+template <bool MIXLO = false>
 __device__ __forceinline__ void gpm_exp_split(const kf_f16v& e, int r0, float neg1, kf_h8& mh, kf_h8& ml) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -230,8 +244,15 @@ __device__ __forceinline__ void gpm_exp_split(const kf_f16v& e, int r0, float ne
     const _Float16 h0 = (_Float16)hp[0], h1 = (_Float16)hp[1];
     mh[2 * q] = h0;
     mh[2 * q + 1] = h1;
-    ml[2 * q] = (_Float16)__builtin_fmaf((float)h0, neg1, m0);
-    ml[2 * q + 1] = (_Float16)__builtin_fmaf((float)h1, neg1, m1);
+    if constexpr (MIXLO) {
+      ml[2 * q] = (_Float16)__builtin_fmaf((float)h0, neg1, m0);
+      ml[2 * q + 1] = (_Float16)__builtin_fmaf((float)h1, neg1, m1);
+    } else {
+      const kf_f2 d = {__builtin_fmaf((float)h0, neg1, m0), __builtin_fmaf((float)h1, neg1, m1)};
+      const kf_h2 l = __builtin_convertvector(d, kf_h2);
+      ml[2 * q] = l[0];
+      ml[2 * q + 1] = l[1];
+    }
   }
 }
 
@@ -255,7 +276,8 @@ __device__ __forceinline__ int gpm_sum_row(int col) {
 // IL: both column blocks' exponent MFMAs are issued first, so the second
 // block's exponent runs on the matrix cores under the first block's
 // exponentials and split (one more 16-register accumulator live).
-template <int D, bool FIRST = false, bool IL = false>
+// MIXLO: gpm_exp_split's flag.
+template <int D, bool FIRST = false, bool IL = false, bool MIXLO = false>
 __device__ __forceinline__ void gpm_chunk(const kf_h8 (&ea)[gpm_k_steps(D)], const kf_h8 (&sa)[2],
                                           const kf_h8 (&xb)[2][gpm_k_steps(D)], float neg1, kf_f16v (&acc)[2]) {
   constexpr int NK = gpm_k_steps(D);
@@ -273,7 +295,7 @@ __device__ __forceinline__ void gpm_chunk(const kf_h8 (&ea)[gpm_k_steps(D)], con
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         kf_h8 mh, ml;
-        gpm_exp_split(e[i], 8 * q, neg1, mh, ml);
+        gpm_exp_split<MIXLO>(e[i], 8 * q, neg1, mh, ml);
         acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[q], mh, (FIRST && q == 0) ? zero : acc[i], 0, 0, 0);
         acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[q], ml, acc[i], 0, 0, 0);
       }
@@ -288,7 +310,7 @@ __device__ __forceinline__ void gpm_chunk(const kf_h8 (&ea)[gpm_k_steps(D)], con
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       kf_h8 mh, ml;
-      gpm_exp_split(e, 8 * q, neg1, mh, ml);
+      gpm_exp_split<MIXLO>(e, 8 * q, neg1, mh, ml);
       acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[q], mh, (FIRST && q == 0) ? zero : acc[i], 0, 0, 0);
       acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[q], ml, acc[i], 0, 0, 0);
     }
@@ -300,7 +322,7 @@ __device__ __forceinline__ void gpm_chunk(const kf_h8 (&ea)[gpm_k_steps(D)], con
 // fragment.  Returns the lane's S[0] = sum sgn m, S[1 + d] = sum sgn m B_d,
 // unscaled (gpm_scale not applied; 2^cl is).  Every lane of the wave must call
 // it (MFMA); lanes without an observation pass any finite x.
-template <int D, bool IL = false>
+template <int D, bool IL = false, bool MIXLO = false>
 __device__ __forceinline__ void gp_mfma_sums(const kf_h8* __restrict__ tab, const kf_h8* __restrict__ zf, int nchunk,
                                              const float (&xi)[D], float c, float (&S)[D + 1]) {
   static_assert(D >= 1 && D <= GPM_MAX_D, "GP input count for the matrix-core path");
@@ -332,12 +354,12 @@ __device__ __forceinline__ void gp_mfma_sums(const kf_h8* __restrict__ tab, cons
   {
     kf_h8 ea[NK], sa[2];
     load(0, ea, sa);
-    gpm_chunk<D, true, IL>(ea, sa, xb, neg1, acc);
+    gpm_chunk<D, true, IL, MIXLO>(ea, sa, xb, neg1, acc);
   }
   for (int ch = 1; ch < nchunk; ++ch) {
     kf_h8 ea[NK], sa[2];
     load(ch, ea, sa);
-    gpm_chunk<D, false, IL>(ea, sa, xb, neg1, acc);
+    gpm_chunk<D, false, IL, MIXLO>(ea, sa, xb, neg1, acc);
   }
   gpm_extract2<D>(acc, S);
   const float s = kexp2(cl);
@@ -350,7 +372,7 @@ __device__ __forceinline__ void gp_mfma_sums(const kf_h8* __restrict__ tab, cons
 // PROSAIL bands).  PF: the next chunk's fragments are loaded while the current
 // one runs (register double buffer).
 
-template <int D, bool PF = false, bool IL = false>
+template <int D, bool PF = false, bool IL = false, bool MIXLO = false>
 __device__ __forceinline__ void gp_mfma_sums_g_xb(const void* tab_, int nchunk, const kf_h8 (&xb)[2][gpm_k_steps(D)],
                                                   float cl, float (&S)[D + 1]) {
   static_assert(D >= 1 && D <= GPM_MAX_D, "GP input count for the matrix-core path");
@@ -397,7 +419,7 @@ __device__ __forceinline__ void gp_mfma_sums_g_xb(const void* tab_, int nchunk, 
       sa[0] = san[0];
       sa[1] = san[1];
     }
-    gpm_chunk<D, decltype(first)::value, IL>(ea, sa, xb, neg1, acc);
+    gpm_chunk<D, decltype(first)::value, IL, MIXLO>(ea, sa, xb, neg1, acc);
     if constexpr (PF) {
 #pragma unroll
       for (int kk = 0; kk < NK; ++kk) ea[kk] = ean[kk];
@@ -416,13 +438,13 @@ __device__ __forceinline__ void gp_mfma_sums_g_xb(const void* tab_, int nchunk, 
   for (int f = 0; f <= D; ++f) S[f] *= s;
 }
 
-template <int D, bool PF = false, bool IL = false>
+template <int D, bool PF = false, bool IL = false, bool MIXLO = false>
 __device__ __forceinline__ void gp_mfma_sums_g(const void* tab_, int nchunk, const float (&xi)[D], float c,
                                                float (&S)[D + 1]) {
   kf_h8 xb[2][gpm_k_steps(D)];
   float cl;
   gpm_operands<D>(xi, c, xb, cl);
-  gp_mfma_sums_g_xb<D, PF, IL>(tab_, nchunk, xb, cl, S);
+  gp_mfma_sums_g_xb<D, PF, IL, MIXLO>(tab_, nchunk, xb, cl, S);
 }
 
 // BAND_LAYOUT_SHARED_X: every band is a full-state GP around the same centre,
@@ -589,7 +611,7 @@ __device__ __forceinline__ void gpm_epilogue(const KF_CONST_AS BandDesc* q, cons
 }
 
 template <int NP, int D, int FOBS, bool GT = false, bool PF = false, int LAYOUT = BAND_LAYOUT_RUNTIME,
-          bool IL = false, int SPEC = SPEC_ANY>
+          bool IL = false, int SPEC = SPEC_ANY, bool MIXLO = false>
 __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int64_t p, bool act,
                                                      const kf_h8* lds, float& dn_first KF_PHASE_PARAM,
                                                      int pre_j = -1, float pre_x = 0.f, float pre_p = 0.f) {
@@ -757,14 +779,14 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
             for (int kk = 0; kk < gpm_k_steps(D); ++kk) xb[i][kk] = sxb[i][kk];
           float cl;
           gpm_patch_c<D>(xb, c, cl);
-          gp_mfma_sums_g_xb<D, PF, IL>(bdp->gpm, nch, xb, cl, S);
+          gp_mfma_sums_g_xb<D, PF, IL, MIXLO>(bdp->gpm, nch, xb, cl, S);
         } else {
-          gp_mfma_sums_g<D, PF, IL>(bdp->gpm, nch, xi, c, S);
+          gp_mfma_sums_g<D, PF, IL, MIXLO>(bdp->gpm, nch, xi, c, S);
         }
       } else if constexpr (GT) {
-        gp_mfma_sums_g<D, PF, IL>(bdp->gpm, nch, xi, c, S);
+        gp_mfma_sums_g<D, PF, IL, MIXLO>(bdp->gpm, nch, xi, c, S);
       } else {
-        gp_mfma_sums<D, IL>(lds + off, lds + a.gpm_frags - 1, nch, xi, c, S);
+        gp_mfma_sums<D, IL, MIXLO>(lds + off, lds + a.gpm_frags - 1, nch, xi, c, S);
       }
       KF_PHASE(KF_PH_GP)
       const KF_CONST_AS BandDesc* q = opaque(bdp);   // epilogue fields: not live across the chunk loop
@@ -913,7 +935,7 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
 // (gpm_patch_c), as pixel_analysis_mfma; the centred inputs are recomputed per
 // band from x0 (the same subtraction: bit-identical, ten registers fewer
 // across the band updates).
-template <int NP, int D, int FOBS, bool GT = false, bool IL = false>
+template <int NP, int D, int FOBS, bool GT = false, bool IL = false, bool MIXLO = false>
 __device__ __forceinline__ float pixel_gain_mfma(const GainArgs& a, int64_t p, bool act, const kf_h8* lds,
                                                  float& dn1) {
   constexpr bool SXC = GT && D == NP && D % 2 == 0;
@@ -980,12 +1002,12 @@ __device__ __forceinline__ float pixel_gain_mfma(const GainArgs& a, int64_t p, b
               for (int kk = 0; kk < gpm_k_steps(D); ++kk) xb[i][kk] = sxb[i][kk];
             float cl;
             gpm_patch_c<D>(xb, c, cl);
-            gp_mfma_sums_g_xb<D, false, IL>(bdp->gpm, nch, xb, cl, S);
+            gp_mfma_sums_g_xb<D, false, IL, MIXLO>(bdp->gpm, nch, xb, cl, S);
           }
         }
-        if (!sx) gp_mfma_sums_g<D, false, IL>(bdp->gpm, nch, xi, c, S);
+        if (!sx) gp_mfma_sums_g<D, false, IL, MIXLO>(bdp->gpm, nch, xi, c, S);
       } else {
-        gp_mfma_sums<D>(lds + off, lds + a.gpm_frags - 1, nch, xi, c, S);
+        gp_mfma_sums<D, false, MIXLO>(lds + off, lds + a.gpm_frags - 1, nch, xi, c, S);
       }
       const KF_CONST_AS BandDesc* q = opaque(bdp);
       const float sc = q->gpm_scale;

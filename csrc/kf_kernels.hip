@@ -609,6 +609,7 @@ bool gp_operator_supported(int np, int d) {
 }
 
 hipError_t dev_analysis(int np, const AnalysisArgs& a, int grid, hipStream_t s, int* n_part) {
+  if (a.variant == AV_MIXLO_SPLIT && !mixlo_split_analysis(np, a)) return hipErrorInvalidValue;
   switch (np) {
     case 7: return dev_analysis_np7(a, grid, s, n_part);     // kf_analysis7.hip
     case 10: return dev_analysis_np10(a, grid, s, n_part);   // kf_analysis10.hip
@@ -622,6 +623,7 @@ hipError_t dev_analysis(int np, const AnalysisArgs& a, int grid, hipStream_t s, 
 }
 
 hipError_t dev_gain(int np, const GainArgs& a, int grid, hipStream_t s) {
+  if (a.split_mixlo && !mixlo_split_gain(np, a)) return hipErrorInvalidValue;
   if (np == 10) return dev_gain_np10(a, grid, s);   // kf_gain10.hip
   switch (np) {
     case 1: l_gain<1>(a, grid, s); break;
@@ -706,6 +708,54 @@ hipError_t dev_lut_nearest(const float* lut, int M, int D, const float* x, int64
   if (N <= 0) return hipSuccess;
   hipLaunchKernelGGL(lut_nearest_kernel, dim3(grid_for(N, KF_MAX_BLOCKS)), dim3(BLOCK), 0, s, lut, M, D, x, N,
                      ld, out);
+  return hipGetLastError();
+}
+
+// Test kernel: gpm_exp_split (kf_gp_mfma.h) of 8 exponents per lane, the f16
+// bit patterns of the hi and lo halves of 2^e and m = 2^e itself as the loop
+// computes it (tests/test_gpu_split.py).  Whole groups of 8 (n8 of them: the
+// caller pads), so the halves leave as the packed operand registers the MFMAs
+// read.
+template <bool MIXLO>
+__global__ __launch_bounds__(BLOCK) void exp_split_probe_kernel(const float* e, kf_h8* mh, kf_h8* ml, float* m,
+                                                                int64_t n8) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= n8) return;
+  const f4 e0 = ((const f4*)e)[2 * g], e1 = ((const f4*)e)[2 * g + 1];
+  kf_f16v ev = {};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    ev[k] = e0[k];
+    ev[4 + k] = e1[k];
+  }
+  kf_h8 h, l;
+  gpm_exp_split<MIXLO>(ev, 0, gpm_neg1(), h, l);
+  mh[g] = h;
+  ml[g] = l;
+  f4 m0, m1;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    m0[k] = kexp2(e0[k]);
+    m1[k] = kexp2(e1[k]);
+  }
+  ((f4*)m)[2 * g] = m0;
+  ((f4*)m)[2 * g + 1] = m1;
+#endif
+}
+
+// e, m: 8 n8 floats, mh / ml: 8 n8 f16 bit patterns, all 16-byte aligned
+hipError_t dev_exp_split_probe(const float* e, uint16_t* mh, uint16_t* ml, float* m, int64_t n8, bool mixlo,
+                               hipStream_t s) {
+  if (n8 <= 0) return hipSuccess;
+  if (n8 > (int64_t)BLOCK * 0x7fffffff || (((uintptr_t)e | (uintptr_t)mh | (uintptr_t)ml | (uintptr_t)m) & 15))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n8 + BLOCK - 1) / BLOCK));
+  if (mixlo)
+    hipLaunchKernelGGL(exp_split_probe_kernel<true>, grid, dim3(BLOCK), 0, s, e, (kf_h8*)mh, (kf_h8*)ml, m, n8);
+  else
+    hipLaunchKernelGGL(exp_split_probe_kernel<false>, grid, dim3(BLOCK), 0, s, e, (kf_h8*)mh, (kf_h8*)ml, m, n8);
   return hipGetLastError();
 }
 

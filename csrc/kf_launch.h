@@ -50,6 +50,10 @@ hipError_t dev_gather(int elem_bytes, const void* src, const int64_t* idx, void*
                       int64_t src_ld, int64_t dst_ld, hipStream_t s);
 hipError_t dev_lut_nearest(const float* lut, int M, int D, const float* x, int64_t N, int64_t ld, int32_t* out,
                            hipStream_t s);
+// test kernel: the f16 bit patterns of gpm_exp_split's hi / lo halves of m[i] = 2^e[i],
+// n8 groups of 8 values, 16-byte aligned (mixlo: the AV_MIXLO_SPLIT body)
+hipError_t dev_exp_split_probe(const float* e, uint16_t* mh, uint16_t* ml, float* m, int64_t n8, bool mixlo,
+                               hipStream_t s);
 hipError_t dev_reg_tiled(const RegTileArgs& a, hipStream_t s);
 int reg_rho_blocks(int64_t N);
 hipError_t dev_reg_rho(const float* vrow, const StripGeo& g, int64_t N, const RegScheduleArgs& a, hipStream_t s);

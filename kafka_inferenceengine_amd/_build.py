@@ -106,8 +106,10 @@ def build(force: bool = False, verbose: bool = False, checked: bool = False, pro
         src, obj = csrc / name, build_dir / (Path(name).stem + ".o")
         if force or _stale(obj, [src] + hdrs):
             # MFMA results straight into VGPRs (no v_accvgpr_read per exponent in kf_gp_mfma.h)
-            # -fno-slp-vectorize: keeps the GP hi/lo split scalar so hipcc selects
-            # v_fma_mix (kf_gp_mfma.h:gpm_exp_split) instead of v_pk_fma_f32 + conversions
+            # -fno-slp-vectorize: keeps the FMAs of the GP hi/lo split scalar so hipcc selects
+            # v_fma_mix_f32 (v_fma_mixlo/mixhi_f16 under the MIXLO flag) with the f16 operand
+            # (kf_gp_mfma.h:gpm_exp_split) instead of conversions + v_pk_fma_f32; only the
+            # rounding of a pair's residuals is packed (v_cvt_pk_f16_f32, written as a vector)
             jobs.append([hipcc, f"--offload-arch={ARCH}", *common, "-munsafe-fp-atomics", "-fno-slp-vectorize", "-mllvm",
                          "-amdgpu-mfma-vgpr-form", "-c", str(src), "-o", str(obj)])
         objs.append(obj)

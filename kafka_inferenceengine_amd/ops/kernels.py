@@ -8,6 +8,7 @@ the identical per-pixel source through the OpenMP host runner.
 """
 from __future__ import annotations
 
+import itertools
 from dataclasses import dataclass
 from enum import IntEnum
 
@@ -55,6 +56,7 @@ def _sig(t):
 
 # validated analysis argument blocks by operand identity (analysis(): launch memo)
 _ANALYSIS_MEMO: dict = {}
+_TABLE_SERIAL = itertools.count()
 
 
 def _table_key(bands) -> tuple:
@@ -62,8 +64,12 @@ def _table_key(bands) -> tuple:
     k = bands.__dict__.get("_memo_key")
     if k is None:
         dom = None if bands.dom is None else (tuple(bands.dom[0]), tuple(bands.dom[1]))
-        k = bands.__dict__["_memo_key"] = (bands.ptr, bands.n, bands.fast_d, bands.fast_obs, bands.gpm_frags,
-                                           bool(bands.gpm_global), bands.layout, dom, bool(bands.tip_maps))
+        # the serial number tells two tables apart whose descriptors land at the same (recycled)
+        # device address: an argument block also carries what follows from the table's
+        # emulators (the line table), which the address does not identify
+        k = bands.__dict__["_memo_key"] = (next(_TABLE_SERIAL), bands.ptr, bands.n, bands.fast_d, bands.fast_obs,
+                                           bands.gpm_frags, bool(bands.gpm_global), bands.layout, dom,
+                                           bool(bands.tip_maps))
     return k
 
 
@@ -171,6 +177,11 @@ class Variant(IntEnum):
     BLOCK_ORDER = 16         # exponent MFMAs block by block
     GENERIC_SPEC = 18        # fused forecast through the generic launch instead of SPEC_PROP
     DENSE_SOLVE = 20         # the dense solve where the JRC-TIP structure would select the structure-aware one
+    # lo half of the GP values by v_fma_mixlo/mixhi_f16 (kf_gp_mfma.h gpm_exp_split MIXLO: the split
+    # before profiles/split_issue_probe.jsonl, the same bits).  Built for the JRC-TIP LDS-table and
+    # the 10-parameter global-table kernels with DN16 observations, both forms (kf_device.h
+    # mixlo_split_analysis / mixlo_split_gain); any other launch with it raises.
+    MIXLO_SPLIT = 22
 
 
 # analysis variant of launches that pass none (tests switch it to an oracle path;
@@ -358,9 +369,11 @@ def tip_structure(n_params, bands: BandTable, prop, variant=None) -> int:
     so does its Cholesky factor, which the structure-aware solve skips.
     ``A_STRUCT_TIP_PRIOR`` in addition when that precision is diagonal plus the
     (2, 5) pair and finite with finite reset means (the kernels' unobserved-wave
-    shortcut).  0 (the dense solve) otherwise and for every oracle variant."""
+    shortcut).  0 (the dense solve) otherwise and for every oracle variant but
+    ``MIXLO_SPLIT`` (the default's kernels with the other split)."""
     v = DEFAULT_VARIANT if variant is None else variant
-    if prop is None or n_params != 7 or not bands.tip_maps or int(v) != int(Variant.DEFAULT):
+    if prop is None or n_params != 7 or not bands.tip_maps or int(v) not in (int(Variant.DEFAULT),
+                                                                             int(Variant.MIXLO_SPLIT)):
         return 0
     c = [float(x) for x in list(prop.args.reset_cinv)[:ntri(7)]]
     if any(c[_tri(7, i, j)] != 0.0 for i, j in TIP_ZERO_ENTRIES):
@@ -771,6 +784,7 @@ def gain(n_params, bands: BandTable, x_prev, x_f, p_f, x_out, p_out=None, status
                        and n_params in GAIN_GLOBAL_D and DEFAULT_VARIANT != Variant.VALU_ORACLE)
     if a.gpm_global and bands.layout == BAND_LAYOUT_SHARED_X and DEFAULT_VARIANT != Variant.PER_BAND_OPERAND:
         a.band_layout = BAND_LAYOUT_SHARED_X
+    a.split_mixlo = int(DEFAULT_VARIANT == Variant.MIXLO_SPLIT)
     a.bands = bands.ptr
     a.x_prev, a.x_f, a.p_f, a.x_out, a.p_out = map(_ptr, (x_prev, x_f, p_f, x_out, p_out))
     a.status, a.partials = _ptr(status), _ptr(partials)
@@ -1389,6 +1403,24 @@ def gather(src, idx, out=None, rows=None):
     ext().gather(eb, _ptr(src2), _ptr(idx), _ptr(out), n, src2.shape[0], src2.stride(0),
                  out.view(src2.shape[0], -1).stride(0), _stream(src))
     return out.view(-1) if squeeze else out
+
+
+def exp_split_probe(e, mixlo=False):
+    """Test kernel: ``(mh, ml, m)``, the f16 bit patterns (int16 tensors) of the
+    hi and lo halves of m = 2^e as the matrix-core GP loop splits them
+    (kf_gp_mfma.h gpm_exp_split; ``mixlo``: the ``Variant.MIXLO_SPLIT`` body)
+    and the kernel's float32 m itself.  ``e``: float32, device."""
+    if e.dtype != torch.float32 or not e.is_contiguous() or e.dim() != 1 or not _dev(e):
+        raise ValueError("e must be a contiguous float32 device vector")
+    n = e.numel()
+    n8 = (n + 7) // 8    # the kernel splits whole groups of 8 (padded with e = 0)
+    ep = torch.zeros(8 * n8, dtype=torch.float32, device=e.device)
+    ep[:n] = e
+    mh = torch.empty(8 * n8, dtype=torch.int16, device=e.device)
+    ml = torch.empty_like(mh)
+    m = torch.empty_like(ep)
+    ext().exp_split_probe(_ptr(ep), _ptr(mh), _ptr(ml), _ptr(m), n8, bool(mixlo), _stream(e))
+    return mh[:n], ml[:n], m[:n]
 
 
 def lut_nearest(lut, x, out=None, N=None):
