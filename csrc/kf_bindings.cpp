@@ -317,13 +317,21 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     else check_host(host_unpack(np, P<const float>(x), P<const float>(a), N, ld, P<const int64_t>(idx),
                                 P<float>(mean), P<float>(unc), plane), "unpack");
   });
-  // GeoTIFF tile encoder (predictor 3 + fixed-Huffman zlib per 256^2 tile)
+  // GeoTIFF tile encoder (predictor 3 + one zlib stream per 256^2 tile; mode:
+  // fixed Huffman, or a dynamic table per tile where that is smaller)
   m.attr("DFL_TILE") = DFL_TILE;
   m.attr("DFL_BOUND") = DFL_BOUND;
   m.attr("DFL_ROW_SCRATCH") = (int64_t)DFL_TILE * DFL_ROW_WORDS * 4;   // scratch bytes per tile (device)
+  m.attr("DFL_ROW_SCRATCH_DYN") = (int64_t)DFL_TILE * DFL_ROW_WORDS_DYN * 4;   // the same, dynamic mode
+  m.attr("DFL_MODE_FIXED") = DFL_MODE_FIXED;
+  m.attr("DFL_MODE_DYNAMIC") = DFL_MODE_DYNAMIC;
+  m.attr("DFL_MODE_DYNAMIC_FORCE_FIXED") = DFL_MODE_DYNAMIC_FORCE_FIXED;   // host runner only (tests)
   m.def("deflate_tiles", [](uintptr_t src, int64_t plane_ld, int H, int W, int nplanes, uintptr_t out,
-                            uintptr_t sizes, bool device, uintptr_t stream, uintptr_t scratch) {
+                            uintptr_t sizes, bool device, uintptr_t stream, uintptr_t scratch, int mode) {
     DflArgs a{};
+    a.mode = mode;
+    if (mode != DFL_MODE_FIXED && mode != DFL_MODE_DYNAMIC && !(mode == DFL_MODE_DYNAMIC_FORCE_FIXED && !device))
+      throw std::runtime_error("deflate_tiles: unknown mode");
     a.src = P<const float>(src);
     a.plane_ld = plane_ld;
     a.H = H;
@@ -341,7 +349,8 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
       py::gil_scoped_release nogil;
       check_host(host_deflate_tiles(a), "deflate_tiles");
     }
-  });
+  }, py::arg("src"), py::arg("plane_ld"), py::arg("H"), py::arg("W"), py::arg("nplanes"), py::arg("out"),
+     py::arg("sizes"), py::arg("device"), py::arg("stream"), py::arg("scratch"), py::arg("mode") = (int)DFL_MODE_FIXED);
   m.def("deflate_pack", [](uintptr_t scratch, uintptr_t sizes, uintptr_t offs, uintptr_t packed, int ntiles,
                            uintptr_t stream) {
     check_hip(dev_deflate_pack(P<const uint8_t>(scratch), P<const uint32_t>(sizes), P<const int64_t>(offs),

@@ -1,6 +1,7 @@
 // kf_deflate.hip — device GeoTIFF tile encoder (kf_deflate.h): predictor 3 +
-// one fixed-Huffman zlib stream per 256 x 256 float32 tile, then the tiles
-// packed back to back.  Reference-cadence output (observations.py:354-394)
+// one zlib stream per 256 x 256 float32 tile (fixed Huffman: dfl_tile_kernel,
+// described first; a dynamic table per tile: dfl_tile_dyn_kernel), then the tiles
+// packed back to back. Reference-cadence output (observations.py:354-394)
 // then ships compressed tiles to the host instead of raw planes, and the host
 // writer only writes files.
 //
@@ -149,6 +150,182 @@ __global__ __launch_bounds__(DFL_TILE) void dfl_tile_kernel(DflArgs a) {
   if (shared_left) out[start >> 5] = head | tail[r - 1];
 }
 
+// Dynamic-Huffman mode (kf_deflate.h): the same launch shape, three passes.
+//   count:  each thread tokenises its row into a per-wave LDS histogram
+//           (integer LDS adds: any order gives the same counts) and sums its
+//           Adler partials;
+//   build:  the used symbols are ranked by (frequency, index), one or two
+//           symbols per thread; lane 0 derives the code lengths, the codes and
+//           the header, compares the block with the fixed one and leaves the
+//           chosen table in LDS;
+//   encode: each thread tokenises its row again, with the table, into its
+//           scratch slot (DFL_ROW_WORDS_DYN words: up to 15 bits per byte);
+//           a workgroup scan gives the bit offsets, then the shift.
+// A row here can be shorter than a word (a constant tile: ~33 bits), so any
+// number of rows may share a word: every word that a row covers only in part
+// is zeroed first and then receives the rows' disjoint bit ranges by atomic OR
+// (order-independent); words wholly inside a row are stored directly.
+__global__ __launch_bounds__(DFL_TILE) void dfl_tile_dyn_kernel(DflArgs a) {
+  const int tile = blockIdx.x;
+  const int per = a.tiles_x * a.tiles_y;
+  const int plane = tile / per, tt = tile - plane * per;
+  const int ty = tt / a.tiles_x, tx = tt - ty * a.tiles_x;
+  const int r = threadIdx.x;
+  const int64_t y = (int64_t)ty * DFL_TILE + r;
+  const int x0 = tx * DFL_TILE;
+  const bool rin = y < a.H;
+  const int ncol = a.W - x0 < DFL_TILE ? a.W - x0 : DFL_TILE;
+  const float* rowp = a.src + (int64_t)plane * a.plane_ld + (rin ? y : 0) * a.W + x0;
+  __shared__ uint32_t line[DFL_TILE][17];
+  auto row = [&](int c) -> uint32_t {
+    if ((c & 15) == 0) {
+      uint32_t v[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = (rin && c + j < ncol) ? __float_as_uint(rowp[c + j]) : 0u;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) line[r][j] = v[j];
+    }
+    return line[r][c & 15];
+  };
+  const int64_t rest = DFL_RAW - (int64_t)r * DFL_ROW;
+
+  __shared__ uint32_t hist[DFL_TILE / 64][DFL_NSYM];
+  __shared__ DflTable tab;
+  __shared__ DflWork work;
+  __shared__ int used;
+  __shared__ uint64_t scan[DFL_TILE];
+  __shared__ uint64_t red1[DFL_TILE / 64], red2[DFL_TILE / 64];
+
+  // count
+  for (int i = r; i < (DFL_TILE / 64) * DFL_NSYM; i += DFL_TILE) (&hist[0][0])[i] = 0;
+  if (r == 0) used = 0;
+  __syncthreads();
+  uint64_t s1 = 0, s2 = 0;
+  {
+    uint32_t* h = hist[r >> 6];
+    dfl_tokenise_row(row, rest, [&](uint32_t v, int L) { atomicAdd(&h[dfl_token_symbol(v, L)], 1u); }, s1, s2);
+  }
+  uint64_t w1 = s1, w2 = s2;
+  for (int o = 32; o > 0; o >>= 1) {
+    w1 += __shfl_down(w1, o, 64);
+    w2 += __shfl_down(w2, o, 64);
+  }
+  if ((r & 63) == 0) {
+    red1[r >> 6] = w1;
+    red2[r >> 6] = w2;
+  }
+  __syncthreads();
+  uint32_t* freq = hist[0];
+  for (int i = r; i < DFL_NSYM; i += DFL_TILE) {
+    uint32_t f = 0;
+#pragma unroll
+    for (int w = 0; w < DFL_TILE / 64; ++w) f += hist[w][i];
+    freq[i] = i == 256 ? 1u : f;               // the end-of-block code
+  }
+  __syncthreads();
+
+  // build
+  for (int i = r; i < DFL_NSYM; i += DFL_TILE) {
+    const int rk = dfl_rank(freq, DFL_NSYM, i);
+    if (rk >= 0) {
+      work.sorted[rk] = (uint16_t)i;
+      atomicAdd(&used, 1);
+    }
+  }
+  __syncthreads();
+  if (r == 0) dfl_choose_table(freq, used, false, tab, work);
+  __syncthreads();
+
+  // encode: the row's bit string into its own word-aligned scratch slot
+  uint32_t* rs = reinterpret_cast<uint32_t*>(a.scratch) + ((int64_t)tile * DFL_TILE + r) * DFL_ROW_WORDS_DYN;
+  uint64_t nbits = 0;
+  {
+    uint64_t acc = 0, u1, u2;
+    int nacc = 0, wi = 0;
+    dfl_tokenise_row(row, rest, [&](uint32_t v, int L) {
+      uint32_t bits;
+      int len;
+      dfl_table_token(tab, v, L, bits, len);
+      acc |= (uint64_t)bits << nacc;
+      nacc += len;
+      nbits += (uint64_t)len;
+      if (nacc >= 32) {
+        rs[wi++] = (uint32_t)acc;
+        acc >>= 32;
+        nacc -= 32;
+      }
+    }, u1, u2);
+    if (nacc > 0) rs[wi] = (uint32_t)acc;
+  }
+  KF_DCHECK(nbits >= 1 && nbits <= 32u * (DFL_ROW_WORDS_DYN - 1));
+
+  scan[r] = nbits;
+  __syncthreads();
+  // inclusive Hillis-Steele scan of the row bit counts
+  for (int o = 1; o < DFL_TILE; o <<= 1) {
+    const uint64_t v = r >= o ? scan[r - o] : 0;
+    __syncthreads();
+    scan[r] += v;
+    __syncthreads();
+  }
+  uint64_t t1 = 0, t2 = 0;
+#pragma unroll
+  for (int w = 0; w < DFL_TILE / 64; ++w) {
+    t1 += red1[w];
+    t2 += red2[w];
+  }
+  const uint32_t adler = dfl_adler(t1, t2, DFL_RAW);
+
+  // this thread's bit range [b0, b1) of the stream: its row, with the zlib and
+  // block headers in front of row 0 and the end-of-block code, the byte
+  // padding and the Adler-32 behind row 255
+  const uint64_t start = 16u + tab.head_bits + scan[r] - nbits;
+  const uint64_t b0 = r == 0 ? 0 : start;
+  uint64_t b1 = start + nbits;
+  const int eobl = tab.len[256];
+  if (r == DFL_TILE - 1) b1 = ((b1 + eobl + 7u) & ~(uint64_t)7u) + 32u;
+  KF_DCHECK(r != DFL_TILE - 1 || b1 <= 8u * (uint64_t)DFL_BOUND);
+  uint32_t* out = reinterpret_cast<uint32_t*>(a.out + (int64_t)tile * DFL_BOUND);
+  if (b0 & 31u) out[b0 >> 5] = 0u;
+  if (b1 & 31u) out[(b1 - 1) >> 5] = 0u;
+  __threadfence();
+  __syncthreads();
+
+  const bool shared_left = (b0 & 31u) != 0;
+  uint64_t wi = b0 >> 5;
+  uint64_t acc = 0;
+  int nacc = (int)(b0 & 31u);
+  bool first = true;
+  auto sink = [&](uint32_t bits, int len) {
+    acc |= (uint64_t)bits << nacc;
+    nacc += len;
+    while (nacc >= 32) {
+      if (first && shared_left) atomicOr(&out[wi], (uint32_t)acc);
+      else out[wi] = (uint32_t)acc;
+      first = false;
+      ++wi;
+      acc >>= 32;
+      nacc -= 32;
+    }
+  };
+  if (r == 0) {
+    sink(0x0178u, 16);                                   // 78 01
+    dfl_write_block_header(tab, sink);
+  }
+  const int full = (int)(nbits >> 5), part = (int)(nbits & 31u);
+  for (int k = 0; k < full; ++k) sink(rs[k], 32);
+  if (part) sink(rs[full] & ((1u << part) - 1u), part);
+  if (r == DFL_TILE - 1) {
+    sink(tab.code[256], eobl);                           // end of block
+    const int pad = (8 - (int)(((wi << 5) + nacc) & 7u)) & 7;
+    if (pad) sink(0u, pad);
+    for (int k = 3; k >= 0; --k) sink((adler >> (8 * k)) & 0xFFu, 8);   // Adler-32, big-endian bytes
+    a.sizes[tile] = (uint32_t)(b1 >> 3);
+  }
+  KF_DCHECK((wi << 5) + (uint64_t)nacc == b1);
+  if (nacc > 0) atomicOr(&out[wi], (uint32_t)acc);       // the last word: covered in part
+}
+
 // tile t's stream (sizes[t] bytes at t * DFL_BOUND) -> packed + offs[t]
 __global__ __launch_bounds__(256) void dfl_pack_kernel(const uint8_t* scratch, const uint32_t* sizes,
                                                        const int64_t* offs, uint8_t* packed) {
@@ -162,7 +339,9 @@ __global__ __launch_bounds__(256) void dfl_pack_kernel(const uint8_t* scratch, c
 hipError_t dev_deflate_tiles(const DflArgs& a, hipStream_t s) {
   const int n = a.nplanes * a.tiles_x * a.tiles_y;
   if (n <= 0 || a.W <= 0 || a.H <= 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(dfl_tile_kernel, dim3(n), dim3(DFL_TILE), 0, s, a);
+  if (a.mode == DFL_MODE_FIXED) hipLaunchKernelGGL(dfl_tile_kernel, dim3(n), dim3(DFL_TILE), 0, s, a);
+  else if (a.mode == DFL_MODE_DYNAMIC) hipLaunchKernelGGL(dfl_tile_dyn_kernel, dim3(n), dim3(DFL_TILE), 0, s, a);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

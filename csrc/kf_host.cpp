@@ -180,11 +180,15 @@ static int h_unpack(const float* x, const float* a, int64_t N, int64_t ld, const
 }
 
 // GeoTIFF tiles on the host: the same row encoder as dfl_tile_kernel, rows in
-// order into one byte stream per tile (bit-identical streams)
+// order into one byte stream per tile (bit-identical streams).  Dynamic mode:
+// the same two passes as dfl_tile_dyn_kernel (histogram, table, encode).
+// Returns -2 if a tile's stream is not the size its table announced.
 int host_deflate_tiles(const DflArgs& a) {
   const int per = a.tiles_x * a.tiles_y, n = a.nplanes * per;
   if (n <= 0) return -1;
-#pragma omp parallel for schedule(dynamic, 1)
+  if (a.mode != DFL_MODE_FIXED && a.mode != DFL_MODE_DYNAMIC && a.mode != DFL_MODE_DYNAMIC_FORCE_FIXED) return -1;
+  int bad = 0;
+#pragma omp parallel for schedule(dynamic, 1) reduction(| : bad)
   for (int tile = 0; tile < n; ++tile) {
     const int plane = tile / per, tt = tile - plane * per;
     const int ty = tt / a.tiles_x, tx = tt - ty * a.tiles_x;
@@ -203,33 +207,74 @@ int host_deflate_tiles(const DflArgs& a) {
         nacc -= 8;
       }
     };
+    // fn(r, row, rest) for every row of the tile
+    auto rows = [&](auto&& fn) {
+      for (int r = 0; r < DFL_TILE; ++r) {
+        const int64_t y = (int64_t)ty * DFL_TILE + r;
+        const bool rin = y < a.H;
+        const float* rowp = a.src + (int64_t)plane * a.plane_ld + (rin ? y : 0) * a.W + x0;
+        auto row = [&](int c) -> uint32_t {
+          if (!(rin && c < ncol)) return 0u;
+          uint32_t u;
+          memcpy(&u, rowp + c, 4);
+          return u;
+        };
+        fn(row, DFL_RAW - (int64_t)r * DFL_ROW);
+      }
+    };
     sink(0x78u, 8);
     sink(0x01u, 8);
-    sink(1u, 1);                 // BFINAL
-    sink(1u, 2);                 // BTYPE 01: fixed Huffman
     uint64_t t1 = 0, t2 = 0;
-    for (int r = 0; r < DFL_TILE; ++r) {
-      const int64_t y = (int64_t)ty * DFL_TILE + r;
-      const bool rin = y < a.H;
-      const float* rowp = a.src + (int64_t)plane * a.plane_ld + (rin ? y : 0) * a.W + x0;
-      auto row = [&](int c) -> uint32_t {
-        if (!(rin && c < ncol)) return 0u;
-        uint32_t u;
-        memcpy(&u, rowp + c, 4);
-        return u;
-      };
-      uint64_t s1, s2;
-      dfl_encode_row(row, DFL_RAW - (int64_t)r * DFL_ROW, sink, s1, s2);
-      t1 += s1;
-      t2 += s2;
+    if (a.mode == DFL_MODE_FIXED) {
+      sink(1u, 1);                 // BFINAL
+      sink(1u, 2);                 // BTYPE 01: fixed Huffman
+      rows([&](auto& row, int64_t rest) {
+        uint64_t s1, s2;
+        dfl_encode_row(row, rest, sink, s1, s2);
+        t1 += s1;
+        t2 += s2;
+      });
+      sink(0u, 7);                 // end of block
+    } else {
+      uint32_t freq[DFL_NSYM] = {0};
+      DflTable t;
+      DflWork k;
+      rows([&](auto& row, int64_t rest) {
+        uint64_t s1, s2;
+        dfl_tokenise_row(row, rest, [&](uint32_t v, int L) { ++freq[dfl_token_symbol(v, L)]; }, s1, s2);
+        t1 += s1;
+        t2 += s2;
+      });
+      freq[256] = 1;
+      int used = 0;
+      for (int s = 0; s < DFL_NSYM; ++s) {
+        const int rk = dfl_rank(freq, DFL_NSYM, s);
+        if (rk >= 0) {
+          k.sorted[rk] = (uint16_t)s;
+          ++used;
+        }
+      }
+      dfl_choose_table(freq, used, a.mode == DFL_MODE_DYNAMIC_FORCE_FIXED, t, k);
+      dfl_write_block_header(t, sink);
+      if ((uint64_t)(nb - 2) * 8 + (uint64_t)nacc != t.head_bits) bad |= 1;
+      rows([&](auto& row, int64_t rest) {
+        uint64_t s1, s2;
+        dfl_tokenise_row(row, rest, [&](uint32_t v, int L) {
+          uint32_t b;
+          int l;
+          dfl_table_token(t, v, L, b, l);
+          sink(b, l);
+        }, s1, s2);
+      });
+      sink(t.code[256], t.len[256]);   // end of block
+      if ((uint64_t)(nb - 2) * 8 + (uint64_t)nacc != t.block_bits) bad |= 1;
     }
-    sink(0u, 7);                 // end of block
     if (nacc) sink(0u, 8 - nacc);
     const uint32_t adler = dfl_adler(t1, t2, DFL_RAW);
     for (int k = 3; k >= 0; --k) sink((adler >> (8 * k)) & 0xFFu, 8);
     a.sizes[tile] = (uint32_t)nb;
   }
-  return 0;
+  return bad ? -2 : 0;
 }
 
 int host_analysis(int np, const AnalysisArgs& a, int grid) { KF_HOST_NP_SWITCH(np, h_analysis, a, grid); }

@@ -103,10 +103,11 @@ int host_reg_schedule(const RegScheduleArgs& a);
 struct DflArgs {
   const float* src;
   int64_t plane_ld;
-  int32_t H, W, nplanes, tiles_x, tiles_y, pad_;
+  int32_t H, W, nplanes, tiles_x, tiles_y, mode;   // mode: DFL_MODE_* (kf_deflate.h); 0 = fixed Huffman
   uint8_t* out;
   uint32_t* sizes;
-  uint8_t* scratch;   // device: DFL_TILE * DFL_ROW_WORDS words per tile (row bit strings before the shift)
+  uint8_t* scratch;   // device: DFL_TILE * DFL_ROW_WORDS words per tile (row bit strings before the shift;
+                      // DFL_ROW_WORDS_DYN in the dynamic mode)
 };
 hipError_t dev_deflate_tiles(const DflArgs& a, hipStream_t s);
 hipError_t dev_deflate_pack(const uint8_t* scratch, const uint32_t* sizes, const int64_t* offs, uint8_t* packed,

@@ -108,19 +108,30 @@ class KafkaOutput:
 
     ``encoder``: "device" encodes the DEFLATE tiles on the GPU
     (``ops.kernels.TileEncoder``, csrc/kf_deflate.hip: predictor 3 and one
-    fixed-Huffman zlib stream per 256 x 256 tile) on the side stream, so only
+    zlib stream per 256 x 256 tile) on the side stream, so only
     the compressed tiles cross PCIe and the writer thread only writes files;
     "host" sends the raw planes to the native CPU encoder (``level``,
     ``strategy``, ``predictor``); "auto" (default): device for GPU planes with
-    DEFLATE output in 256-pixel tiles."""
+    DEFLATE output in 256-pixel tiles.
+
+    ``huffman``: the device encoder's block type.  "fixed" (default): one
+    fixed-Huffman block per tile.  "dynamic": one Huffman table per tile, built
+    on the device from the tile's token histogram, wherever that makes the
+    tile smaller (never larger than "fixed"; the files decode the same).  The
+    host encoder has no such mode: "dynamic" with ``encoder="host"`` raises."""
 
     def __init__(self, parameter_list, geotransform, projection, folder, prefix=None, fmt="GTiff",
                  compress="deflate", asynchronous=True, level: int = 6, tile: int = 256, gather: bool = False,
                  threads: int | None = None, predictor: int = 1, strategy: str | None = None,
-                 keep_timesteps: int | None = None, encoder: str = "auto"):
+                 keep_timesteps: int | None = None, encoder: str = "auto", huffman: str = "fixed"):
         if encoder not in ("auto", "device", "host"):
             raise ValueError("encoder must be 'auto', 'device' or 'host'")
+        if huffman not in ("fixed", "dynamic"):
+            raise ValueError("huffman must be 'fixed' or 'dynamic'")
+        if huffman == "dynamic" and encoder == "host":
+            raise ValueError("huffman='dynamic' is a mode of the device encoder (encoder='device' or 'auto')")
         self.encoder = encoder
+        self.huffman = huffman
         self._enc = None          # ops.kernels.TileEncoder (device encoder)
         self._copier = None       # device encoder: the thread bringing compressed tiles to pinned memory
         self._eslots = []         # device encoder: ring of 2 (packed device buffer, meta pinned, host pinned, done)
@@ -217,7 +228,7 @@ class KafkaOutput:
         if self.compress != "deflate":
             return None
         if self._eslots:
-            return "device (fixed-Huffman run-length zlib streams, kf_deflate.hip)"
+            return f"device ({self.huffman}-Huffman run-length zlib streams, kf_deflate.hip)"
         from .tiff import _native
         E = _native()
         if E is None or not self.tile:
@@ -242,9 +253,11 @@ class KafkaOutput:
         self._ship(timestep, engine)
 
     def _device_encode(self, cuda: bool) -> bool:
+        ok = self.encoder != "host" and cuda and self.compress == "deflate" and self.tile == 256
+        if self.huffman == "dynamic" and not ok:
+            raise ValueError("huffman='dynamic' needs the device encoder: GPU planes, DEFLATE output, 256-pixel tiles")
         if self.encoder == "host" or not cuda or self.compress != "deflate":
             return False
-        ok = self.tile == 256
         if self.encoder == "device" and not ok:
             raise ValueError("the device encoder writes 256-pixel tiles")
         return ok
@@ -316,7 +329,7 @@ class KafkaOutput:
         if self._stream is None:
             self._stream = torch.cuda.Stream(dev)
         if self._enc is None:
-            self._enc = TileEncoder()
+            self._enc = TileEncoder(huffman=self.huffman)
         tx, ty = TileEncoder.tiles(H, W)
         per = tx * ty
         nt = n * per

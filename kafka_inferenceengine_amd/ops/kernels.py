@@ -1296,9 +1296,21 @@ class TileEncoder:
     ``encode(planes, H, W)`` -> (packed uint8, sizes int64, offsets int64), all
     on the planes' device and queued on the current stream; the scratch and
     packed buffers are kept for the next call of the same shape.  On the CPU
-    the host runner of the same row encoder produces the same bytes."""
+    the host runner of the same row encoder produces the same bytes.
 
-    def __init__(self):
+    ``huffman``: "fixed" (default) writes every tile as one fixed-Huffman
+    block.  "dynamic" builds one Huffman table per tile from the tile's own
+    token histogram (same tokens) and writes a dynamic block wherever that is
+    strictly smaller, else the fixed block: a tile is never larger than in
+    the fixed mode.  The dynamic mode tokenises every row twice and needs the
+    larger row scratch (15 instead of 9 bits per byte), allocated only then."""
+
+    MODES = ("fixed", "dynamic")
+
+    def __init__(self, huffman: str = "fixed"):
+        if huffman not in self.MODES:
+            raise ValueError("huffman must be 'fixed' or 'dynamic'")
+        self.huffman = huffman
         self._bufs = {}
 
     @staticmethod
@@ -1327,9 +1339,12 @@ class TileEncoder:
         dev = planes.device
         scratch = self._buf("scratch", nt * bound, torch.uint8, dev)
         sizes = self._buf("sizes", nt, torch.int32, dev)        # uint32 byte counts (< 2^31)
-        rows = self._buf("rows", nt * int(ext().DFL_ROW_SCRATCH), torch.uint8, dev) if _dev(planes) else None
+        dyn = self.huffman == "dynamic"
+        row_bytes = int(ext().DFL_ROW_SCRATCH_DYN if dyn else ext().DFL_ROW_SCRATCH)
+        rows = self._buf("rows", nt * row_bytes, torch.uint8, dev) if _dev(planes) else None
         ext().deflate_tiles(_ptr(planes), planes.stride(0), int(H), int(W), int(n), _ptr(scratch), _ptr(sizes),
-                            _dev(planes), _stream(planes), _ptr(rows))
+                            _dev(planes), _stream(planes), _ptr(rows),
+                            int(ext().DFL_MODE_DYNAMIC if dyn else ext().DFL_MODE_FIXED))
         s64 = sizes.to(torch.int64)
         offs = torch.cumsum(s64, 0) - s64
         if base is not None:

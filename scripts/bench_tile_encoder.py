@@ -1,0 +1,147 @@
+#!/usr/bin/env python
+"""Bytes and time of the GeoTIFF tile encoder's two block types on rasters.
+
+Inputs are float32 rasters: ``.npy`` files (``bench.py --dump-outputs`` writes
+``output_mean.npy`` / ``output_unc.npy`` as [n_params, n] arrays; [n, H, W] and
+[H, W] arrays are taken as they are) and GeoTIFFs the engine wrote.  An
+[n, N] array becomes n rasters of ``--width`` columns (default 256: one tile
+column); ``bench.py`` samples jobs above 131,072 pixels, so its rows are then
+pixel samples in raster order, not neighbours -- the report says so.
+
+Per raster and in total: the bytes of the fixed and the dynamic mode
+(``ops.kernels.TileEncoder``), and of zlib level 1 with the default strategy
+and with ``Z_RLE`` on the same predicted bytes (predictor 3, one stream per
+256 x 256 tile).  On a GPU, the event-timed encode of both modes over all
+planes of an input.  One JSON line per raster, one per input and a total.
+
+    python scripts/bench_tile_encoder.py dump/output_mean.npy dump/output_unc.npy
+    python scripts/bench_tile_encoder.py out/*_A2017017*.tif --crop 3882 --device cuda
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import zlib
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from kafka_inferenceengine_amd.ops.kernels import TileEncoder  # noqa: E402
+
+
+def load(path, width, crop):
+    """-> (planes [n, H, W] float32, note)"""
+    note = None
+    if path.endswith(".npy"):
+        a = np.load(path)
+        if a.ndim == 2 and a.shape[0] <= 64 and a.shape[1] > 4096:      # [n, N]: planes of pixel columns
+            n, N = a.shape
+            rows = N // width
+            a = a[:, :rows * width].reshape(n, rows, width)
+            note = f"[n, N] array folded into rows of {width}: neighbours in a row are samples, not adjacent pixels"
+        elif a.ndim == 2:
+            a = a[None]
+    else:
+        from kafka_inferenceengine_amd.input_output.tiff import read_tiff
+        a = read_tiff(path)[0][None]
+    a = np.ascontiguousarray(a, np.float32)
+    if crop:
+        H, W = a.shape[1:]
+        y0, x0 = max(0, (H - crop) // 2), max(0, (W - crop) // 2)
+        a = np.ascontiguousarray(a[:, y0:y0 + crop, x0:x0 + crop])
+    return a, note
+
+
+def pred3_tiles(plane):
+    """Predictor-3 bytes of every zero-padded 256^2 tile of one raster (TIFF TN3)."""
+    H, W = plane.shape
+    ty, tx = -(-H // 256), -(-W // 256)
+    full = np.zeros((ty * 256, tx * 256), np.float32)
+    full[:H, :W] = plane
+    for j in range(ty):
+        for i in range(tx):
+            t = np.ascontiguousarray(full[j * 256:(j + 1) * 256, i * 256:(i + 1) * 256])
+            b = t.view(np.uint8).reshape(256, 256, 4)[:, :, ::-1]
+            rows = np.ascontiguousarray(b.transpose(0, 2, 1)).reshape(256, 1024)
+            d = rows.copy()
+            d[:, 1:] = rows[:, 1:] - rows[:, :-1]
+            yield d.tobytes()
+
+
+def zlib_bytes(plane):
+    out = [0, 0]
+    for raw in pred3_tiles(plane):
+        for s, strategy in enumerate((zlib.Z_DEFAULT_STRATEGY, zlib.Z_RLE)):
+            c = zlib.compressobj(1, zlib.DEFLATED, 15, 8, strategy)
+            out[s] += len(c.compress(raw)) + len(c.flush())
+    return out
+
+
+def encode(planes, device, reps):
+    """-> {mode: (per-plane bytes, ms per encode of all planes or None)}"""
+    n, H, W = planes.shape
+    t = torch.from_numpy(planes.reshape(n, -1)).to(device)
+    tiles = TileEncoder.tiles(H, W)
+    per = tiles[0] * tiles[1]
+    res = {}
+    for mode in TileEncoder.MODES:
+        enc = TileEncoder(huffman=mode)
+        _, sizes, _ = enc.encode(t, H, W)
+        ms = None
+        if t.is_cuda:
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                enc.encode(t, H, W)
+                e1.record()
+                e1.synchronize()
+                times.append(e0.elapsed_time(e1))
+            ms = [round(x, 3) for x in sorted(times)]
+        res[mode] = (sizes.cpu().numpy().reshape(n, per).sum(1), ms)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("inputs", nargs="+")
+    ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--width", type=int, default=256, help="columns of a raster folded from an [n, N] array")
+    ap.add_argument("--crop", type=int, default=0, help="central crop x crop window of every raster (0: all of it)")
+    ap.add_argument("--reps", type=int, default=5, help="timed encodes per mode (GPU)")
+    ap.add_argument("--no-zlib", action="store_true", help="skip the zlib columns")
+    a = ap.parse_args()
+    keys = ("raw", "fixed", "dynamic", "zlib1", "zlib1_rle")
+    total = dict.fromkeys(keys, 0)
+    for path in a.inputs:
+        planes, note = load(path, a.width, a.crop)
+        n, H, W = planes.shape
+        res = encode(planes, torch.device(a.device), a.reps)
+        tx, ty = TileEncoder.tiles(H, W)
+        sub = dict.fromkeys(keys, 0)
+        for p in range(n):
+            z = [0, 0] if a.no_zlib else zlib_bytes(planes[p])
+            rec = {"raw": H * W * 4, "fixed": int(res["fixed"][0][p]),
+                   "dynamic": int(res["dynamic"][0][p]), "zlib1": z[0], "zlib1_rle": z[1]}
+            for key in keys:
+                sub[key] += rec[key]
+            print(json.dumps({"input": os.path.basename(path), "plane": p, "shape": [H, W], **rec,
+                              **{f"ratio_{m}": round(rec["raw"] / rec[m], 4) for m in keys[1:] if rec[m]}}))
+        for key in keys:
+            total[key] += sub[key]
+        print(json.dumps({"input": os.path.basename(path), "planes": n, "shape": [H, W], **sub,
+                          **{f"ratio_{m}": round(sub["raw"] / sub[m], 4) for m in keys[1:] if sub[m]},
+                          "encode_ms_fixed": res["fixed"][1], "encode_ms_dynamic": res["dynamic"][1],
+                          **({"note": note} if note else {})}))
+    print(json.dumps({"total": True, **total,
+                      **{f"ratio_{m}": round(total["raw"] / total[m], 4) for m in keys[1:] if total[m]},
+                      "dynamic_over_fixed": round(total["dynamic"] / total["fixed"], 4)}))
+
+
+if __name__ == "__main__":
+    main()
