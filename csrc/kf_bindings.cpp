@@ -10,6 +10,7 @@
 #include <vector>
 #include "kf_launch.h"
 #include "kf_deflate.h"
+#include "kf_inflate.h"
 #include "kf_stream.h"
 
 namespace py = pybind11;
@@ -356,6 +357,58 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     check_hip(dev_deflate_pack(P<const uint8_t>(scratch), P<const uint32_t>(sizes), P<const int64_t>(offs),
                                P<uint8_t>(packed), ntiles, (hipStream_t)stream), "deflate_pack");
   });
+  // GeoTIFF tile decoder (kf_inflate.h): zlib streams -> predictor undone -> window of a plane
+  m.attr("INF_OK") = INF_OK;
+  m.attr("INF_STATUS_NAMES") = std::vector<std::string>{
+      "INF_OK", "INF_TRUNCATED", "INF_BAD_HEADER", "INF_BAD_BLOCK", "INF_BAD_STORED", "INF_BAD_CODE",
+      "INF_BAD_SYMBOL", "INF_BAD_DISTANCE", "INF_OVERRUN", "INF_SHORT", "INF_BAD_ADLER"};
+  static_assert(INF_NSTATUS == 11, "INF_STATUS_NAMES lists every status");
+  m.def("inflate_scratch_stride", [](int64_t raw_bytes, int tile, int elem_bytes) {
+    return inf_scratch_stride(raw_bytes, tile, elem_bytes);
+  });
+  m.def("inflate_count_tokens", [](uintptr_t comp, int64_t comp_bytes, uintptr_t offs, uintptr_t sizes, int ntiles,
+                                   int64_t raw_bytes) {
+    py::gil_scoped_release nogil;
+    return host_inflate_count_tokens(P<const uint8_t>(comp), comp_bytes, P<const int64_t>(offs),
+                                     P<const int64_t>(sizes), ntiles, raw_bytes);
+  }, "literal + match tokens of host-memory zlib streams (-1: a stream does not decode)");
+  m.def("inflate_tiles", [](uintptr_t comp, int64_t comp_bytes, uintptr_t offs, uintptr_t sizes, uintptr_t tile_rc,
+                            int ntiles, int tile, int elem_bytes, int predictor, int64_t raw_bytes, int64_t r0,
+                            int64_t r1, int64_t c0, int64_t c1, uintptr_t dst, int64_t ld, uintptr_t status,
+                            bool device, uintptr_t stream, uintptr_t scratch) {
+    InfArgs a{};
+    a.comp = P<const uint8_t>(comp);
+    a.comp_bytes = comp_bytes;
+    a.offs = P<const int64_t>(offs);
+    a.sizes = P<const int64_t>(sizes);
+    a.tile_rc = P<const int32_t>(tile_rc);
+    a.ntiles = ntiles;
+    a.tile = tile;
+    a.elem_bytes = elem_bytes;
+    a.predictor = predictor;
+    a.raw_bytes = raw_bytes;
+    a.r0 = r0;
+    a.r1 = r1;
+    a.c0 = c0;
+    a.c1 = c1;
+    a.dst = P<void>(dst);
+    a.ld = ld;
+    a.status = P<int32_t>(status);
+    a.scratch = P<uint8_t>(scratch);
+    if (!inf_args_ok(a))
+      throw std::runtime_error("inflate_tiles: 256-pixel tiles of 16-bit (predictor 1, 2) or float32 (predictor 1, 3) "
+                               "samples and a non-empty window that fits ld");
+    if (device) {
+      if (!scratch) throw std::runtime_error("inflate_tiles: the device decoder needs its raw-tile scratch");
+      check_hip(dev_inflate_tiles(a, (hipStream_t)stream), "inflate_tiles");
+    } else {
+      py::gil_scoped_release nogil;
+      check_host(host_inflate_tiles(a), "inflate_tiles");
+    }
+  }, py::arg("comp"), py::arg("comp_bytes"), py::arg("offs"), py::arg("sizes"), py::arg("tile_rc"), py::arg("ntiles"),
+     py::arg("tile"), py::arg("elem_bytes"), py::arg("predictor"), py::arg("raw_bytes"), py::arg("r0"), py::arg("r1"),
+     py::arg("c0"), py::arg("c1"), py::arg("dst"), py::arg("ld"), py::arg("status"), py::arg("device"),
+     py::arg("stream"), py::arg("scratch"));
   m.def("reduce_partials", [](uintptr_t partials, int n, uintptr_t out, uintptr_t stream) {
     check_hip(dev_reduce(P<const double>(partials), n, P<double>(out), (hipStream_t)stream), "reduce_partials");
   });

@@ -6,6 +6,7 @@
 #include <string.h>
 #include "kf_launch.h"
 #include "kf_deflate.h"
+#include "kf_inflate.h"
 #include <algorithm>
 #include <vector>
 
@@ -275,6 +276,114 @@ int host_deflate_tiles(const DflArgs& a) {
     a.sizes[tile] = (uint32_t)nb;
   }
   return bad ? -2 : 0;
+}
+
+// GeoTIFF tiles inflated on the host: the decoder of inf_tile_kernel
+// (kf_inflate.h: inf_step) with the serial drain, one tile per OpenMP
+// iteration, then the predictor undo and the placement into the window.
+int host_inflate_tiles(const InfArgs& a) {
+  if (!inf_args_ok(a)) return -1;
+  const int T = a.tile, e = a.elem_bytes;
+  const int64_t row_bytes = (int64_t)T * e, tile_bytes = row_bytes * T;
+  const int64_t stride = inf_scratch_stride(a.raw_bytes, T, e);
+  const uint32_t n = (uint32_t)a.raw_bytes;
+#pragma omp parallel
+  {
+    std::vector<uint8_t> raw((size_t)stride), tmp((size_t)row_bytes);
+    InfTables tab;
+    uint32_t q[INF_QUEUE];
+#pragma omp for schedule(dynamic, 1)
+    for (int tile = 0; tile < a.ntiles; ++tile) {
+      const int64_t off = a.offs[tile], sz = a.sizes[tile];
+      int32_t status = INF_OK;
+      if (off < 0 || sz < 0 || sz > 0x7FFFFFFF || off > a.comp_bytes || sz > a.comp_bytes - off) {
+        status = INF_TRUNCATED;         // the byte range is not inside comp
+      } else {
+        InfState st;
+        inf_init(st, a.comp + off, (uint32_t)sz, n);
+        uint32_t pos = 0;
+        uint64_t s1 = 0, s2 = 0;
+        for (;;) {
+          const int nq = inf_step(st, tab, q, INF_QUEUE);
+          inf_drain_serial(q, nq, raw.data(), pos, n, s1, s2);
+          for (uint32_t j = 0; j < st.sto_len; ++j) {
+            KF_DCHECK(pos + j < n && st.sto_off + j < st.n);
+            const uint32_t b = st.in[st.sto_off + j];
+            raw[pos + j] = (uint8_t)b;
+            inf_adler_add(s1, s2, b, pos + j, n);
+          }
+          pos += st.sto_len;
+          if (st.status != INF_OK || st.phase == INF_P_DONE) break;
+        }
+        status = st.status;
+        if (status == INF_OK && dfl_adler(s1, s2, (int64_t)n) != st.adler) status = INF_BAD_ADLER;
+        for (int64_t i = a.raw_bytes; i < tile_bytes; ++i) raw[(size_t)i] = 0;   // a raw size short of a tile
+      }
+      a.status[tile] = status;
+      // the tile's part of the window
+      const int64_t gy0 = (int64_t)a.tile_rc[2 * tile] * T, gx0 = (int64_t)a.tile_rc[2 * tile + 1] * T;
+      const int64_t ya = std::max(gy0, a.r0), yb = std::min(gy0 + T, a.r1);
+      const int64_t xa = std::max(gx0, a.c0), xb = std::min(gx0 + T, a.c1);
+      if (ya >= yb || xa >= xb) continue;
+      uint8_t* dst = static_cast<uint8_t*>(a.dst);
+      for (int64_t y = ya; y < yb; ++y) {
+        uint8_t* d = dst + ((y - a.r0) * a.ld + (xa - a.c0)) * e;
+        KF_DCHECK(y - a.r0 < a.r1 - a.r0 && xb - a.c0 <= a.ld);
+        if (status != INF_OK) {
+          memset(d, 0, (size_t)((xb - xa) * e));
+          continue;
+        }
+        uint8_t* row = raw.data() + (y - gy0) * row_bytes;
+        KF_DCHECK((y - gy0 + 1) * row_bytes <= stride);
+        if (a.predictor == 2) {         // 16-bit horizontal differencing
+          uint16_t acc = 0;
+          for (int c = 0; c < T; ++c) {
+            uint16_t v;
+            memcpy(&v, row + 2 * c, 2);
+            acc = (uint16_t)(acc + v);
+            memcpy(row + 2 * c, &acc, 2);
+          }
+        } else if (a.predictor == 3) {  // float32: byte differences of the 4 byte planes, most significant first
+          uint8_t acc = 0;
+          for (int64_t i = 0; i < row_bytes; ++i) {
+            acc = (uint8_t)(acc + row[i]);
+            tmp[(size_t)i] = acc;
+          }
+          for (int c = 0; c < T; ++c)
+            for (int b = 0; b < 4; ++b) row[4 * c + b] = tmp[(size_t)((3 - b) * T + c)];
+        }
+        memcpy(d, row + (xa - gx0) * e, (size_t)((xb - xa) * e));
+      }
+    }
+  }
+  return 0;
+}
+
+// Literal + match tokens of the streams (nothing is written): what the
+// decoder lane of inf_tile_kernel processes, for a symbols-per-second figure.
+// -1 if a stream does not decode to raw_bytes.
+int64_t host_inflate_count_tokens(const uint8_t* comp, int64_t comp_bytes, const int64_t* offs, const int64_t* sizes,
+                                  int ntiles, int64_t raw_bytes) {
+  int64_t total = 0;
+  bool bad = false;
+#pragma omp parallel for schedule(dynamic, 1) reduction(+ : total) reduction(|| : bad)
+  for (int tile = 0; tile < ntiles; ++tile) {
+    if (offs[tile] < 0 || sizes[tile] < 0 || sizes[tile] > 0x7FFFFFFF || offs[tile] > comp_bytes ||
+        sizes[tile] > comp_bytes - offs[tile]) {
+      bad = true;
+      continue;
+    }
+    InfTables tab;
+    InfState st;
+    uint32_t q[INF_QUEUE];
+    inf_init(st, comp + offs[tile], (uint32_t)sizes[tile], (uint32_t)raw_bytes);
+    for (;;) {
+      total += inf_step(st, tab, q, INF_QUEUE);
+      if (st.status != INF_OK || st.phase == INF_P_DONE) break;
+    }
+    bad = bad || st.status != INF_OK;
+  }
+  return bad ? -1 : total;
 }
 
 int host_analysis(int np, const AnalysisArgs& a, int grid) { KF_HOST_NP_SWITCH(np, h_analysis, a, grid); }

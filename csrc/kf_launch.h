@@ -114,4 +114,45 @@ hipError_t dev_deflate_pack(const uint8_t* scratch, const uint32_t* sizes, const
                             int ntiles, hipStream_t s);
 int host_deflate_tiles(const DflArgs& a);
 
+// GeoTIFF tile decoder (kf_inflate.h / kf_inflate.hip): one status per tile
+constexpr int32_t INF_OK = 0;
+constexpr int32_t INF_TRUNCATED = 1;      // the stream (or its byte range in `comp`) ends too early
+constexpr int32_t INF_BAD_HEADER = 2;     // zlib header: CM, CINFO, FCHECK or FDICT
+constexpr int32_t INF_BAD_BLOCK = 3;      // BTYPE 11
+constexpr int32_t INF_BAD_STORED = 4;     // LEN / NLEN mismatch
+constexpr int32_t INF_BAD_CODE = 5;       // a dynamic block's code lengths describe no usable code
+constexpr int32_t INF_BAD_SYMBOL = 6;     // bits that are no code, or a reserved symbol
+constexpr int32_t INF_BAD_DISTANCE = 7;   // a match reaches before the tile's first byte
+constexpr int32_t INF_OVERRUN = 8;        // more output than the raw size
+constexpr int32_t INF_SHORT = 9;          // end of stream before the raw size
+constexpr int32_t INF_BAD_ADLER = 10;
+constexpr int32_t INF_NSTATUS = 11;
+
+// Tiles i < ntiles: the zlib stream comp[offs[i], offs[i] + sizes[i]) inflates
+// to raw_bytes bytes = a tile x tile block of elem_bytes samples at tile row /
+// column tile_rc[2 i], tile_rc[2 i + 1] of a raster; the TIFF predictor is
+// undone per tile row and the tile's intersection with the window rows
+// [r0, r1) x columns [c0, c1) is written to dst (row-major, ld elements per
+// row, element (r0, c0) first).  status[i] = INF_*; a tile that fails leaves
+// its part of the window zeroed.  The window must lie inside the raster, so a
+// padded edge tile's padding is never written.
+struct InfArgs {
+  const uint8_t* comp;
+  int64_t comp_bytes;
+  const int64_t* offs;
+  const int64_t* sizes;
+  const int32_t* tile_rc;
+  int32_t ntiles, tile, elem_bytes, predictor;   // tile: 256; 2 bytes: predictor 1 / 2; 4 bytes: 1 / 3
+  int64_t raw_bytes;
+  int64_t r0, r1, c0, c1;
+  void* dst;
+  int64_t ld;
+  int32_t* status;
+  uint8_t* scratch;   // device: ntiles * inf_scratch_stride(raw_bytes, tile, elem_bytes) bytes, 16-byte aligned
+};
+hipError_t dev_inflate_tiles(const InfArgs& a, hipStream_t s);
+int host_inflate_tiles(const InfArgs& a);
+int64_t host_inflate_count_tokens(const uint8_t* comp, int64_t comp_bytes, const int64_t* offs, const int64_t* sizes,
+                                  int ntiles, int64_t raw_bytes);
+
 }  // namespace kf

@@ -143,6 +143,34 @@ class HostRing {
     cv_.notify_one();
   }
 
+  // The compressed tiles of a tile table (kf_tiff.cpp: tile_table) back to
+  // back into slot s at slot_off, in the background, NOT inflated: the device
+  // decoder (kf_inflate.hip) takes them from there.  `band` is the table's.
+  void read_tiff_tiles_async(int s, const std::string& path, int band, const py::dict& table, size_t slot_off,
+                             int nthreads) {
+    (void)band;
+    const auto offsets = table["offsets"].cast<std::vector<uint64_t>>();
+    const auto counts = table["counts"].cast<std::vector<uint64_t>>();
+    if (offsets.size() != counts.size()) throw std::runtime_error("HostRing: one count per tile offset");
+    size_t total = 0;
+    for (uint64_t c : counts) total += (size_t)c;
+    check_range(s, slot_off, total);
+    pending_[s]++;
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      q_.push_back([=] {
+        try {
+          kf::tiff::read_ranges(path, offsets, counts, slots_[s] + slot_off, nthreads);
+        } catch (const std::exception& e) {
+          std::lock_guard<std::mutex> g2(err_mu_);
+          errors_[s] = std::string(e.what()) + ": " + path;
+        }
+        pending_[s]--;
+      });
+    }
+    cv_.notify_one();
+  }
+
   void wait_reads(int s) {
     while (pending_.at(s).load() > 0) std::this_thread::yield();
     std::lock_guard<std::mutex> g(err_mu_);
@@ -203,6 +231,16 @@ class HostRing {
     wait_submitted(s);
     if (hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), events_.at(s), 0) != hipSuccess)
       throw std::runtime_error("HostRing: hipStreamWaitEvent failed");
+  }
+
+  // Re-record slot s's event on `stream`: work queued there after the slot's
+  // copies (the device tile decoder reading them) then belongs to what
+  // stream_wait / host_wait of the slot wait for.
+  void record(int s, uintptr_t stream) {
+    if (!device_) return;
+    wait_submitted(s);
+    if (hipEventRecord(events_.at(s), reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
+      throw std::runtime_error("HostRing: hipEventRecord failed");
   }
 
   void host_wait(int s) {
@@ -441,10 +479,13 @@ void bind_stream(py::module_& m) {
       .def_property_readonly("pinned", &HostRing::pinned)
       .def("read_file_async", &HostRing::read_file_async)
       .def("read_tiff_async", &HostRing::read_tiff_async)
+      .def("read_tiff_tiles_async", &HostRing::read_tiff_tiles_async, py::arg("slot"), py::arg("path"),
+           py::arg("band"), py::arg("table"), py::arg("dst_off"), py::arg("nthreads") = 4)
       .def("wait_reads", &HostRing::wait_reads, py::call_guard<py::gil_scoped_release>())
       .def("h2d", &HostRing::h2d)
       .def("h2d_async", &HostRing::h2d_async)
       .def("stream_wait", &HostRing::stream_wait, py::call_guard<py::gil_scoped_release>())
+      .def("record", &HostRing::record)
       .def("host_wait", &HostRing::host_wait, py::call_guard<py::gil_scoped_release>())
       .def("write_slot", &HostRing::write_slot);
   py::class_<PhaseEvents>(m, "PhaseEvents")

@@ -377,6 +377,54 @@ void read_window(const std::string& path, int band, void* dst, uint64_t r0, uint
   });
 }
 
+TileTable tile_table(const std::string& path, int band, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1) {
+  File f(path);
+  const Info in = parse(f);
+  if (in.spp > 1 && in.planar != 2) throw std::runtime_error("pixel-interleaved multi-band TIFF not supported natively");
+  if (band < 0 || band >= in.spp) throw std::runtime_error("band out of range");
+  if (r1 > in.H || c1 > in.W || r0 >= r1 || c0 >= c1) throw std::runtime_error("window outside the raster");
+  TileTable t;
+  t.width = in.W;
+  t.height = in.H;
+  t.bits = in.bits;
+  t.sample_format = in.fmt;
+  t.compression = in.comp;
+  t.predictor = in.pred;
+  if (!in.tiled || in.tw != in.th) return t;      // strips, or tiles that are not square: no table
+  t.tile = in.tw;
+  const uint64_t across = (in.W + in.tw - 1) / in.tw, down = (in.H + in.th - 1) / in.th;
+  const uint64_t per_band = across * down;
+  if (in.off.size() < per_band * (uint64_t)(band + 1)) throw std::runtime_error("truncated chunk table");
+  for (uint64_t ty = r0 / in.th; ty <= (r1 - 1) / in.th; ++ty)
+    for (uint64_t tx = c0 / in.tw; tx <= (c1 - 1) / in.tw; ++tx) {
+      const uint64_t cid = per_band * (uint64_t)band + ty * across + tx;
+      t.offsets.push_back(in.off[cid]);
+      t.counts.push_back(in.cnt[cid]);
+      t.tile_rc.push_back((int32_t)ty);
+      t.tile_rc.push_back((int32_t)tx);
+    }
+  return t;
+}
+
+void read_ranges(const std::string& path, const std::vector<uint64_t>& offsets, const std::vector<uint64_t>& counts,
+                 void* dst, int nthreads) {
+  if (offsets.size() != counts.size()) throw std::runtime_error("read_ranges: one count per offset");
+  File f(path);
+  std::vector<uint64_t> at(offsets.size());
+  uint64_t pos = 0;
+  for (size_t i = 0; i < counts.size(); ++i) {
+    at[i] = pos;
+    pos += counts[i];
+  }
+  uint8_t* out = static_cast<uint8_t*>(dst);
+  // a few tiles per task: a tile is tens of KB, a task should be a worthwhile pread batch
+  const int64_t per = 16, ntask = ((int64_t)counts.size() + per - 1) / per;
+  parallel_for(ntask, nthreads, [&](int64_t k) {
+    for (size_t i = (size_t)(k * per); i < std::min<size_t>(counts.size(), (size_t)((k + 1) * per)); ++i)
+      if (counts[i]) f.read_at(out + at[i], counts[i], offsets[i]);
+  });
+}
+
 // ---------------------------------------------------------------- writer
 struct Tag {
   uint16_t tag, typ;
@@ -654,6 +702,23 @@ void bind_tiff(py::module_& m) {
     tiff::read_window(path, band, reinterpret_cast<void*>(dst), r0, r1, c0, c1, nthreads, elem_bytes);
   }, py::arg("path"), py::arg("band"), py::arg("dst"), py::arg("r0"), py::arg("r1"), py::arg("c0"), py::arg("c1"),
      py::arg("nthreads"), py::arg("elem_bytes") = 0);
+  m.def("tiff_tile_table", [](const std::string& path, int band, uint64_t r0, uint64_t r1, uint64_t c0, uint64_t c1) {
+    const tiff::TileTable t = tiff::tile_table(path, band, r0, r1, c0, c1);
+    py::dict d;
+    d["offsets"] = t.offsets;
+    d["counts"] = t.counts;
+    d["tile_rc"] = t.tile_rc;
+    d["width"] = t.width;
+    d["height"] = t.height;
+    d["tile"] = t.tile;
+    d["bits"] = t.bits;
+    d["sample_format"] = t.sample_format;
+    d["compression"] = t.compression;
+    d["predictor"] = t.predictor;
+    return d;
+  }, py::arg("path"), py::arg("band"), py::arg("r0"), py::arg("r1"), py::arg("c0"), py::arg("c1"),
+     "The tiles of one band that intersect a window: file offsets, byte counts, tile row / column, and the "
+     "layout (tile = 0: striped or non-square tiles)");
   m.def("tiff_fast_deflate", &tiff::fast_deflate_available,
         "True when tile DEFLATE uses libdeflate (else zlib)");
   m.def("tiff_deflate_backend", [](const std::string& b) {

@@ -121,7 +121,7 @@ def _build(args, comm):
             # a --mask GeoTIFF is the state grid every band is warped onto
             # (kafka_test_S2.py:155-162); without one the granule grid (ROI-cropped)
             obs = Sentinel2Observations(args.s2_folder, args.emulator_folder, args.mask or mask,
-                                        roi=None if args.mask else args.roi)
+                                        roi=None if args.mask else args.roi, decoder=args.in_decoder)
         elif args.sensor == "s2":
             obs = k.SyntheticS2Observations(mask, n_bands=10, n_train=args.n_train or 250, **syn)
         else:
@@ -212,6 +212,10 @@ def cmd_run(args):
             ing = getattr(kf.observations, "_ingest", None)
             if ing is not None:
                 rec["ingest"] = {"bytes_read": ing.bytes_read, "bytes_h2d": ing.bytes_h2d, "pinned": ing.pinned}
+        ing = getattr(kf.observations, "_ingest", None)
+        if ing is not None and getattr(ing, "decoder", "host") == "device":   # --in-decoder device: what it took
+            rec["ingest"] = {"bytes_read": ing.bytes_read, "bytes_h2d": ing.bytes_h2d, "pinned": ing.pinned,
+                             "decoder": "device", **ing.stats()}
         ck = getattr(kf, "checkpointer", None)
         if ck is not None and ck.stats["bytes"]:
             rec["checkpoint"] = {k_: [round(v, 3) for v in vals] for k_, vals in ck.stats.items() if k_ != "bytes"}
@@ -319,6 +323,10 @@ def main(argv=None):
     r.add_argument("--out-encoder", default="auto", choices=["auto", "device", "host"],
                    help="DEFLATE tiles encoded on the GPU (device: predictor 3 + fixed-Huffman run-length streams, "
                         "only compressed tiles cross PCIe) or by the host thread pool; auto: device on a GPU")
+    r.add_argument("--in-decoder", default="host", choices=["host", "device"],
+                   help="--s2-folder granules: DEFLATE tiles inflated by the host thread pool (host), or shipped "
+                        "compressed and inflated on the GPU (device: 256 x 256 tiles, 16-bit samples, predictor 1 / 2; "
+                        "other files take the host path, file by file)")
     r.add_argument("--out-huffman", default="fixed", choices=["fixed", "dynamic"],
                    help="block type of the device encoder: fixed Huffman codes, or one Huffman table per tile "
                         "built on the GPU wherever that makes the tile smaller (never larger than fixed)")

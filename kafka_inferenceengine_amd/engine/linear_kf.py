@@ -300,6 +300,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin):
             with self.timer.phase("checkpoint"):
                 ckpt.finish()
         self.resolve_pending()
+        if hasattr(self.observations, "check"):
+            self.observations.check()      # device tile decoder: a failed tile never goes unreported
         self.final_state = analysis
         if self.metrics.enabled:
             self.metrics_summary()

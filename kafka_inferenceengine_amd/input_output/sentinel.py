@@ -175,7 +175,11 @@ class Sentinel2Observations:
     1e-4, valid = DN > 0, sigma = rel_unc x reflectance, weight = 1 / sigma^2 —
     the reference's :163-179 without the N x N sparse weight matrix).
     ``prefetch(date)`` starts the next date's decode under the current
-    kernels.
+    kernels.  ``decoder="device"`` ships the files' compressed 256 x 256 tiles
+    instead and inflates them on the device (``RasterIngest``,
+    ``csrc/kf_inflate.hip``); files the device decoder cannot take (strips, no
+    compression, another tile size, sample type or predictor) go through the
+    host reader, file by file.
 
     Grids: with a georeferenced state mask (a GeoTIFF path, or an array plus
     ``mask_geotransform`` / ``mask_projection``) every band is warped onto the
@@ -190,9 +194,12 @@ class Sentinel2Observations:
     keeps the granule grid, cropped to ``roi``."""
 
     def __init__(self, parent_folder, emulator_folder, state_mask, chunk=None, roi=None, rel_unc=0.05,
-                 device_ingest: bool = True, mask_geotransform=None, mask_projection=None):
+                 device_ingest: bool = True, mask_geotransform=None, mask_projection=None, decoder: str = "host"):
         if not os.path.exists(parent_folder):
             raise IOError("S2 data folder doesn't exist")
+        if decoder not in ("host", "device"):
+            raise ValueError("decoder must be 'host' or 'device'")
+        self.decoder = decoder
         self.device_ingest = device_ingest
         self.parent = parent_folder
         self.emulator_folder = emulator_folder
@@ -313,11 +320,12 @@ class Sentinel2Observations:
             if plan is not None:
                 self._warp_plan = plan
                 elems = max((w[1] - w[0]) * (w[3] - w[2]) for w in plan["windows"].values())
-                self._ingest = RasterIngest(len(self.band_map), (1, elems), torch.int16, self._device)
+                self._ingest = RasterIngest(len(self.band_map), (1, elems), torch.int16, self._device,
+                                            decoder=self.decoder)
                 return
         ulx, uly = (self.roi[0], self.roi[1]) if self.roi is not None else (0, 0)
         self._window = (uly + part.r0, uly + part.r0 + H, ulx, ulx + W)
-        self._ingest = RasterIngest(len(self.band_map), (H, W), torch.int16, self._device)
+        self._ingest = RasterIngest(len(self.band_map), (H, W), torch.int16, self._device, decoder=self.decoder)
         self._identity = part.N == H * W
         self._idx = None if self._identity else torch.from_numpy(part.local_idx).to(self._device)
 
@@ -370,6 +378,17 @@ class Sentinel2Observations:
     def prefetch(self, timestep):
         if self._ingest is not None and timestep in self.date_data:
             self._ingest.prefetch(timestep, self._files(timestep))
+
+    def check(self):
+        """Raise if a tile of the device decoder (``decoder="device"``) failed;
+        waits for the statuses still in flight.  ``LinearKalman.run`` calls it
+        before it returns."""
+        if self._ingest is not None:
+            self._ingest.check()
+
+    def ingest_stats(self) -> dict:
+        """``RasterIngest.stats()`` of the bound ingest (empty before ``bind_engine``)."""
+        return self._ingest.stats() if self._ingest is not None else {}
 
     def __getattr__(self, name):
         # the engine probes hasattr(obs, "get_device_band_data"): only bound

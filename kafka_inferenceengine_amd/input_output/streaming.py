@@ -161,9 +161,15 @@ class RasterIngest:
     warp reader's per-grid windows, ``plane = (1, max elements)``) leave a
     tail the gather never reads."""
 
-    def __init__(self, n_planes: int, plane, dtype, device, n_slots: int = 2, io_threads: int | None = None):
+    DECODERS = ("host", "device")
+
+    def __init__(self, n_planes: int, plane, dtype, device, n_slots: int = 2, io_threads: int | None = None,
+                 decoder: str = "host"):
         import os
 
+        if decoder not in self.DECODERS:
+            raise ValueError("decoder must be 'host' or 'device'")
+        self.decoder = decoder
         self.device = torch.device(device)
         self.n_planes = int(n_planes)
         self.plane = tuple(int(v) for v in plane)
@@ -171,7 +177,9 @@ class RasterIngest:
         self.esize = torch.empty((), dtype=dtype).element_size()
         self.plane_bytes = self.plane[0] * self.plane[1] * self.esize
         self.slot_bytes = self.plane_bytes * self.n_planes
-        self.ring = _ext.require_ext().HostRing(n_slots, self.slot_bytes, 2)
+        self.n_slots = int(n_slots)
+        # decoder="device": the ring is sized by the first date's tile tables (_layout)
+        self.ring = _ext.require_ext().HostRing(n_slots, self.slot_bytes, 2) if decoder == "host" else None
         self.slot_key = [None] * n_slots
         self.bufs = [torch.empty((self.n_planes,) + self.plane, dtype=dtype, device=self.device) for _ in range(2)]
         self.buf_key = [None, None]
@@ -181,10 +189,37 @@ class RasterIngest:
         self._current = None
         self.bytes_h2d = 0
         self.bytes_read = 0
+        # device decoder state
+        self._tables = {}                   # (path, band, window) -> tile table or None (host path)
+        self._slot_plan = [None] * n_slots  # per slot: the date's per-file plan
+        self._region = None                 # per plane: (slot offset, bytes)
+        self._stage = None                  # per device buffer: the compressed tiles + tables on the device
+        self._status = [None, None]
+        self._pending = []                  # statuses in flight: (event, pinned host statuses, [(path, tile_rc, lo, hi)])
+        self._decoder = None
+        self._stats = {"files_device": 0, "files_host": 0, "tiles_device": 0, "bytes_compressed_h2d": 0,
+                       "bytes_raw": 0}
 
     @property
     def pinned(self) -> bool:
-        return bool(self.ring.pinned)
+        return bool(self.ring is not None and self.ring.pinned)
+
+    def stats(self) -> dict:
+        """Ingest counters: files that went through the device decoder / the host
+        reader, tiles decoded on the device, compressed bytes copied to the
+        device, raw bytes delivered to the planes.  ``bytes_h2d`` counts every
+        byte actually copied."""
+        return dict(self._stats)
+
+    def _check_window(self, win):
+        r0, r1, c0, c1 = win
+        if (r1 - r0, c1 - c0) != self.plane and (r1 - r0) * (c1 - c0) > self.plane[0] * self.plane[1]:
+            raise ValueError(f"window {(r0, r1, c0, c1)} does not fit a {self.plane} plane")
+
+    def _free_slot(self) -> int:
+        cur = self.slot_key.index(self._current) if self._current in self.slot_key else -1
+        return next((i for i in range(len(self.slot_key)) if i != cur and self.slot_key[i] is None),
+                    next(i for i in range(len(self.slot_key)) if i != cur))
 
     def prefetch(self, key, files) -> int:
         """Start decoding ``files`` into a free pinned slot (no wait)."""
@@ -192,13 +227,12 @@ class RasterIngest:
             return self.slot_key.index(key)
         if len(files) != self.n_planes:
             raise ValueError(f"{len(files)} files for {self.n_planes} planes")
-        cur = self.slot_key.index(self._current) if self._current in self.slot_key else -1
-        s = next((i for i in range(len(self.slot_key)) if i != cur and self.slot_key[i] is None),
-                 next(i for i in range(len(self.slot_key)) if i != cur))
+        if self.decoder == "device":
+            return self._prefetch_tiles(key, files)
+        s = self._free_slot()
         self.ring.host_wait(s)          # the slot's previous H2D has finished reading it
         for i, (path, band, (r0, r1, c0, c1)) in enumerate(files):
-            if (r1 - r0, c1 - c0) != self.plane and (r1 - r0) * (c1 - c0) > self.plane[0] * self.plane[1]:
-                raise ValueError(f"window {(r0, r1, c0, c1)} does not fit a {self.plane} plane")
+            self._check_window((r0, r1, c0, c1))
             self.ring.read_tiff_async(s, str(path), int(band), r0, r1, c0, c1, self.esize, i * self.plane_bytes,
                                       self.io_threads)
             self.bytes_read += self.plane_bytes
@@ -208,20 +242,207 @@ class RasterIngest:
     def acquire(self, key, files) -> torch.Tensor:
         """Device planes ``[n_planes, *plane]`` of ``key``; the current stream
         waits for their copy."""
+        if self.decoder == "device":
+            self._poll()
         s = self.prefetch(key, files)
         if key in self.buf_key:
             b = self.buf_key.index(key)
         else:
             b = 1 if (self._current is not None and self.buf_key[0] == self._current) else 0
             dst = self.bufs[b]
-            if self.cuda:
+            if self.decoder == "device":
+                self._ship_tiles(s, b)
+            elif self.cuda:
                 self.stream.wait_stream(torch.cuda.current_stream(self.device))
                 self.ring.h2d(s, dst.data_ptr(), self.slot_bytes, 0, int(self.stream.cuda_stream))
             else:
                 self.ring.h2d(s, dst.data_ptr(), self.slot_bytes, 0, 0)
             self.buf_key[b] = key
-            self.bytes_h2d += self.slot_bytes
+            if self.decoder == "host":
+                self.bytes_h2d += self.slot_bytes
         if self.cuda:
             self.ring.stream_wait(s, current_raw_stream(self.device))
         self._current = key
         return self.bufs[b]
+
+    # ------------------------------------------------------ decoder="device"
+    # Per file: the tile table (cached) decides device or host.  A device file's
+    # region of the slot holds [offsets int64 | sizes int64 | tile_rc int32 x 2 |
+    # pad to 16 | the compressed tiles back to back]; one copy ships it, and
+    # ``TileDecoder`` inflates it on the ingest stream straight into the plane
+    # the gather reads.  A host file's region holds its decoded window, as in the
+    # host mode.  S1 / BHR readers, an automatic choice and pixel-interleaved
+    # multi-band files are not wired.
+    TILE_SLACK = 64                          # a tile's stream may exceed its raw size by this much
+
+    def _table(self, path, band, win):
+        k = (str(path), int(band), tuple(int(v) for v in win))
+        if k in self._tables:
+            return self._tables[k]
+        import numpy as np
+
+        from ..ops.kernels import TileDecoder
+
+        E = _ext.require_ext()
+        t = E.tiff_tile_table(k[0], k[1], *k[2])
+        tile, e = int(t["tile"]), int(t["bits"]) // 8
+        n = len(t["offsets"])
+        fmt, pred = int(t["sample_format"]), int(t["predictor"])
+        ok = (n > 0 and int(t["compression"]) in (8, 32946) and e == self.esize and TileDecoder.supports(tile, e, pred)
+              and (fmt in (1, 2) if e == 2 else fmt == 3 or pred == 1)
+              and max(t["counts"]) <= tile * tile * e + self.TILE_SLACK)
+        tab = None
+        if ok:
+            counts = np.asarray(t["counts"], dtype=np.int64)
+            offs = np.cumsum(counts) - counts
+            head = np.concatenate([offs.view(np.uint8), counts.view(np.uint8),
+                                   np.asarray(t["tile_rc"], dtype=np.int32).view(np.uint8)])
+            pad = (-head.size) % 16
+            tab = {"table": t, "n": n, "tile": tile, "pred": pred, "comp_bytes": int(counts.sum()),
+                   "head": np.concatenate([head, np.zeros(pad, np.uint8)]), "tile_rc": list(t["tile_rc"])}
+        if len(self._tables) > 256:
+            self._tables.clear()
+        self._tables[k] = tab
+        return tab
+
+    def _layout(self, tabs):
+        """Ring, staging and status buffers from the first date's tables: a
+        plane's region holds its decoded window (host file) or the largest
+        table + streams its tiles can have (device file)."""
+        sizes, off = [], 0
+        for tab in tabs:
+            need = self.plane_bytes
+            if tab is not None:
+                need = max(need, tab["head"].size + tab["n"] * (tab["tile"] ** 2 * self.esize + self.TILE_SLACK))
+            need = -(-need // 4096) * 4096
+            sizes.append((off, need))
+            off += need
+        self._region = sizes
+        self.slot_bytes = off
+        self.ring = _ext.require_ext().HostRing(self.n_slots, off, 2)
+        self._stage = [torch.empty(off, dtype=torch.uint8, device=self.device) for _ in range(2)]
+
+    def _prefetch_tiles(self, key, files) -> int:
+        self._poll()
+        tabs = []
+        for path, band, win in files:
+            self._check_window(win)
+            tabs.append(self._table(path, band, win))
+        if self.ring is None:
+            self._layout(tabs)
+        s = self._free_slot()
+        self.ring.host_wait(s)          # the slot's previous copies and decodes have finished reading it
+        plan = []
+        for i, ((path, band, (r0, r1, c0, c1)), tab) in enumerate(zip(files, tabs)):
+            off, room = self._region[i]
+            nwin = (r1 - r0) * (c1 - c0) * self.esize
+            if tab is not None and tab["head"].size + tab["comp_bytes"] > room:
+                tab = None              # more tiles than the first date's layout allows for: host path
+            if tab is None:
+                self.ring.read_tiff_async(s, str(path), int(band), r0, r1, c0, c1, self.esize, off, self.io_threads)
+                self.bytes_read += nwin
+                self._stats["files_host"] += 1
+            else:
+                self.ring.write_slot(s, tab["head"], off)
+                self.ring.read_tiff_tiles_async(s, str(path), int(band), tab["table"], off + tab["head"].size,
+                                                self.io_threads)
+                self.bytes_read += tab["comp_bytes"]
+                self._stats["files_device"] += 1
+                self._stats["tiles_device"] += tab["n"]
+            self._stats["bytes_raw"] += nwin
+            plan.append((str(path), (r0, r1, c0, c1), tab, off, nwin))
+        self._slot_plan[s] = plan
+        self.slot_key[s] = key
+        return s
+
+    def _ship_tiles(self, s: int, b: int):
+        from ..ops.kernels import TileDecoder
+
+        if self._decoder is None:
+            self._decoder = TileDecoder()
+        plan = self._slot_plan[s]
+        raw = int(self.stream.cuda_stream) if self.cuda else 0
+        if self.cuda:
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        stage, dst = self._stage[b], self.bufs[b]
+        for i, (path, win, tab, off, nwin) in enumerate(plan):
+            if tab is None:
+                self.ring.h2d(s, dst[i].data_ptr(), nwin, off, raw)
+                self.bytes_h2d += nwin
+            else:
+                nb = tab["head"].size + tab["comp_bytes"]
+                self.ring.h2d(s, stage.data_ptr() + off, nb, off, raw)
+                self.bytes_h2d += nb
+                self._stats["bytes_compressed_h2d"] += tab["comp_bytes"]
+        ntile = sum(p[2]["n"] for p in plan if p[2] is not None)
+        if not ntile:
+            return
+        if self._status[b] is None or self._status[b].numel() < ntile:
+            self._status[b] = torch.empty(ntile, dtype=torch.int32, device=self.device)
+        status, meta, lo = self._status[b], [], 0
+
+        def decode_all():
+            nonlocal lo
+            for i, (path, (r0, r1, c0, c1), tab, off, nwin) in enumerate(plan):
+                if tab is None:
+                    continue
+                n, h = tab["n"], off
+                offs = stage[h:h + 8 * n].view(torch.int64)
+                sizes = stage[h + 8 * n:h + 16 * n].view(torch.int64)
+                rc = stage[h + 16 * n:h + 24 * n].view(torch.int32).view(n, 2)
+                data = stage[off + tab["head"].size:off + tab["head"].size + tab["comp_bytes"]]
+                out = dst[i].reshape(-1)[:(r1 - r0) * (c1 - c0)].view(r1 - r0, c1 - c0)
+                self._decoder.decode(data, offs, sizes, rc, tile=tab["tile"], elem_bytes=self.esize,
+                                     predictor=tab["pred"], window=(r0, r1, c0, c1), out=out,
+                                     status=status[lo:lo + n])
+                meta.append((path, tab["tile_rc"], lo, lo + n))
+                lo += n
+
+        if self.cuda:
+            with torch.cuda.stream(self.stream):
+                decode_all()
+                host = torch.empty(ntile, dtype=torch.int32, pin_memory=True)
+                host.copy_(status[:ntile], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+            self.ring.record(s, raw)     # the slot's event now covers the decode too
+            self._pending.append((ev, host, meta))
+        else:
+            decode_all()
+            self._pending.append((None, status[:ntile].clone(), meta))
+            self._poll()
+
+    @staticmethod
+    def _report(host, meta):
+        from ..ops.kernels import TileDecoder
+
+        bad = torch.nonzero(host).reshape(-1).tolist()
+        if not bad:
+            return
+        msgs = []
+        for j in bad[:8]:
+            path, rc, lo, hi = next(m for m in meta if m[2] <= j < m[3])
+            k = j - lo
+            msgs.append(f"{path}: tile (row {rc[2 * k]}, column {rc[2 * k + 1]}): "
+                        f"{TileDecoder.status_name(int(host[j]))}")
+        more = f" (+{len(bad) - 8} more)" if len(bad) > 8 else ""
+        raise RuntimeError("device tile decoder: " + "; ".join(msgs) + more)
+
+    def _poll(self, block: bool = False):
+        """Statuses that have arrived (``block``: all of them): a failed tile raises."""
+        keep, done = [], []
+        for ev, host, meta in self._pending:
+            if ev is not None and block:
+                ev.synchronize()
+            if ev is None or block or ev.query():
+                done.append((host, meta))
+            else:
+                keep.append((ev, host, meta))
+        self._pending = keep
+        for host, meta in done:
+            self._report(host, meta)
+
+    def check(self):
+        """Wait for every tile status still in flight; ``RuntimeError`` names the
+        file, tile and status of the tiles that failed to decode."""
+        self._poll(block=True)

@@ -1362,6 +1362,74 @@ class TileEncoder:
         return packed, s64, offs
 
 
+class TileDecoder:
+    """GeoTIFF tiles decoded on the device (csrc/kf_inflate.h), the counterpart
+    of ``TileEncoder``: every tile's zlib stream is inflated (stored, fixed and
+    dynamic Huffman blocks), the TIFF predictor is undone and the tile's part
+    of ``window`` is written into ``out``.  ``decode`` is queued on the current
+    stream for CUDA tensors; on the CPU the host runner of the same decoder
+    gives the same bytes and statuses.  Supported: 256-pixel tiles of 16-bit
+    samples (predictor 1 or 2) or float32 samples (predictor 1 or 3).
+
+    The raw-tile scratch is kept for the next call of the same size."""
+
+    TILE = 256
+
+    def __init__(self):
+        self._scratch = None
+
+    @staticmethod
+    def status_name(code: int) -> str:
+        names = ext().INF_STATUS_NAMES
+        return names[code] if 0 <= int(code) < len(names) else f"status {int(code)}"
+
+    @classmethod
+    def supports(cls, tile, elem_bytes, predictor) -> bool:
+        return int(tile) == cls.TILE and (int(elem_bytes), int(predictor)) in ((2, 1), (2, 2), (4, 1), (4, 3))
+
+    def decode(self, data, offsets, sizes, tile_rc, *, tile=256, elem_bytes, predictor=1, window, out, status=None,
+               raw_bytes=None):
+        """``data``: uint8 tensor holding the streams; ``offsets`` / ``sizes``:
+        int64 [n] byte ranges in it; ``tile_rc``: int32 [n, 2] tile row and
+        column in the raster; ``window`` = (r0, r1, c0, c1) in raster pixels,
+        inside the raster; ``out``: [r1 - r0, >= c1 - c0] tensor of
+        ``elem_bytes`` elements with unit column stride.  Returns (out, status):
+        status int32 [n], 0 = ok (``status_name``); a failed tile's part of the
+        window is zero.  ``raw_bytes``: the size every stream must inflate to
+        (default: one tile)."""
+        if not self.supports(tile, elem_bytes, predictor):
+            raise ValueError("TileDecoder: 256-pixel tiles of 16-bit (predictor 1, 2) or float32 (predictor 1, 3) samples")
+        n = int(offsets.numel())
+        dev = data.device
+        if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+            raise ValueError("data: contiguous 1-d uint8")
+        for t, name, dt, shape in ((offsets, "offsets", torch.int64, (n,)), (sizes, "sizes", torch.int64, (n,)),
+                                   (tile_rc, "tile_rc", torch.int32, (n, 2))):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{name}: contiguous {dt} {shape} on {dev}")
+        r0, r1, c0, c1 = (int(v) for v in window)
+        if not (0 <= r0 < r1 and 0 <= c0 < c1) or n <= 0:
+            raise ValueError("window: 0 <= r0 < r1, 0 <= c0 < c1, and at least one tile")
+        if out.dim() != 2 or out.element_size() != elem_bytes or out.stride(1) != 1 or out.device != dev or \
+                out.shape[0] < r1 - r0 or out.shape[1] < c1 - c0 or out.stride(0) < c1 - c0:
+            raise ValueError(f"out: [{r1 - r0}, >= {c1 - c0}] of {elem_bytes}-byte elements on {dev}")
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+        elif status.dtype != torch.int32 or status.numel() < n or status.device != dev or not status.is_contiguous():
+            raise ValueError("status: contiguous int32 [n]")
+        raw = int(tile) * int(tile) * int(elem_bytes) if raw_bytes is None else int(raw_bytes)
+        scratch = None
+        if _dev(data):
+            need = n * int(ext().inflate_scratch_stride(raw, int(tile), int(elem_bytes)))
+            if self._scratch is None or self._scratch.numel() < need or self._scratch.device != dev:
+                self._scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+            scratch = self._scratch
+        ext().inflate_tiles(_ptr(data), int(data.numel()), _ptr(offsets), _ptr(sizes), _ptr(tile_rc), n, int(tile),
+                            int(elem_bytes), int(predictor), raw, r0, r1, c0, c1, _ptr(out), int(out.stride(0)),
+                            _ptr(status), _dev(data), _stream(data), _ptr(scratch))
+        return out, status[:n]
+
+
 def unpack(n_params, x, a, mean=None, unc=None, idx=None, N=None):
     """Scatter mean and 1/sqrt(diag(P^-1)) onto raster planes [n_p, H*W]."""
     check_np(n_params)
