@@ -148,7 +148,66 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
       .def_readwrite("line_n", &AnalysisArgs::line_n)
       .def_readwrite("line_j", &AnalysisArgs::line_j)
       .def_readwrite("a_struct", &AnalysisArgs::a_struct)
+      // the straight-line JRC-TIP kernel's constant block (kf_core.h TipConst), field by field
+      .def_property_readonly("tc_on", [](const AnalysisArgs& s) { return s.tc.on != 0; })
+      .def_property_readonly("tc", [](const AnalysisArgs& s) {
+        const TipConst& t = s.tc;
+        py::dict d;
+        d["on"] = t.on;
+        d["j"] = t.j;
+        d["m"] = t.m;
+        d["q"] = t.q;
+        d["xa_row"] = (uintptr_t)t.xa_row;
+        d["pa_row"] = (uintptr_t)t.pa_row;
+        d["dn"] = std::vector<uintptr_t>{(uintptr_t)t.dn[0], (uintptr_t)t.dn[1]};
+        d["line_tab"] = (uintptr_t)t.line_tab;
+        d["line_t0"] = t.line_t0;
+        d["line_inv_h"] = t.line_inv_h;
+        d["line_n"] = t.line_n;
+        d["dom_check"] = t.dom_check;
+        d["dom_lo"] = get_arr(t.dom_lo);
+        d["dom_hi"] = get_arr(t.dom_hi);
+        d["mean"] = get_arr(t.mean);
+        d["cinv"] = get_arr(t.cinv);
+        py::list bands;
+        for (int b = 0; b < 2; ++b) {
+          const TipBandConst& c = t.band[b];
+          py::dict e;
+          e["center"] = get_arr(c.center);
+          e["coef"] = get_arr(c.coef);
+          e["offset"] = c.offset;
+          e["gpm_scale"] = c.gpm_scale;
+          e["scale"] = c.scale;
+          e["rel_unc"] = c.rel_unc;
+          e["unc_floor"] = c.unc_floor;
+          e["nchunk"] = c.nchunk;
+          bands.append(e);
+        }
+        d["band"] = bands;
+        d["rows"] = t.rows;
+        d["out"] = t.out;
+        d["ld"] = t.ld;
+        d["out_plane"] = t.out_plane;
+        d["x_out"] = (uintptr_t)t.x_out;
+        d["a_out"] = (uintptr_t)t.a_out;
+        d["out_mean"] = (uintptr_t)t.out_mean;
+        d["out_unc"] = (uintptr_t)t.out_unc;
+        d["out_idx"] = (uintptr_t)t.out_idx;
+        d["status"] = (uintptr_t)t.status;
+        d["gn_fused"] = t.gn_fused;
+        d["gpm_frags"] = t.gpm_frags;
+        return d;
+      })
       .GEO_FIELDS(AnalysisArgs, reg_geo);
+
+  // host side of the straight-line JRC-TIP kernel: the launch-shape predicate and the fill of
+  // AnalysisArgs.tc from the host copies of the launch's PropArgs and BandDescs
+  m.def("tip_sl_shape", [](int np, const AnalysisArgs& a, const PropArgs* pa, const std::vector<BandDesc>& bd) {
+    return tip_sl_shape(np, a, pa, bd.data(), (int)bd.size());
+  });
+  m.def("tip_const_fill", [](int np, AnalysisArgs& a, const PropArgs* pa, const std::vector<BandDesc>& bd) {
+    return tip_const_fill(np, a, pa, bd.data(), (int)bd.size());
+  });
 
   py::class_<GainArgs>(m, "GainArgs")
       .def(py::init([]() { GainArgs a; memset(&a, 0, sizeof(a)); return a; }))

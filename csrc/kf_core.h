@@ -309,7 +309,50 @@ enum AnalysisVariant : int32_t {
   AV_BLOCK_ORDER = 16,       // exponent MFMAs block by block (gpm_il_default's other order)
   AV_GENERIC_SPEC = 18,      // fused forecast through the generic launch instead of SPEC_PROP
   AV_DENSE_SOLVE = 20,       // the dense solve where a_struct would select the structure-aware kernels / host path
-  AV_MIXLO_SPLIT = 22        // lo half of m by v_fma_mixlo/mixhi_f16 (gpm_exp_split MIXLO; kf_device.h mixlo_split_analysis)
+  AV_MIXLO_SPLIT = 22,       // lo half of m by v_fma_mixlo/mixhi_f16 (gpm_exp_split MIXLO; kf_device.h mixlo_split_analysis)
+  AV_LOOPED_TIP = 24         // the SPEC_PROP_TIP kernels where the launch has the straight-line kernel's shape (TipConst)
+};
+
+// Launch constants of the straight-line JRC-TIP kernel (kf_gp_mfma.h
+// pixel_analysis_tip_sl): everything launch-uniform that the per-group code
+// outside the GP loop reads, gathered by the host (tip_const_fill) from the
+// PropArgs, the two BandDescs and the output arguments into one contiguous
+// kernarg block, so the kernel fetches it with a few wide scalar loads instead
+// of walking three descriptors field by field behind mask and null tests.
+struct TipBandConst {
+  float center[4], coef[4];
+  float offset, gpm_scale;         // GP epilogue
+  float scale, rel_unc, unc_floor; // DN16 decode
+  int32_t nchunk;
+  int32_t pad[2];
+};
+constexpr int TIP_ROWS_NONE = 0, TIP_ROWS_DIAG = 1, TIP_ROWS_ALL = 2;   // TipConst.rows: stored precision rows
+constexpr int TIP_OUT_NONE = 0, TIP_OUT_UNC = 1, TIP_OUT_MEAN = 2;      // TipConst.out: fused output rasters
+struct TipConst {
+  int32_t on;                  // 1: filled, the launch has the kernel's shape (tip_sl_shape)
+  int32_t j;                   // the single propagated parameter
+  float m, q;                  // its trajectory model and uncertainty
+  const float* xa_row;         // x_a + j ld
+  const float* pa_row;         // p_a + tri(j, j) ld
+  const uint16_t* dn[2];       // the bands' digital numbers
+  const float* line_tab;       // line-table header (AnalysisArgs.line_*; null: none)
+  float line_t0, line_inv_h;
+  int32_t line_n;
+  int32_t dom_check;           // domain box (AnalysisArgs.dom_*)
+  float dom_lo[8], dom_hi[8];
+  float mean[8];               // reset mean
+  float cinv[28];              // reset precision, packed (only the StructTip entries are read)
+  TipBandConst band[2];
+  // outputs
+  int32_t rows, out;           // TIP_ROWS_* / TIP_OUT_*: the kernel instantiation
+  int64_t ld, out_plane;
+  float* x_out;
+  float* a_out;
+  float* out_mean;
+  float* out_unc;
+  const int64_t* out_idx;
+  uint8_t* status;
+  int32_t gn_fused, gpm_frags;
 };
 
 struct AnalysisArgs {
@@ -396,7 +439,97 @@ struct AnalysisArgs {
   // the structure-aware solve (SPEC_*_TIP kernels, the host runner's StructTip
   // path); 0: dense
   int32_t a_struct;
+  // the straight-line JRC-TIP kernel's constants (tc.on: filled by tip_const_fill)
+  TipConst tc;
 };
+
+// The launch shape of the straight-line JRC-TIP kernel, from the launch
+// arguments and the host copies of what a.prop and a.bands point to (nb
+// descriptors): the matrix-core LDS-table launch of the JRC-TIP layout with
+// two DN16 bands, the fused forecast with exactly one propagated parameter
+// and no per-pixel Q, linearised at the forecast, the structured prior
+// (A_STRUCT_TIP | A_STRUCT_TIP_PRIOR), the plain solve (no regulariser, no
+// band chunks, no b_out / x0_out / h0_out) and the stored rows none, the
+// propagated parameter's diagonal entry, or all.  Lane offsets are 32-bit
+// byte offsets (kf_core.h pxp), so every row must stay below 4 GiB.
+KF_HD int prop_single(uint32_t mask);
+inline bool tip_sl_shape(int np, const AnalysisArgs& a, const PropArgs* pa, const BandDesc* bd, int nb) {
+  if (np != 7 || !pa || !bd || nb != 2 || a.n_bands != 2) return false;
+  if (a.variant != AV_DEFAULT) return false;
+  if (a.fast_d != 4 || a.fast_obs != OBS_DN16 || a.band_layout != BAND_LAYOUT_TIP) return false;
+  if (a.gpm_frags <= 0 || a.gpm_global) return false;
+  if (!a.prop || a.x_prev || a.x_f || a.pf_inv || a.a_in || a.b_in) return false;
+  if ((a.a_struct & (A_STRUCT_TIP | A_STRUCT_TIP_PRIOR)) != (A_STRUCT_TIP | A_STRUCT_TIP_PRIOR)) return false;
+  if (!a.solve || !a.x_out || a.b_out || a.x0_out || a.reg_v) return false;
+  if (a.gn_fused != 1 && a.gn_fused != 2) return false;
+  if (a.out_mean && !a.out_unc) return false;
+  const int j = prop_single(pa->prop_mask);
+  if (pa->mode != PROP_PRIOR_PARTIAL || pa->blend || j < 0 || j >= 7 || pa->q_pix || !pa->x_a || !pa->p_a) return false;
+  if (pa->ld != a.ld) return false;
+  if (a.line_tab && a.line_j != j) return false;
+  for (int b = 0; b < 2; ++b) {
+    const BandDesc& d = bd[b];
+    if (d.op != OP_GP || d.obs != OBS_DN16 || d.d != 4 || !d.dn || d.h0_out || d.gpm_nchunk < 1) return false;
+    if (d.map_kind != (b == 0 ? GPM_MAP_TIP_VIS : GPM_MAP_TIP_NIR)) return false;
+  }
+  if (a.a_out && a.a_rows != 0 && a.a_rows != (1ull << tri(7, j, j))) return false;
+  const int64_t lim = (int64_t)1 << 30;   // elements of a row: 4-byte values at 32-bit byte offsets
+  if (a.N < 1 || a.N > a.ld || a.ld >= lim || (a.out_unc && (a.out_plane < 1 || a.out_plane >= lim))) return false;
+  if (a.out_idx && a.N >= lim / 2) return false;   // 8-byte raster positions
+  return true;
+}
+
+// Fills a.tc for a launch of that shape (tc.on = 1), else clears it; returns tc.on.
+inline bool tip_const_fill(int np, AnalysisArgs& a, const PropArgs* pa, const BandDesc* bd, int nb) {
+  TipConst& t = a.tc;
+  t = TipConst{};
+  if (!tip_sl_shape(np, a, pa, bd, nb)) return false;
+  t.on = 1;
+  t.j = prop_single(pa->prop_mask);
+  t.m = pa->m[t.j];
+  t.q = pa->q[t.j];
+  t.xa_row = pa->x_a + (int64_t)t.j * pa->ld;
+  t.pa_row = pa->p_a + (int64_t)tri(7, t.j, t.j) * pa->ld;
+  t.line_tab = a.line_tab;
+  t.line_t0 = a.line_t0;
+  t.line_inv_h = a.line_inv_h;
+  t.line_n = a.line_n;
+  t.dom_check = a.dom_check;
+  for (int i = 0; i < 7; ++i) {
+    t.dom_lo[i] = a.dom_lo[i];
+    t.dom_hi[i] = a.dom_hi[i];
+    t.mean[i] = pa->reset_mean[i];
+  }
+  for (int i = 0; i < 28; ++i) t.cinv[i] = pa->reset_cinv[i];
+  for (int b = 0; b < 2; ++b) {
+    const BandDesc& d = bd[b];
+    TipBandConst& c = t.band[b];
+    for (int i = 0; i < 4; ++i) {
+      c.center[i] = d.center[i];
+      c.coef[i] = d.coef[i];
+    }
+    c.offset = d.offset;
+    c.gpm_scale = d.gpm_scale;
+    c.scale = d.scale;
+    c.rel_unc = d.rel_unc;
+    c.unc_floor = d.unc_floor;
+    c.nchunk = d.gpm_nchunk;
+    t.dn[b] = d.dn;
+  }
+  t.rows = !a.a_out ? TIP_ROWS_NONE : (a.a_rows ? TIP_ROWS_DIAG : TIP_ROWS_ALL);
+  t.out = !a.out_unc ? TIP_OUT_NONE : (a.out_mean ? TIP_OUT_MEAN : TIP_OUT_UNC);
+  t.ld = a.ld;
+  t.out_plane = a.out_plane;
+  t.x_out = a.x_out;
+  t.a_out = a.a_out;
+  t.out_mean = a.out_mean;
+  t.out_unc = a.out_unc;
+  t.out_idx = a.out_idx;
+  t.status = a.status;
+  t.gn_fused = a.gn_fused;
+  t.gpm_frags = a.gpm_frags;
+  return true;
+}
 
 // slots visited by a launch: n_visit (0: N), or the device count (<= that bound)
 KF_HD int64_t visit_bounded(int64_t n_visit, int64_t N, const int32_t* n_dev) {

@@ -195,6 +195,83 @@ __global__ __launch_bounds__(BS, MINW) void analysis_mfma_mixlo_kernel(AnalysisA
   analysis_mfma_body<NP, D, FOBS, BS, LAYOUT, IL, SPEC, true>(a);
 }
 
+// The straight-line JRC-TIP kernel (kf_gp_mfma.h pixel_analysis_tip_sl): the
+// launch shape of kf_core.h tip_sl_shape, its constants in a.tc.  ROWS / OUT:
+// TIP_ROWS_* / TIP_OUT_* (stored precision rows, fused output rasters).  Each
+// group's own loads (tip_group_load) are issued right after its order index.
+template <bool IL, int ROWS, int OUT>
+__global__ __launch_bounds__(BLOCK, 3) void analysis_tip_sl_kernel(AnalysisArgs a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  extern __shared__ kf_h8 gpm_lds[];
+  KF_PHASE_KERNEL_BEGIN
+  {
+    int off = 0;
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi) {
+      const KF_CONST_AS BandDesc* bd = cptr(a.bands) + bi;
+      const int n = bd->gpm_nchunk * gpm_frags_per_chunk(4);
+      const kf_h8* src = (const kf_h8*)bd->gpm;
+      for (int i = threadIdx.x; i < n; i += BLOCK) gpm_lds[off + i] = src[i];
+      off += n;
+    }
+    if (threadIdx.x == 0) gpm_lds[a.gpm_frags - 1] = kf_h8{};   // shared zero fragment
+  }
+  __syncthreads();
+  KF_PHASE(KF_PH_PROLOGUE)
+  double acc = 0.0, acc1 = 0.0;
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * BLOCK;
+  const int64_t nv = visit_count(a);
+  for (int64_t base = (int64_t)blockIdx.x * BLOCK + (threadIdx.x - lane); base < nv; base += stride) {
+    const int64_t q = base + lane;
+    const bool act = q < nv;
+    const int64_t p = visit_px(a.order, act ? q : nv - 1);
+    const KF_CONST_AS AnalysisArgs* ka = opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr());
+    const TipGroup g = tip_group_load<OUT>(&ka->tc, p);
+    float dn1;
+    const float dn = pixel_analysis_tip_sl<IL, ROWS, OUT>(p, act, g, gpm_lds, dn1 KF_PHASE_ARG);
+    {
+      float* dno = opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->dn_out;
+      if (act && dno) KF_PX(dno, 0, p) = dn;
+    }
+    acc += act ? (double)dn : 0.0;
+    acc1 += act ? (double)dn1 : 0.0;
+  }
+  analysis_partials<BLOCK>(a, acc, acc1);
+  KF_PHASE_KERNEL_END
+#endif
+}
+
+template <typename K>
+static void gpm_lds_attr(K kernel, size_t bytes);
+
+template <int ROWS, int OUT>
+static void launch_tip_sl(size_t lds, const AnalysisArgs& a, int grid, hipStream_t s, int* n_part) {
+  constexpr bool IL = true;   // gpm_il_default<7, BAND_LAYOUT_TIP>()
+  gpm_lds_attr(analysis_tip_sl_kernel<IL, ROWS, OUT>, lds);
+  *n_part = grid;
+  hipLaunchKernelGGL((analysis_tip_sl_kernel<IL, ROWS, OUT>), dim3(grid), dim3(BLOCK), lds, s, a);
+}
+
+static bool l_analysis_tip_sl(size_t lds, const AnalysisArgs& a, int grid, hipStream_t s, int* n_part) {
+#define KF_TIP_SL_GO(R_, O_)                               \
+  if (a.tc.rows == R_ && a.tc.out == O_) {                 \
+    launch_tip_sl<R_, O_>(lds, a, grid, s, n_part);        \
+    return true;                                           \
+  }
+  KF_TIP_SL_GO(TIP_ROWS_NONE, TIP_OUT_NONE)
+  KF_TIP_SL_GO(TIP_ROWS_NONE, TIP_OUT_UNC)
+  KF_TIP_SL_GO(TIP_ROWS_NONE, TIP_OUT_MEAN)
+  KF_TIP_SL_GO(TIP_ROWS_DIAG, TIP_OUT_NONE)
+  KF_TIP_SL_GO(TIP_ROWS_DIAG, TIP_OUT_UNC)
+  KF_TIP_SL_GO(TIP_ROWS_DIAG, TIP_OUT_MEAN)
+  KF_TIP_SL_GO(TIP_ROWS_ALL, TIP_OUT_NONE)
+  KF_TIP_SL_GO(TIP_ROWS_ALL, TIP_OUT_UNC)
+  KF_TIP_SL_GO(TIP_ROWS_ALL, TIP_OUT_MEAN)
+#undef KF_TIP_SL_GO
+  return false;
+}
+
 // K1 on the matrix cores with every band's table read from global memory
 // (gp_mfma_sums_g): many-band GP states (PROSAIL: ten bands, 358-716 KiB of
 // tables) whose tables exceed the LDS.  No LDS, so the waves per SIMD follow
@@ -709,6 +786,9 @@ static bool l_analysis_fast(const AnalysisArgs& a, int grid, hipStream_t s, int*
         tip = a.band_layout == BAND_LAYOUT_TIP && a.n_bands == 2 && a.variant != AV_RUNTIME_LAYOUT;
       if (a.fast_obs == OBS_DN16) {
         if constexpr (NP == 7 && FD == 4) {
+          // the launch shape of the straight-line kernel (a.tc filled by the host: tip_const_fill);
+          // AV_LOOPED_TIP: the SPEC_PROP_TIP kernels below for the same launch (its oracle)
+          if (tip && a.tc.on && a.variant == AV_DEFAULT && l_analysis_tip_sl(lds, a, grid, s, n_part)) return true;
           if (tip) {
             KF_MFMA_GO_SPEC(OBS_DN16, BLOCK, 3, BAND_LAYOUT_TIP)
             return true;

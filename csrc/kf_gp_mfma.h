@@ -922,6 +922,310 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
   }
 }
 
+// ---------------------------------------------------------------------------
+// Straight-line JRC-TIP kernel: pixel_analysis_mfma<7, 4, OBS_DN16, ..., BAND_LAYOUT_TIP, IL, SPEC_PROP_TIP>
+// for the one launch shape the steady state of a JRC-TIP run repeats
+// (kf_core.h tip_sl_shape), with every launch-uniform constant read from the
+// TipConst block of the kernel arguments.  The code outside the GP loop has no
+// per-parameter mask loops and no null tests of launch-uniform pointers; the
+// stored-rows mode (ROWS) and the fused output rasters (OUT) are template
+// parameters; the group's own loads are issued by the caller before anything
+// waits on them (TipGroup) and every per-pixel access is SGPR base + 32-bit
+// lane offset (KF_PXS).  The arithmetic is that kernel's, operation for
+// operation and in the same order, so the results are bit-identical
+// (tests/test_gpu_tip_straight.py; AV_LOOPED_TIP selects that kernel).
+struct TipGroup {
+  float xa, pa;        // x_a[j], P_a[j, j] of the propagated parameter
+  uint16_t dn[2];      // the two bands' digital numbers
+  uint32_t r;          // raster position (the pixel itself without out_idx)
+};
+
+template <int OUT>
+__device__ __forceinline__ TipGroup tip_group_load(const KF_CONST_AS TipConst* tc, int64_t p) {
+  TipGroup g;
+  g.xa = KF_PXS(tc->xa_row, 0, p);
+  g.pa = KF_PXS(tc->pa_row, 0, p);
+  g.dn[0] = KF_PXS(tc->dn[0], 0, p);
+  g.dn[1] = KF_PXS(tc->dn[1], 0, p);
+  g.r = (uint32_t)p;
+  if constexpr (OUT != TIP_OUT_NONE) {
+    const int64_t* oi = tc->out_idx;
+    if (oi) g.r = (uint32_t)KF_PXS(oi, 0, p);
+  }
+  return g;
+}
+
+// forecast_partial<7, StructTip> for one propagated parameter without q_pix
+// (returns the propagated diagonal entry: forecast_partial_spd tests it)
+__device__ __forceinline__ float tip_forecast(const KF_CONST_AS TipConst* tc, float xa, float pa, float (&xf)[7],
+                                              float (&P)[28]) {
+#pragma unroll
+  for (int i = 0; i < 7; ++i)
+#pragma unroll
+    for (int j = i; j < 7; ++j)
+      if (StructTip::on(i, j)) P[tri(7, i, j)] = tc->cinv[tri(7, i, j)];
+  const int J = tc->j;
+  const float pjj = kf_rcp(kf_rcp(pa) + tc->q);
+  const float xj = tc->m * xa;
+#pragma unroll
+  for (int j = 0; j < 7; ++j) {
+    P[tri(7, j, j)] = (j == J) ? pjj : P[tri(7, j, j)];
+    xf[j] = (j == J) ? xj : tc->mean[j];
+  }
+  return pjj;
+}
+
+// store_a_rows<7, StructTip> for the stored-rows mode ROWS
+template <int ROWS>
+__device__ __forceinline__ void tip_store_rows(const KF_CONST_AS TipConst* tc, int64_t p, const float (&A)[28]) {
+  if constexpr (ROWS == TIP_ROWS_ALL) {
+    const int64_t ld = tc->ld;
+#pragma unroll
+    for (int i = 0; i < 7; ++i)
+#pragma unroll
+      for (int j = i; j < 7; ++j) {
+        const int t = tri(7, i, j);
+        if (StructTip::on(i, j)) KF_PXS(tc->a_out, t * ld, p) = A[t];
+        else KF_PXS(tc->a_out, t * ld, p) = tc->cinv[t];
+      }
+  } else if constexpr (ROWS == TIP_ROWS_DIAG) {
+    const int J = tc->j;
+    // (gather_state_u: a plain select chain is lowered to a scratch array)
+    float dg[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) dg[j] = A[tri(7, j, j)];
+    const float v = gather_state_u<7>(dg, J);
+    // row tri(J, J) = J * 7 - J (J - 1) / 2
+    KF_PXS(tc->a_out, (int64_t)(J * 7 - (J * (J - 1)) / 2) * tc->ld, p) = v;
+  }
+}
+
+template <int K>
+__device__ __forceinline__ void tip_inputs(const KF_CONST_AS TipBandConst* bc, const float (&x0)[7], float (&xi)[4],
+                                           float& c) {
+  constexpr GpmMap M = gpm_const_map(K);
+#pragma unroll
+  for (int d = 0; d < 4; ++d) xi[d] = x0[M.m[d]] - bc->center[d];
+#pragma unroll
+  for (int d = 0; d < 4; ++d) c = fmaf(bc->coef[d] * xi[d], xi[d], c);
+}
+
+template <bool IL, int ROWS, int OUT>
+__device__ __forceinline__ float pixel_analysis_tip_sl(int64_t p, bool act, const TipGroup& grp, const kf_h8* lds,
+                                                       float& dn_first KF_PHASE_PARAM) {
+  constexpr int NP = 7, D = 4, NT = 28;
+  typedef StructTip M;
+  float x0[NP], A[NT], b[NP];
+  dn_first = 0.f;
+  KF_PHASE_COUNT(KF_PH_GROUPS)
+  for (int it = 0;; ++it) {
+    p = opaque_lane(p);
+    // re-read through the opaque kernarg pointer: the block is not pinned in SGPRs across the GP loop
+    const KF_CONST_AS TipConst* tc =
+        &opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->tc;
+    uint8_t st = 0;
+    {
+      float xf[NP];
+      const float pjj = tip_forecast(tc, grp.xa, grp.pa, xf, A);
+      if (!((pjj > 0.f) && finitef(pjj))) st |= ST_NONSPD;
+      if (it == 0) {
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+          x0[j] = xf[j];
+          b[j] = 0.f;
+        }
+      } else {
+        prior_rhs<NP, true, M>(A, xf, x0, b);
+      }
+    }
+    int nobs = 0;
+    int off = 0;
+    bool wave_obs = false;
+    const bool line = it == 0 && tc->line_tab;
+    LinePos lp_it{nullptr, 0.f, false};
+    if (line) {
+      // line_pos with the table's parameter known to be the propagated one
+      const int n = tc->line_n;
+      const float t = gather_state_u<NP>(x0, tc->j);
+      const float u = (t - tc->line_t0) * tc->line_inv_h;
+      lp_it.in = u >= 0.f && u <= (float)n;
+      const float uc = fminf(fmaxf(u, 0.f), (float)n);
+      const int k = min((int)uc, n - 1);
+      lp_it.s = uc - (float)k;
+      lp_it.row = tc->line_tab + (int64_t)k * (2 * (D + 1) * 4);
+    }
+    auto band = [&](auto bic, auto mkc) {
+      constexpr int BI = decltype(bic)::value, MK = decltype(mkc)::value;
+      const KF_CONST_AS TipBandConst* bc = &tc->band[BI];
+      // decode_obs<OBS_DN16>
+      float y, w;
+      {
+        const uint16_t dn = grp.dn[BI];
+        const float yd = (float)dn * bc->scale;
+        const float sig = fmaxf(bc->rel_unc * yd, bc->unc_floor);
+        const bool okd = dn > 0 && sig > 0.f;
+        w = okd ? kf_rcp(sig * sig) : 0.f;
+        y = dn > 0 ? yd : 0.f;
+      }
+      const bool use = act && (w > 0.f);
+      float H0 = 0.f, g[D];
+#pragma unroll
+      for (int d = 0; d < D; ++d) g[d] = 0.f;
+      bool ok = false;
+      const int nch = bc->nchunk;
+      const bool any = __any(use);
+      wave_obs = wave_obs || any;
+      bool tabled = false;
+      if (any && line) {
+        if (__all(lp_it.in || !use)) {
+          line_eval<D>(lp_it.row + BI * (D + 1) * 4, lp_it.s, H0, g);
+          tabled = true;
+          ok = true;
+        }
+      }
+      if (any && !tabled) {
+        float xi[D], c = 0.f;
+        tip_inputs<MK>(bc, x0, xi, c);
+        c *= -0.5f * LOG2E;
+        float S[D + 1];
+        KF_PHASE(KF_PH_BAND_IN)
+        gp_mfma_sums<D, IL, false>(lds + off, lds + tc->gpm_frags - 1, nch, xi, c, S);
+        KF_PHASE(KF_PH_GP)
+        const KF_CONST_AS TipBandConst* q = opaque(bc);   // epilogue fields: not live across the chunk loop
+        const float sc = q->gpm_scale;
+        const float S0 = S[0] * sc;
+        H0 = q->offset + S0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) g[d] = fmaf(-q->coef[d] * xi[d], S0, LN2 * (S[1 + d] * sc));
+        ok = finitef(H0);
+#pragma unroll
+        for (int d = 0; d < D; ++d) ok = ok && finitef(g[d]);
+      }
+      off += nch * gpm_frags_per_chunk(D);
+      if (use && !ok) st |= ST_BAD_OP;
+      if (use && ok) {
+        ++nobs;
+        const float wy = w * (y - H0);
+        gpm_update_const<NP, D, MK>(A, b, g, w, wy);
+      }
+      KF_PHASE(KF_PH_BAND_OUT)
+    };
+    KF_PHASE(KF_PH_FORECAST)
+    band(std::integral_constant<int, 0>{}, std::integral_constant<int, GPM_MAP_TIP_VIS>{});
+    band(std::integral_constant<int, 1>{}, std::integral_constant<int, GPM_MAP_TIP_NIR>{});
+    if (nobs == 0) st |= ST_NO_OBS;
+    const KF_CONST_AS TipConst* ka =
+        &opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->tc;
+    const int64_t ld = ka->ld;
+    // the launch's domain box (state_out_of_domain)
+    auto out_of_domain = [&](const float (&x)[NP]) {
+      bool o = false;
+#pragma unroll
+      for (int j = 0; j < NP; ++j) o = o || !(x[j] >= ka->dom_lo[j] && x[j] <= ka->dom_hi[j]);
+      return ka->dom_check && o;
+    };
+    auto store_out = [&](const float (&x)[NP], const float (&dA)[NP]) {
+      if constexpr (OUT != TIP_OUT_NONE) {
+        const int64_t r = (int64_t)grp.r;
+        const int64_t pl = ka->out_plane;
+        if constexpr (OUT == TIP_OUT_MEAN) {
+#pragma unroll
+          for (int j = 0; j < NP; ++j) KF_PXS(ka->out_mean, j * pl, r) = x[j];
+        }
+#pragma unroll
+        for (int j = 0; j < NP; ++j) KF_PXS(ka->out_unc, j * pl, r) = kf_rsqrt(dA[j]);
+      }
+    };
+    // unobserved wave at the forecast (pixel_analysis_mfma): written directly when every lane is healthy
+    if (it == 0 && !wave_obs) {
+      bool healthy = true;
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        float s = A[tri(NP, j, j)];
+        if (j == 5) {
+          const float s2 = A[tri(NP, 2, 2)];
+          const float u25 = A[tri(NP, 2, 5)] * kf_rsqrt(s2 > 0.f ? s2 : 1.f);
+          s = fmaf(-u25, u25, s);
+        }
+        healthy = healthy && (s > 0.f) && finitef(s) && finitef(x0[j]);
+      }
+      if (__all(healthy)) {
+        st = ST_NO_OBS;
+        float x1[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) x1[j] = x0[j] + 0.f;
+        if (out_of_domain(x1)) st |= ST_OUT_OF_DOMAIN;
+        if (act) {
+          tip_store_rows<ROWS>(ka, p, A);
+#pragma unroll
+          for (int j = 0; j < NP; ++j) KF_PXS(ka->x_out, j * ld, p) = x1[j];
+          float dA[NP];
+#pragma unroll
+          for (int j = 0; j < NP; ++j) dA[j] = A[tri(NP, j, j)];
+          store_out(x1, dA);
+          uint8_t* sp = ka->status;
+          if (sp) KF_PXS(sp, 0, p) = st;
+        }
+        KF_PHASE(KF_PH_SOLVE)
+        return 0.f;
+      }
+    }
+    const bool last = it + 1 >= ka->gn_fused;
+    if (last) {
+      if (out_of_domain(x0)) st |= ST_OUT_OF_DOMAIN;
+    }
+    const bool store = last && act;
+    // analysis_epilogue<7, true, SPEC_PROP_TIP>: plain solve, no b_out / x0_out
+    if (store) tip_store_rows<ROWS>(ka, p, A);
+    float dn = 0.f;
+    {
+      float dA[NP];
+#pragma unroll
+      for (int j = 0; j < NP; ++j) dA[j] = A[tri(NP, j, j)];
+      const bool spd = chol_packed<NP, M>(A) && !(st & ST_NONSPD);
+      chol_solve<NP, M>(A, b);
+      {
+        // analysis_epilogue adds x0 behind its test of b_out, in a block of its own: a product and a
+        // sum, two roundings.  Here the sum follows the solve's last product directly and would be
+        // contracted into one FMA (one rounding, other bits), so contraction is off for it.
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int j = 0; j < NP; ++j) b[j] = b[j] + x0[j];
+      }
+      bool fin = true;
+#pragma unroll
+      for (int j = 0; j < NP; ++j) fin = fin && finitef(b[j]);
+      if (!spd || !fin) {
+        st |= (!spd ? ST_NONSPD : 0) | (!fin ? ST_NONFINITE : 0) | ST_FALLBACK;
+        tip_forecast(opaque(ka), grp.xa, grp.pa, b, A);
+#pragma unroll
+        for (int j = 0; j < NP; ++j) dA[j] = A[tri(NP, j, j)];
+        if (store) tip_store_rows<ROWS>(ka, p, A);
+      }
+      if (store) {
+#pragma unroll
+        for (int j = 0; j < NP; ++j) KF_PXS(ka->x_out, j * ld, p) = b[j];
+      }
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        const float d = b[j] - x0[j];
+        dn = fmaf(d, d, dn);
+      }
+      if ((st & ST_FALLBACK) && !finitef(dn)) dn = 0.f;
+      if (store) {
+        store_out(b, dA);
+        uint8_t* sp = ka->status;
+        if (sp) KF_PXS(sp, 0, p) = st;
+      }
+    }
+    KF_PHASE(KF_PH_SOLVE)
+    if (last) return act ? dn : 0.f;
+    dn_first = dn;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) x0[j] = b[j];
+  }
+}
+
 // K1g (gain / covariance form) with the GP on the matrix cores: gain_pixel
 // (kf_core.h) with lane = pixel, each band's GP sums wave-cooperative as in
 // pixel_analysis_mfma (every lane of the wave takes part, act = false lanes

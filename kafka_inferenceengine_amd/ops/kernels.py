@@ -138,6 +138,7 @@ class BandTable:
     dom: tuple | None = None  # GP domain box in state space (lo, hi lists; ST_OUT_OF_DOMAIN)
     specs: tuple = ()       # the bands' OperatorSpecs (line tables of the first iteration at the forecast)
     tip_maps: bool = False  # exactly two 4-input GP bands with the JRC-TIP VIS then NIR state maps
+    descs: tuple = ()       # host copies of the descriptors (the straight-line JRC-TIP kernel's constants)
 
     @property
     def ptr(self) -> int:
@@ -182,6 +183,9 @@ class Variant(IntEnum):
     # the 10-parameter global-table kernels with DN16 observations, both forms (kf_device.h
     # mixlo_split_analysis / mixlo_split_gain); any other launch with it raises.
     MIXLO_SPLIT = 22
+    # the SPEC_PROP_TIP kernels where the launch has the shape of the straight-line JRC-TIP kernel
+    # (kf_core.h tip_sl_shape): that kernel's oracle and the other arm of its A/B
+    LOOPED_TIP = 24
 
 
 # analysis variant of launches that pass none (tests switch it to an oracle path;
@@ -272,7 +276,7 @@ def make_band_table(descs: list, device, keepalive=(), specs=()) -> BandTable:
     tip_maps = len(descs) == 2 and all(d.op == OP_GP and d.d == 4 for d in descs) and \
         [d.map_kind for d in descs] == [2, 3]
     return BandTable(buf, len(descs), tuple(keepalive), fast_d, fast_obs, gpm_frags, gpm_global, layout,
-                     _state_domain(descs), tuple(specs), tip_maps)
+                     _state_domain(descs), tuple(specs), tip_maps, tuple(descs))
 
 
 def _state_domain(descs):
@@ -355,6 +359,17 @@ A_STRUCT_TIP_PRIOR = 2
 TIP_ZERO_ENTRIES = ((0, 3), (0, 4), (0, 5), (1, 3), (1, 4), (1, 5), (2, 3), (2, 4))
 # what the last analysis() launches took: "tip" the structure-aware solve, "dense" the dense one
 STRUCT_LAUNCHES = {"tip": 0, "dense": 0}
+# of the "tip" launches: "straight" took the straight-line kernel (AnalysisArgs.tc filled: the launch
+# has its shape, kf_core.h tip_sl_shape), "looped" the SPEC_*_TIP kernels
+TIP_SL_LAUNCHES = {"straight": 0, "looped": 0}
+
+
+def _count_launch(a):
+    if a.prop:
+        tip = bool(getattr(a, "a_struct", 0))
+        STRUCT_LAUNCHES["tip" if tip else "dense"] += 1
+        if tip:
+            TIP_SL_LAUNCHES["straight" if getattr(a, "tc_on", False) else "looped"] += 1
 
 
 def _tri(n, i, j):
@@ -370,10 +385,11 @@ def tip_structure(n_params, bands: BandTable, prop, variant=None) -> int:
     ``A_STRUCT_TIP_PRIOR`` in addition when that precision is diagonal plus the
     (2, 5) pair and finite with finite reset means (the kernels' unobserved-wave
     shortcut).  0 (the dense solve) otherwise and for every oracle variant but
-    ``MIXLO_SPLIT`` (the default's kernels with the other split)."""
+    ``MIXLO_SPLIT`` (the default's kernels with the other split) and ``LOOPED_TIP``
+    (the default's kernels before the straight-line one)."""
     v = DEFAULT_VARIANT if variant is None else variant
-    if prop is None or n_params != 7 or not bands.tip_maps or int(v) not in (int(Variant.DEFAULT),
-                                                                             int(Variant.MIXLO_SPLIT)):
+    if prop is None or n_params != 7 or not bands.tip_maps or int(v) not in (
+            int(Variant.DEFAULT), int(Variant.MIXLO_SPLIT), int(Variant.LOOPED_TIP)):
         return 0
     c = [float(x) for x in list(prop.args.reset_cinv)[:ntri(7)]]
     if any(c[_tri(7, i, j)] != 0.0 for i, j in TIP_ZERO_ENTRIES):
@@ -470,8 +486,7 @@ def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=
         hit = _ANALYSIS_MEMO.get(key)
         if hit is not None:
             a, grid = hit
-            if a.prop:
-                STRUCT_LAUNCHES["tip" if getattr(a, "a_struct", 0) else "dense"] += 1
+            _count_launch(a)
             n_part = ext().analysis(n_params, a, grid, _dev(ref), _stream(ref))
             _set_valid(partials, n_part)
             _set_valid(partials_first if gn_fused == 2 else None, n_part)
@@ -607,8 +622,10 @@ def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=
     if prop is not None and a_in is None and hasattr(a, "a_struct") and (
             dev.type != "cuda" or (fast and a.band_layout == BAND_LAYOUT_TIP and bands.fast_obs == OBS_DN16)):
         a.a_struct = tip_structure(n_params, bands, prop, v)
-    if prop is not None:
-        STRUCT_LAUNCHES["tip" if getattr(a, "a_struct", 0) else "dense"] += 1
+    # the straight-line JRC-TIP kernel: its constant block, filled where the launch has its shape
+    if dev.type == "cuda" and prop is not None and getattr(a, "a_struct", 0) and hasattr(ext(), "tip_const_fill"):
+        ext().tip_const_fill(n_params, a, prop.args, list(bands.descs))
+    _count_launch(a)
     grid = grid_for(nv)
     if partials is not None and partials.numel() < grid:
         raise ValueError("partials must hold one entry per workgroup (partials_buffer)")
