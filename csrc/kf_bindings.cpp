@@ -386,12 +386,28 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
   m.attr("DFL_MODE_FIXED") = DFL_MODE_FIXED;
   m.attr("DFL_MODE_DYNAMIC") = DFL_MODE_DYNAMIC;
   m.attr("DFL_MODE_DYNAMIC_FORCE_FIXED") = DFL_MODE_DYNAMIC_FORCE_FIXED;   // host runner only (tests)
+  // the same for sample = DFL_FMT_U16 (scaled 16-bit samples, predictor 2, 512-byte rows)
+  m.attr("DFL_BOUND16") = DFL_BOUND16;
+  m.attr("DFL_ROW_SCRATCH16") = (int64_t)DFL_TILE * DFL_ROW_WORDS16 * 4;
+  m.attr("DFL_ROW_SCRATCH16_DYN") = (int64_t)DFL_TILE * DFL_ROW_WORDS16_DYN * 4;
+  m.attr("DFL_FMT_F32") = DFL_FMT_F32;
+  m.attr("DFL_FMT_U16") = DFL_FMT_U16;
   m.def("deflate_tiles", [](uintptr_t src, int64_t plane_ld, int H, int W, int nplanes, uintptr_t out,
-                            uintptr_t sizes, bool device, uintptr_t stream, uintptr_t scratch, int mode) {
+                            uintptr_t sizes, bool device, uintptr_t stream, uintptr_t scratch, int mode, int sample,
+                            uintptr_t qa, uintptr_t qb, uintptr_t sat) {
     DflArgs a{};
     a.mode = mode;
     if (mode != DFL_MODE_FIXED && mode != DFL_MODE_DYNAMIC && !(mode == DFL_MODE_DYNAMIC_FORCE_FIXED && !device))
       throw std::runtime_error("deflate_tiles: unknown mode");
+    if (sample != DFL_FMT_F32 && sample != DFL_FMT_U16) throw std::runtime_error("deflate_tiles: unknown sample format");
+    if (sample == DFL_FMT_U16 && (!qa || !qb))
+      throw std::runtime_error("deflate_tiles: 16-bit samples need the per-plane a and b");
+    if (sample == DFL_FMT_F32 && (qa || qb || sat))
+      throw std::runtime_error("deflate_tiles: a, b and the saturation counter belong to the 16-bit format");
+    a.fmt = sample;
+    a.qa = P<const float>(qa);
+    a.qb = P<const float>(qb);
+    a.sat = P<uint32_t>(sat);
     a.src = P<const float>(src);
     a.plane_ld = plane_ld;
     a.H = H;
@@ -410,11 +426,23 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
       check_host(host_deflate_tiles(a), "deflate_tiles");
     }
   }, py::arg("src"), py::arg("plane_ld"), py::arg("H"), py::arg("W"), py::arg("nplanes"), py::arg("out"),
-     py::arg("sizes"), py::arg("device"), py::arg("stream"), py::arg("scratch"), py::arg("mode") = (int)DFL_MODE_FIXED);
+     py::arg("sizes"), py::arg("device"), py::arg("stream"), py::arg("scratch"), py::arg("mode") = (int)DFL_MODE_FIXED,
+     py::arg("sample") = (int)DFL_FMT_F32, py::arg("qa") = (uintptr_t)0, py::arg("qb") = (uintptr_t)0,
+     py::arg("sat") = (uintptr_t)0);
   m.def("deflate_pack", [](uintptr_t scratch, uintptr_t sizes, uintptr_t offs, uintptr_t packed, int ntiles,
-                           uintptr_t stream) {
+                           uintptr_t stream, int64_t bound) {
     check_hip(dev_deflate_pack(P<const uint8_t>(scratch), P<const uint32_t>(sizes), P<const int64_t>(offs),
-                               P<uint8_t>(packed), ntiles, (hipStream_t)stream), "deflate_pack");
+                               P<uint8_t>(packed), ntiles, (hipStream_t)stream, bound), "deflate_pack");
+  }, py::arg("scratch"), py::arg("sizes"), py::arg("offs"), py::arg("packed"), py::arg("ntiles"), py::arg("stream"),
+     py::arg("bound") = (int64_t)DFL_BOUND);
+  // host runner of the 16-bit encoder's quantiser (dfl_quantise): planes [nplanes][plane_ld] float32 ->
+  // dst [nplanes][n] uint16, sat[plane] += saturated samples
+  m.def("quantise_u16", [](uintptr_t src, int64_t plane_ld, int64_t n, int nplanes, uintptr_t qa, uintptr_t qb,
+                           uintptr_t dst, uintptr_t sat) {
+    if (n > plane_ld) throw std::runtime_error("quantise_u16: plane_ld < n");
+    py::gil_scoped_release nogil;
+    check_host(host_quantise_u16(P<const float>(src), plane_ld, n, nplanes, P<const float>(qa), P<const float>(qb),
+                                 P<uint16_t>(dst), P<uint32_t>(sat)), "quantise_u16");
   });
   // GeoTIFF tile decoder (kf_inflate.h): zlib streams -> predictor undone -> window of a plane
   m.attr("INF_OK") = INF_OK;

@@ -45,6 +45,10 @@
 // Predictor 3 (TIFF Technical Note 3): each row's samples are split into byte
 // planes, most significant byte first, and the 4 x 256 bytes are differenced
 // (d[0] = r[0], d[i] = r[i] - r[i - 1] mod 256).
+//
+// Scaled 16-bit samples (DFL_FMT_U16, opt-in): the same streams over rows of
+// 512 bytes, the float samples quantised on the way in (dfl_quantise) and
+// differenced as 16-bit words (TIFF predictor 2); see DFL_FMT_* below.
 #pragma once
 #include <stdint.h>
 #include "kf_core.h"
@@ -72,6 +76,50 @@ constexpr int DFL_MAX_BITS = 15, DFL_MAX_CL_BITS = 7;
 constexpr int DFL_ROW_WORDS_DYN = (DFL_MAX_BITS * DFL_ROW + 31) / 32 + 1;
 static_assert(32 * (DFL_ROW_WORDS_DYN - 1) >= DFL_MAX_BITS * DFL_ROW, "dynamic row scratch: 15 bits per byte");
 static_assert(32 * (DFL_ROW_WORDS - 1) >= 9 * DFL_ROW, "fixed row scratch: 9 bits per byte");
+
+// DflArgs.fmt: the samples of the written tile.  DFL_FMT_F32: float32 under
+// predictor 3 (above).  DFL_FMT_U16: scaled 16-bit integers under predictor 2
+// (TIFF 6.0 §14): the float sample is quantised (dfl_quantise) in the row
+// load, the row's samples are differenced as 16-bit little-endian words
+// (d[0] = q[0], d[c] = q[c] - q[c - 1] mod 65536, columns past the raster 0)
+// and the 512 bytes (low byte of d[c], then its high byte) go to the row
+// tokeniser as they are.  Everything that follows the row length -- the Adler
+// partials, the raw size, the per-tile bound, the row scratch -- is below.
+constexpr int DFL_FMT_F32 = 0, DFL_FMT_U16 = 1;
+constexpr uint32_t DFL_U16_NODATA = 65535u, DFL_U16_MAX = 65534u;
+constexpr int DFL_ROW16 = DFL_TILE * 2;
+constexpr int64_t DFL_RAW16 = (int64_t)DFL_TILE * DFL_ROW16;   // 131072 bytes per tile
+constexpr int64_t DFL_BOUND16 = ((2 + (19 + 9 * DFL_RAW16 + 14) / 8 + 4) + 15) / 16 * 16;
+constexpr int DFL_ROW_WORDS16 = (9 * DFL_ROW16 + 31) / 32 + 1;
+constexpr int DFL_ROW_WORDS16_DYN = (DFL_MAX_BITS * DFL_ROW16 + 31) / 32 + 1;
+static_assert(32 * (DFL_ROW_WORDS16_DYN - 1) >= DFL_MAX_BITS * DFL_ROW16, "dynamic row scratch: 15 bits per byte");
+static_assert(32 * (DFL_ROW_WORDS16 - 1) >= 9 * DFL_ROW16, "fixed row scratch: 9 bits per byte");
+KF_HD constexpr int dfl_row_len(int fmt) { return fmt == DFL_FMT_U16 ? DFL_ROW16 : DFL_ROW; }
+KF_HD constexpr int64_t dfl_raw(int fmt) { return fmt == DFL_FMT_U16 ? DFL_RAW16 : DFL_RAW; }
+KF_HD constexpr int64_t dfl_bound(int fmt) { return fmt == DFL_FMT_U16 ? DFL_BOUND16 : DFL_BOUND; }
+KF_HD constexpr int dfl_row_words(int fmt, bool dyn) {
+  return fmt == DFL_FMT_U16 ? (dyn ? DFL_ROW_WORDS16_DYN : DFL_ROW_WORDS16) : (dyn ? DFL_ROW_WORDS_DYN : DFL_ROW_WORDS);
+}
+
+// The 16-bit sample of v for a raster with range [lo, hi]: a = 65534 / (hi - lo)
+// and b = -lo * 65534 / (hi - lo), each formed in float64 and rounded once to
+// float32 by the caller.  NaN is the nodata value 65535; everything else is
+// clamp(rint(fma(v, a, b)), 0, 65534), +-inf included.  The fma is explicit, so
+// no contraction setting decides a bit and the device and the host agree.  A
+// sample whose rounded value falls outside [0, 65534] is saturated: ++sat.
+KF_HD uint32_t dfl_quantise(float v, float a, float b, uint32_t& sat) {
+  if (v != v) return DFL_U16_NODATA;
+  const float t = __builtin_rintf(__builtin_fmaf(v, a, b));
+  if (t < 0.f) {
+    ++sat;
+    return 0u;
+  }
+  if (t > (float)DFL_U16_MAX) {
+    ++sat;
+    return DFL_U16_MAX;
+  }
+  return (uint32_t)t;
+}
 
 KF_HD uint32_t dfl_rev(uint32_t code, int len) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -132,21 +180,27 @@ KF_HD void dfl_match(int L, uint32_t& bits, int& len) {
 
 // byte i of a predicted row (before differencing) from the row's samples
 // (float bits; samples past the raster are 0): plane i / 256 is the sample's
-// byte 3 - i / 256 (most significant first)
-template <typename ROW>
-KF_HD uint32_t dfl_row_byte(const ROW& row, int i) {
-  const int k = i >> 8, c = i & 255;
-  return (row(c) >> (8 * (3 - k))) & 0xFFu;
+// byte 3 - i / 256 (most significant first).  DFL_FMT_U16: row(i) is byte i of
+// the row's 16-bit differences, which the caller forms in one pass over the columns
+template <int FMT = DFL_FMT_F32, typename ROW>
+KF_HD uint32_t dfl_row_byte(ROW&& row, int i) {
+  if constexpr (FMT == DFL_FMT_U16) {
+    return row(i);
+  } else {
+    const int k = i >> 8, c = i & 255;
+    return (row(c) >> (8 * (3 - k))) & 0xFFu;
+  }
 }
 
 // Tokenises one tile row: TOK(v, L) receives the tokens in order, a literal
 // byte v (L = 0) or a distance-1 match of length L (3..258; v is the repeated
 // byte).  Also returns the row's Adler-32 partial sums over its predicted bytes
 // d: s1 = sum d, s2 = sum (rest - i) d with rest = bytes from the row's start
-// to the end of the tile.
-template <typename ROW, typename TOK>
-KF_HD void dfl_tokenise_row(const ROW& row, int64_t rest, TOK&& tok, uint64_t& s1, uint64_t& s2) {
-  uint32_t prev = dfl_row_byte(row, 0);
+// to the end of the tile.  FMT: the row's length and whether its bytes are
+// differenced here (float32, predictor 3) or arrive differenced (16-bit).
+template <int FMT = DFL_FMT_F32, typename ROW, typename TOK>
+KF_HD void dfl_tokenise_row(ROW&& row, int64_t rest, TOK&& tok, uint64_t& s1, uint64_t& s2) {
+  uint32_t prev = dfl_row_byte<FMT>(row, 0);
   uint32_t last = prev;           // the last byte of the output so far (d)
   tok(last, 0);
   s1 = last;
@@ -160,9 +214,9 @@ KF_HD void dfl_tokenise_row(const ROW& row, int64_t rest, TOK&& tok, uint64_t& s
     }
     run = 0;
   };
-  for (int i = 1; i < DFL_ROW; ++i) {
-    const uint32_t r = dfl_row_byte(row, i);
-    const uint32_t d = (r - prev) & 0xFFu;
+  for (int i = 1; i < dfl_row_len(FMT); ++i) {
+    const uint32_t r = dfl_row_byte<FMT>(row, i);
+    const uint32_t d = FMT == DFL_FMT_U16 ? r : (r - prev) & 0xFFu;
     prev = r;
     s1 += d;
     s2 += (uint64_t)(rest - i) * d;
@@ -183,9 +237,9 @@ KF_HD void dfl_tokenise_row(const ROW& row, int64_t rest, TOK&& tok, uint64_t& s
 
 // Encodes one tile row with the fixed Huffman codes: SINK(bits, len) receives
 // the LSB-first bit strings in order (Adler partials as dfl_tokenise_row)
-template <typename ROW, typename SINK>
-KF_HD void dfl_encode_row(const ROW& row, int64_t rest, SINK&& sink, uint64_t& s1, uint64_t& s2) {
-  dfl_tokenise_row(row, rest, [&](uint32_t v, int L) {
+template <int FMT = DFL_FMT_F32, typename ROW, typename SINK>
+KF_HD void dfl_encode_row(ROW&& row, int64_t rest, SINK&& sink, uint64_t& s1, uint64_t& s2) {
+  dfl_tokenise_row<FMT>(row, rest, [&](uint32_t v, int L) {
     uint32_t b;
     int l;
     if (L) dfl_match(L, b, l);

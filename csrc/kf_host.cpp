@@ -183,19 +183,24 @@ static int h_unpack(const float* x, const float* a, int64_t N, int64_t ld, const
 // GeoTIFF tiles on the host: the same row encoder as dfl_tile_kernel, rows in
 // order into one byte stream per tile (bit-identical streams).  Dynamic mode:
 // the same two passes as dfl_tile_dyn_kernel (histogram, table, encode).
+// FMT = DFL_FMT_U16: the row's samples quantised (dfl_quantise) and differenced
+// as 16-bit words in the row functor, as the kernel's row load does.
 // Returns -2 if a tile's stream is not the size its table announced.
-int host_deflate_tiles(const DflArgs& a) {
+template <int FMT>
+static int host_deflate_tiles_fmt(const DflArgs& a) {
   const int per = a.tiles_x * a.tiles_y, n = a.nplanes * per;
-  if (n <= 0) return -1;
-  if (a.mode != DFL_MODE_FIXED && a.mode != DFL_MODE_DYNAMIC && a.mode != DFL_MODE_DYNAMIC_FORCE_FIXED) return -1;
+  constexpr int64_t BOUND = dfl_bound(FMT), RAW = dfl_raw(FMT);
+  constexpr int ROW = dfl_row_len(FMT);
   int bad = 0;
+  std::vector<uint32_t> satv((size_t)a.nplanes, 0u);
+  uint32_t* satp = satv.data();
 #pragma omp parallel for schedule(dynamic, 1) reduction(| : bad)
   for (int tile = 0; tile < n; ++tile) {
     const int plane = tile / per, tt = tile - plane * per;
     const int ty = tt / a.tiles_x, tx = tt - ty * a.tiles_x;
     const int x0 = tx * DFL_TILE;
     const int ncol = a.W - x0 < DFL_TILE ? a.W - x0 : DFL_TILE;
-    uint8_t* o = a.out + (int64_t)tile * DFL_BOUND;
+    uint8_t* o = a.out + (int64_t)tile * BOUND;
     int64_t nb = 0;
     uint64_t acc = 0;
     int nacc = 0;
@@ -208,19 +213,35 @@ int host_deflate_tiles(const DflArgs& a) {
         nacc -= 8;
       }
     };
-    // fn(r, row, rest) for every row of the tile
+    const float qa = FMT == DFL_FMT_U16 ? a.qa[plane] : 0.f, qb = FMT == DFL_FMT_U16 ? a.qb[plane] : 0.f;
+    uint32_t sat = 0;
+    // fn(row, rest) for every row of the tile
     auto rows = [&](auto&& fn) {
       for (int r = 0; r < DFL_TILE; ++r) {
         const int64_t y = (int64_t)ty * DFL_TILE + r;
         const bool rin = y < a.H;
         const float* rowp = a.src + (int64_t)plane * a.plane_ld + (rin ? y : 0) * a.W + x0;
-        auto row = [&](int c) -> uint32_t {
-          if (!(rin && c < ncol)) return 0u;
-          uint32_t u;
-          memcpy(&u, rowp + c, 4);
-          return u;
-        };
-        fn(row, DFL_RAW - (int64_t)r * DFL_ROW);
+        if constexpr (FMT == DFL_FMT_U16) {
+          uint32_t qprev = 0, d = 0;
+          auto row = [&](int i) -> uint32_t {     // byte i of the row's 16-bit differences, i ascending
+            if (!(i & 1)) {
+              const int c = i >> 1;
+              const uint32_t q = (rin && c < ncol) ? dfl_quantise(rowp[c], qa, qb, sat) : 0u;
+              d = (q - (c ? qprev : 0u)) & 0xFFFFu;
+              qprev = q;
+            }
+            return (d >> (8 * (i & 1))) & 0xFFu;
+          };
+          fn(row, RAW - (int64_t)r * ROW);
+        } else {
+          auto row = [&](int c) -> uint32_t {
+            if (!(rin && c < ncol)) return 0u;
+            uint32_t u;
+            memcpy(&u, rowp + c, 4);
+            return u;
+          };
+          fn(row, RAW - (int64_t)r * ROW);
+        }
       }
     };
     sink(0x78u, 8);
@@ -231,7 +252,7 @@ int host_deflate_tiles(const DflArgs& a) {
       sink(1u, 2);                 // BTYPE 01: fixed Huffman
       rows([&](auto& row, int64_t rest) {
         uint64_t s1, s2;
-        dfl_encode_row(row, rest, sink, s1, s2);
+        dfl_encode_row<FMT>(row, rest, sink, s1, s2);
         t1 += s1;
         t2 += s2;
       });
@@ -242,10 +263,11 @@ int host_deflate_tiles(const DflArgs& a) {
       DflWork k;
       rows([&](auto& row, int64_t rest) {
         uint64_t s1, s2;
-        dfl_tokenise_row(row, rest, [&](uint32_t v, int L) { ++freq[dfl_token_symbol(v, L)]; }, s1, s2);
+        dfl_tokenise_row<FMT>(row, rest, [&](uint32_t v, int L) { ++freq[dfl_token_symbol(v, L)]; }, s1, s2);
         t1 += s1;
         t2 += s2;
       });
+      const uint32_t sat1 = sat;   // the second pass quantises the same samples again
       freq[256] = 1;
       int used = 0;
       for (int s = 0; s < DFL_NSYM; ++s) {
@@ -260,22 +282,56 @@ int host_deflate_tiles(const DflArgs& a) {
       if ((uint64_t)(nb - 2) * 8 + (uint64_t)nacc != t.head_bits) bad |= 1;
       rows([&](auto& row, int64_t rest) {
         uint64_t s1, s2;
-        dfl_tokenise_row(row, rest, [&](uint32_t v, int L) {
+        dfl_tokenise_row<FMT>(row, rest, [&](uint32_t v, int L) {
           uint32_t b;
           int l;
           dfl_table_token(t, v, L, b, l);
           sink(b, l);
         }, s1, s2);
       });
+      sat = sat1;
       sink(t.code[256], t.len[256]);   // end of block
       if ((uint64_t)(nb - 2) * 8 + (uint64_t)nacc != t.block_bits) bad |= 1;
     }
     if (nacc) sink(0u, 8 - nacc);
-    const uint32_t adler = dfl_adler(t1, t2, DFL_RAW);
+    const uint32_t adler = dfl_adler(t1, t2, RAW);
     for (int k = 3; k >= 0; --k) sink((adler >> (8 * k)) & 0xFFu, 8);
     a.sizes[tile] = (uint32_t)nb;
+    if (FMT == DFL_FMT_U16 && sat) {
+#pragma omp atomic
+      satp[plane] += sat;
+    }
   }
+  if (FMT == DFL_FMT_U16 && a.sat)
+    for (int p = 0; p < a.nplanes; ++p) a.sat[p] += satv[(size_t)p];
   return bad ? -2 : 0;
+}
+
+int host_deflate_tiles(const DflArgs& a) {
+  if (a.nplanes * a.tiles_x * a.tiles_y <= 0) return -1;
+  if (a.mode != DFL_MODE_FIXED && a.mode != DFL_MODE_DYNAMIC && a.mode != DFL_MODE_DYNAMIC_FORCE_FIXED) return -1;
+  if (a.fmt == DFL_FMT_F32) return host_deflate_tiles_fmt<DFL_FMT_F32>(a);
+  if (a.fmt == DFL_FMT_U16 && a.qa && a.qb) return host_deflate_tiles_fmt<DFL_FMT_U16>(a);
+  return -1;
+}
+
+int host_quantise_u16(const float* src, int64_t plane_ld, int64_t n, int nplanes, const float* qa, const float* qb,
+                      uint16_t* dst, uint32_t* sat) {
+  if (n < 0 || nplanes <= 0 || !qa || !qb) return -1;
+  for (int p = 0; p < nplanes; ++p) {
+    const float* s = src + (int64_t)p * plane_ld;
+    uint16_t* d = dst + (int64_t)p * n;
+    const float a = qa[p], b = qb[p];
+    uint64_t total = 0;
+#pragma omp parallel for schedule(static) reduction(+ : total)
+    for (int64_t i = 0; i < n; ++i) {
+      uint32_t one = 0;
+      d[i] = (uint16_t)dfl_quantise(s[i], a, b, one);
+      total += one;
+    }
+    if (sat) sat[p] += (uint32_t)total;
+  }
+  return 0;
 }
 
 // GeoTIFF tiles inflated on the host: the decoder of inf_tile_kernel

@@ -108,11 +108,27 @@ struct DflArgs {
   uint32_t* sizes;
   uint8_t* scratch;   // device: DFL_TILE * DFL_ROW_WORDS words per tile (row bit strings before the shift;
                       // DFL_ROW_WORDS_DYN in the dynamic mode)
+  // fmt: DFL_FMT_* (kf_deflate.h); 0 = float32 samples under predictor 3, the
+  // fields below unused.  DFL_FMT_U16: the planes are quantised to scaled 16-bit
+  // samples in the row load (q = clamp(rint(fma(v, qa[plane], qb[plane])), 0,
+  // 65534), NaN -> 65535) and written under predictor 2; tiles then lie at
+  // out + tile * DFL_BOUND16, the row scratch is DFL_ROW_WORDS16(_DYN) words per
+  // row, and sat[plane] (may be null) is incremented by the plane's samples
+  // whose rounded value fell outside [0, 65534]
+  int32_t fmt;
+  const float* qa;
+  const float* qb;
+  uint32_t* sat;
 };
 hipError_t dev_deflate_tiles(const DflArgs& a, hipStream_t s);
+// bound: the tiles' stride in scratch (DFL_BOUND, or DFL_BOUND16 for 16-bit tiles)
 hipError_t dev_deflate_pack(const uint8_t* scratch, const uint32_t* sizes, const int64_t* offs, uint8_t* packed,
-                            int ntiles, hipStream_t s);
+                            int ntiles, hipStream_t s, int64_t bound);
 int host_deflate_tiles(const DflArgs& a);
+// the planes' samples quantised as the DFL_FMT_U16 encoder quantises them
+// (dfl_quantise): dst [nplanes][H * W] uint16, sat[plane] += saturated samples
+int host_quantise_u16(const float* src, int64_t plane_ld, int64_t n, int nplanes, const float* qa, const float* qb,
+                      uint16_t* dst, uint32_t* sat);
 
 // GeoTIFF tile decoder (kf_inflate.h / kf_inflate.hip): one status per tile
 constexpr int32_t INF_OK = 0;

@@ -57,7 +57,7 @@ struct Info {
   std::vector<uint64_t> off, cnt;
   std::vector<double> scale, tie;
   std::vector<uint16_t> geokeys;
-  std::string ascii, nodata;
+  std::string ascii, nodata, metadata;   // metadata: tag 42112 (GDAL_METADATA, XML)
 };
 
 struct File {
@@ -174,6 +174,7 @@ Info parse(const File& f) {
       case 33922: in.tie.resize(cnt); std::memcpy(in.tie.data(), data.data(), sz); break;
       case 34735: in.geokeys.resize(cnt); std::memcpy(in.geokeys.data(), data.data(), sz); break;
       case 34737: in.ascii.assign((const char*)data.data(), strnlen((const char*)data.data(), sz)); break;
+      case 42112: in.metadata.assign((const char*)data.data(), strnlen((const char*)data.data(), sz)); break;
       case 42113: in.nodata.assign((const char*)data.data(), strnlen((const char*)data.data(), sz)); break;
       default: break;
     }
@@ -463,11 +464,13 @@ void write_raw(const std::string& path, const void* data, uint64_t n, int nthrea
 void write_chunks(const std::string& path, int nb, uint64_t H, uint64_t W, int bits, int fmt, uint32_t tile,
                   uint64_t rps, int comp, int predictor, const std::vector<uint64_t>& cnts,
                   const std::function<const uint8_t*(uint64_t)>& chunk, int nthreads, const std::vector<double>& gt,
-                  int epsg, const std::string& citation, const std::string& nodata, int force_big);
+                  int epsg, const std::string& citation, const std::string& nodata, int force_big,
+                  const std::string& metadata = std::string());
 
 void write(const std::string& path, const void* data, int nb, uint64_t H, uint64_t W, int bits, int fmt,
            uint32_t tile, int level, int nthreads, const std::vector<double>& gt, int epsg,
-           const std::string& citation, const std::string& nodata, int force_big, int predictor, int strategy) {
+           const std::string& citation, const std::string& nodata, int force_big, int predictor, int strategy,
+           const std::string& metadata = std::string()) {
   if (predictor == 3 && fmt != 3) throw std::runtime_error("predictor 3 needs floating-point samples");
   if (level <= 0) predictor = 1;
   const int bps = bits / 8;
@@ -535,16 +538,18 @@ void write(const std::string& path, const void* data, int nb, uint64_t H, uint64
   for (uint64_t i = 0; i < nchunk; ++i) cnts[i] = striped ? strip_bytes(i) : enc[i].size();
   write_chunks(path, nb, H, W, bits, fmt, striped ? 0u : tile, rps, level > 0 ? 8 : 1, predictor, cnts,
                [&](uint64_t i) { return striped ? strip_ptr(i) : enc[i].data(); }, nthreads, gt, epsg, citation,
-               nodata, force_big);
+               nodata, force_big, metadata);
 }
 
 // The file of a raster whose chunks (tiles, or strips when tile == 0) are
 // already encoded: header, chunk payloads (parallel pwrite), IFD with the
-// GeoTIFF tags.  comp: TIFF compression tag (1 / 8).
+// GeoTIFF tags.  comp: TIFF compression tag (1 / 8).  metadata: the text of
+// tag 42112 (GDAL_METADATA: the scale and offset of scaled integer samples).
 void write_chunks(const std::string& path, int nb, uint64_t H, uint64_t W, int bits, int fmt, uint32_t tile,
                   uint64_t rps, int comp, int predictor, const std::vector<uint64_t>& cnts,
                   const std::function<const uint8_t*(uint64_t)>& chunk, int nthreads, const std::vector<double>& gt,
-                  int epsg, const std::string& citation, const std::string& nodata, int force_big) {
+                  int epsg, const std::string& citation, const std::string& nodata, int force_big,
+                  const std::string& metadata) {
   const bool striped = tile == 0;
   const uint64_t nchunk = cnts.size();
   std::vector<uint64_t> offs(nchunk);
@@ -604,6 +609,7 @@ void write_chunks(const std::string& path, int nb, uint64_t H, uint64_t W, int b
     tags.push_back(mk<uint16_t>(34735, 3, keys));
     tags.push_back(mk_ascii(34737, cit));
   }
+  if (!metadata.empty()) tags.push_back(mk_ascii(42112, metadata));
   if (!nodata.empty()) tags.push_back(mk_ascii(42113, nodata));
   std::sort(tags.begin(), tags.end(), [](const Tag& a, const Tag& b) { return a.tag < b.tag; });
   // IFD after the data; out-of-line values after the IFD
@@ -693,6 +699,7 @@ void bind_tiff(py::module_& m) {
     d["geokeys"] = in.geokeys;
     d["geo_ascii"] = in.ascii;
     d["nodata"] = in.nodata;
+    d["gdal_metadata"] = in.metadata;
     d["n_chunks"] = in.off.size();
     return d;
   });
@@ -733,27 +740,33 @@ void bind_tiff(py::module_& m) {
   m.def("tiff_write", [](const std::string& path, uintptr_t src, int nb, uint64_t H, uint64_t W, int bits, int fmt,
                          uint32_t tile, int level, int nthreads, const std::vector<double>& gt, int epsg,
                          const std::string& citation, const std::string& nodata, int force_big, int predictor,
-                         int strategy) {
+                         int strategy, const std::string& metadata) {
     py::gil_scoped_release nogil;
     tiff::write(path, reinterpret_cast<const void*>(src), nb, H, W, bits, fmt, tile, level, nthreads, gt, epsg,
-                citation, nodata, force_big, predictor, strategy);
+                citation, nodata, force_big, predictor, strategy, metadata);
   }, py::arg("path"), py::arg("src"), py::arg("nb"), py::arg("H"), py::arg("W"), py::arg("bits"), py::arg("fmt"),
      py::arg("tile"), py::arg("level"), py::arg("nthreads"), py::arg("gt"), py::arg("epsg"), py::arg("citation"),
-     py::arg("nodata"), py::arg("force_big"), py::arg("predictor") = 1, py::arg("strategy") = 0);
+     py::arg("nodata"), py::arg("force_big"), py::arg("predictor") = 1, py::arg("strategy") = 0,
+     py::arg("metadata") = std::string());
   // tiles already encoded (the device encoder, kf_deflate.hip): data + offsets[i]
   // holds sizes[i] bytes of tile i (row-major tiles of one band)
   m.def("tiff_write_tiles", [](const std::string& path, uintptr_t data, uint64_t H, uint64_t W, int bits, int fmt,
                                uint32_t tile, int comp, int predictor, const std::vector<uint64_t>& offsets,
                                const std::vector<uint64_t>& sizes, int nthreads, const std::vector<double>& gt,
-                               int epsg, const std::string& citation, const std::string& nodata, int force_big) {
+                               int epsg, const std::string& citation, const std::string& nodata, int force_big,
+                               const std::string& metadata) {
     const uint64_t n = ((W + tile - 1) / tile) * ((H + tile - 1) / tile);
     if (offsets.size() != n || sizes.size() != n) throw std::runtime_error("tiff_write_tiles: one offset and size per tile");
     if (tile == 0 || tile % 16) throw std::runtime_error("tiff_write_tiles: tile edge must be a multiple of 16");
     py::gil_scoped_release nogil;
     const uint8_t* base = reinterpret_cast<const uint8_t*>(data);
     tiff::write_chunks(path, 1, H, W, bits, fmt, tile, 0, comp, predictor, sizes,
-                       [&](uint64_t i) { return base + offsets[i]; }, nthreads, gt, epsg, citation, nodata, force_big);
-  });
+                       [&](uint64_t i) { return base + offsets[i]; }, nthreads, gt, epsg, citation, nodata, force_big,
+                       metadata);
+  }, py::arg("path"), py::arg("data"), py::arg("H"), py::arg("W"), py::arg("bits"), py::arg("fmt"), py::arg("tile"),
+     py::arg("comp"), py::arg("predictor"), py::arg("offsets"), py::arg("sizes"), py::arg("nthreads"), py::arg("gt"),
+     py::arg("epsg"), py::arg("citation"), py::arg("nodata"), py::arg("force_big"),
+     py::arg("metadata") = std::string());
 }
 
 }  // namespace kf

@@ -155,11 +155,28 @@ def _build(args, comm):
     else:
         projection, geotransform = info.get("projection", ""), info.get("geotransform", [0, 1, 0, 0, 0, -1])
     if args.out:
+        def _ranges(items, flag):
+            rg = {}
+            for name, lo, hi in items or []:
+                if name not in params:
+                    raise SystemExit(f"{flag} {name}: not a parameter of this run ({', '.join(params)})")
+                try:
+                    rg[name] = (float(lo), float(hi))
+                except ValueError:
+                    raise SystemExit(f"{flag} {name}: LO and HI are numbers")
+            return rg
+
+        scaled = {}
+        if args.out_sample == "uint16":
+            scaled = dict(sample_type="uint16", ranges=_ranges(args.out_range, "--out-range"),
+                          unc_ranges=_ranges(args.out_unc_range, "--out-unc-range"))
+        elif args.out_range or args.out_unc_range:
+            raise SystemExit("--out-range / --out-unc-range belong to --out-sample uint16")
         out = k.KafkaOutput(params, geotransform, projection,
                             args.out, prefix=args.prefix, level=args.out_level, gather=args.out_gather,
                             predictor=3 if args.out_fast else 1, strategy="rle" if args.out_fast else None,
                             keep_timesteps=args.out_keep, encoder=args.out_encoder,
-                            huffman=args.out_huffman)
+                            huffman=args.out_huffman, **scaled)
     else:
         out = k.DeviceOutput(params)
     kf = k.LinearKalman(obs, out, mask, factory, params, state_propagation=prop,
@@ -330,6 +347,15 @@ def main(argv=None):
     r.add_argument("--out-huffman", default="fixed", choices=["fixed", "dynamic"],
                    help="block type of the device encoder: fixed Huffman codes, or one Huffman table per tile "
                         "built on the GPU wherever that makes the tile smaller (never larger than fixed)")
+    r.add_argument("--out-sample", default="float32", choices=["float32", "uint16"],
+                   help="sample type of the output GeoTIFFs: float32, or uint16 = scaled 16-bit integers (predictor 2, "
+                        "nodata 65535, scale and offset in GDAL_METADATA); uint16 needs --out-range and "
+                        "--out-unc-range for every parameter")
+    r.add_argument("--out-range", nargs=3, action="append", default=None, metavar=("PARAM", "LO", "HI"),
+                   help="--out-sample uint16: the value range [LO, HI] of PARAM's mean raster (repeat per parameter); "
+                        "values outside are clamped and counted (writer_stats: saturated)")
+    r.add_argument("--out-unc-range", nargs=3, action="append", default=None, metavar=("PARAM", "LO", "HI"),
+                   help="--out-sample uint16: the same for PARAM's uncertainty raster")
     r.add_argument("--out-keep", type=int, default=None,
                    help="keep only the newest N timesteps' output files on local disk")
     r.add_argument("--out-gather", action="store_true", help="gather strips to rank 0 and write one raster")

@@ -118,18 +118,48 @@ class KafkaOutput:
     fixed-Huffman block per tile.  "dynamic": one Huffman table per tile, built
     on the device from the tile's token histogram, wherever that makes the
     tile smaller (never larger than "fixed"; the files decode the same).  The
-    host encoder has no such mode: "dynamic" with ``encoder="host"`` raises."""
+    host encoder has no such mode: "dynamic" with ``encoder="host"`` raises.
+
+    ``sample_type``: "float32" (default) or "uint16".  "uint16" writes every
+    raster as scaled 16-bit unsigned integers (predictor 2, nodata 65535 for
+    NaN, scale and offset in GDAL_METADATA: ``value = offset + scale *
+    sample``, ``tiff.read_tiff_scaled``) and needs ``ranges`` and
+    ``unc_ranges``: mappings parameter -> ``(lo, hi)`` for the mean and the
+    uncertainty rasters; the writer does not guess them.  The device encoder
+    quantises in its row load (csrc/kf_deflate.h: ``dfl_quantise``); with
+    ``encoder="host"`` (or CPU planes) the host runner of the same quantiser
+    produces the same samples and ``write_tiff`` encodes them.  Values outside
+    a range are clamped and counted: ``writer_stats()["saturated"]``."""
 
     def __init__(self, parameter_list, geotransform, projection, folder, prefix=None, fmt="GTiff",
                  compress="deflate", asynchronous=True, level: int = 6, tile: int = 256, gather: bool = False,
                  threads: int | None = None, predictor: int = 1, strategy: str | None = None,
-                 keep_timesteps: int | None = None, encoder: str = "auto", huffman: str = "fixed"):
+                 keep_timesteps: int | None = None, encoder: str = "auto", huffman: str = "fixed",
+                 sample_type: str = "float32", ranges=None, unc_ranges=None):
         if encoder not in ("auto", "device", "host"):
             raise ValueError("encoder must be 'auto', 'device' or 'host'")
         if huffman not in ("fixed", "dynamic"):
             raise ValueError("huffman must be 'fixed' or 'dynamic'")
         if huffman == "dynamic" and encoder == "host":
             raise ValueError("huffman='dynamic' is a mode of the device encoder (encoder='device' or 'auto')")
+        if sample_type not in ("float32", "uint16"):
+            raise ValueError("sample_type must be 'float32' or 'uint16'")
+        self.sample_type = sample_type
+        self._ranges = None       # uint16: ((lo, hi) per parameter) of the mean and of the unc rasters
+        if sample_type == "uint16":
+            both = []
+            for name, rg in (("ranges", ranges), ("unc_ranges", unc_ranges)):
+                missing = [p for p in parameter_list if rg is None or p not in rg]
+                if missing:
+                    raise ValueError(f"sample_type='uint16' needs {name}[param] = (lo, hi); missing: "
+                                     + ", ".join(str(p) for p in missing))
+                both.append([(float(rg[p][0]), float(rg[p][1])) for p in parameter_list])
+                K.TileEncoder.quantiser(both[-1])       # hi <= lo or non-finite bounds: ValueError
+            self._ranges = tuple(both)
+        elif ranges is not None or unc_ranges is not None:
+            raise ValueError("ranges / unc_ranges belong to sample_type='uint16'")
+        self.saturated = 0        # uint16: samples clamped to their range so far
+        self.saturated_last = {}  # ... per file (base name) of the last timestep written
         self.encoder = encoder
         self.huffman = huffman
         self._enc = None          # ops.kernels.TileEncoder (device encoder)
@@ -181,15 +211,31 @@ class KafkaOutput:
     def _write_all(self, timestep, mean, unc, gt, prefix):
         t0 = time.perf_counter()
         names = []
-        for planes, suffix in ((mean, ""), (unc, "_unc")):
+        u16 = self.sample_type == "uint16"
+        sat_last = {}
+        for kind, (planes, suffix) in enumerate(((mean, ""), (unc, "_unc"))):
+            if u16:
+                # the host runner of the device encoder's quantiser: the same samples on both paths
+                rg = self._ranges[kind]
+                _, _, scale, offset = K.TileEncoder.quantiser(rg)
+                planes, sat = K.quantise_u16(np.ascontiguousarray(planes, dtype=np.float32), rg)
             for ii, param in enumerate(self.parameter_list):
                 fn = _fname(self.folder, param, timestep, prefix, suffix)
-                write_tiff(fn, planes[ii], gt, self.projection, self.compress, level=self.level, tile=self.tile,
-                           threads=self.threads, predictor=self.predictor, strategy=self.strategy)
+                if u16:
+                    write_tiff(fn, planes[ii], gt, self.projection, self.compress, level=self.level, tile=self.tile,
+                               threads=self.threads, predictor=2, strategy=self.strategy, nodata=65535,
+                               scale=scale[ii], offset=offset[ii])
+                    sat_last[os.path.basename(fn)] = int(sat[ii])
+                    self.saturated += int(sat[ii])
+                else:
+                    write_tiff(fn, planes[ii], gt, self.projection, self.compress, level=self.level, tile=self.tile,
+                               threads=self.threads, predictor=self.predictor, strategy=self.strategy)
                 self.written.append(fn)
                 names.append(fn)
                 self.bytes_in += planes[ii].nbytes
                 self.bytes_out += os.path.getsize(fn)
+        if u16:
+            self.saturated_last = sat_last
         self.write_s.append(time.perf_counter() - t0)
         self._prune(names)
 
@@ -215,7 +261,9 @@ class KafkaOutput:
                "raster_bytes": self.bytes_in, "file_bytes": self.bytes_out,
                "ratio": round(self.bytes_in / self.bytes_out, 3) if self.bytes_out else None,
                "slot_wait_s": round(self.slot_wait_s, 6), "d2h_s": round(self.d2h_s, 6),
-               "prune_s": round(self.prune_s, 6), "deflate_backend": self.deflate_backend()}
+               "prune_s": round(self.prune_s, 6), "deflate_backend": self.deflate_backend(),
+               "sample_type": self.sample_type,
+               "saturated": {"total": int(self.saturated), "last": dict(self.saturated_last)}}
         if w is not None:
             out.update({"queue_depth_last": w.depth[-1] if w.depth else 0,
                         "queue_depth_max": max(w.depth) if w.depth else 0,
@@ -227,14 +275,15 @@ class KafkaOutput:
         host has it) or zlib (always for the rle / huffman strategies)."""
         if self.compress != "deflate":
             return None
+        u16 = ", uint16 samples" if self.sample_type == "uint16" else ""
         if self._eslots:
-            return f"device ({self.huffman}-Huffman run-length zlib streams, kf_deflate.hip)"
+            return f"device ({self.huffman}-Huffman run-length zlib streams{u16}, kf_deflate.hip)"
         from .tiff import _native
         E = _native()
         if E is None or not self.tile:
-            return "zlib (python)"
+            return "zlib (python)" + u16
         fast = hasattr(E, "tiff_fast_deflate") and bool(E.tiff_fast_deflate())
-        return "libdeflate" if fast and self.strategy in (None, "default") else "zlib"
+        return ("libdeflate" if fast and self.strategy in (None, "default") else "zlib") + u16
 
     # ------------------------------------------------------- device path
     def device_targets(self, engine, dev, alias: bool = True):
@@ -324,27 +373,35 @@ class KafkaOutput:
         the writer thread then copies exactly the compressed bytes and writes
         the files (no encode on the host)."""
         from ..ops.kernels import TileEncoder
-        from ..ops import _ext
         dev = mean_d.device
         if self._stream is None:
             self._stream = torch.cuda.Stream(dev)
         if self._enc is None:
-            self._enc = TileEncoder(huffman=self.huffman)
+            self._enc = TileEncoder(huffman=self.huffman, sample=self.sample_type)
+        u16 = self.sample_type == "uint16"
         tx, ty = TileEncoder.tiles(H, W)
         per = tx * ty
         nt = n * per
-        bound = int(_ext.require_ext().DFL_BOUND)
+        bound = self._enc.bound()
         # pinned host bytes for the compressed tiles: allocated with the slot (a
         # multi-GB pinned allocation in the writer thread would stall a timed
         # date), sized for the raw planes plus the fixed-Huffman worst case
-        host_bytes = int(2 * n * H * W * 4 * 1.13) + 2 * nt * 64 + (1 << 20)
-        packed, meta_h, host_box, done = self._next_enc_slot(2 * nt * bound, 4 * nt, dev, host_bytes)
+        host_bytes = int(2 * n * H * W * (2 if u16 else 4) * 1.13) + 2 * nt * 64 + (1 << 20)
+        # meta: sizes and offsets of both rasters' tiles, then (uint16) the planes' saturation counts
+        meta_n = 4 * nt + (2 * n if u16 else 0)
+        packed, meta_h, host_box, done = self._next_enc_slot(2 * nt * bound, meta_n, dev, host_bytes)
         done.clear()
         self._stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(self._stream):
-            _, sm, om = self._enc.encode(mean_d, H, W, packed=packed)
-            _, su, ou = self._enc.encode(unc_d, H, W, packed=packed, base=om[-1:] + sm[-1:])
-            meta_h.copy_(torch.cat([sm, om, su, ou]), non_blocking=True)
+            if u16:
+                _, sm, om, qm = self._enc.encode(mean_d, H, W, packed=packed, ranges=self._ranges[0])
+                _, su, ou, qu = self._enc.encode(unc_d, H, W, packed=packed, base=om[-1:] + sm[-1:],
+                                                 ranges=self._ranges[1])
+                meta_h.copy_(torch.cat([sm, om, su, ou, qm, qu]), non_blocking=True)
+            else:
+                _, sm, om = self._enc.encode(mean_d, H, W, packed=packed)
+                _, su, ou = self._enc.encode(unc_d, H, W, packed=packed, base=om[-1:] + sm[-1:])
+                meta_h.copy_(torch.cat([sm, om, su, ou]), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._stream)
         mean_d.record_stream(self._stream)
@@ -367,8 +424,8 @@ class KafkaOutput:
             try:
                 t0 = time.perf_counter()
                 ev.synchronize()
-                m = meta_h.numpy().reshape(4, nt).copy()
-                total = int(m[3, -1] + m[2, -1])
+                m = meta_h.numpy().copy()
+                total = int(m[4 * nt - 1] + m[3 * nt - 1])
                 host = host_box[0]
                 if host is None or host.numel() < total:
                     host = host_box[0] = torch.empty(int(total * 1.25) + 4096, dtype=torch.uint8, pin_memory=True)
@@ -395,17 +452,31 @@ class KafkaOutput:
         from .tiff import write_tiff_tiles
         t0 = time.perf_counter()
         names = []
-        sm, om, su, ou = meta
-        for sizes, offs, suffix in ((sm, om, ""), (su, ou, "_unc")):
+        nt = n * per
+        sm, om, su, ou = meta[:4 * nt].reshape(4, nt)
+        u16 = self.sample_type == "uint16"
+        sat_last = {}
+        for kind, (sizes, offs, suffix) in enumerate(((sm, om, ""), (su, ou, "_unc"))):
+            if u16:
+                _, _, scale, offset = K.TileEncoder.quantiser(self._ranges[kind])
+                sat = meta[4 * nt + kind * n:4 * nt + (kind + 1) * n]
             for ii, param in enumerate(self.parameter_list):
                 fn = _fname(self.folder, param, timestep, prefix, suffix)
                 sl = slice(ii * per, (ii + 1) * per)
-                write_tiff_tiles(fn, H, W, host, offs[sl], sizes[sl], gt, self.projection, predictor=3,
-                                 threads=self.threads)
+                if u16:
+                    write_tiff_tiles(fn, H, W, host, offs[sl], sizes[sl], gt, self.projection, threads=self.threads,
+                                     dtype="uint16", scale=scale[ii], offset=offset[ii])
+                    sat_last[os.path.basename(fn)] = int(sat[ii])
+                    self.saturated += int(sat[ii])
+                else:
+                    write_tiff_tiles(fn, H, W, host, offs[sl], sizes[sl], gt, self.projection, predictor=3,
+                                     threads=self.threads)
                 self.written.append(fn)
                 names.append(fn)
-                self.bytes_in += H * W * 4
+                self.bytes_in += H * W * (2 if u16 else 4)
                 self.bytes_out += os.path.getsize(fn)
+        if u16:
+            self.saturated_last = sat_last
         self.write_s.append(time.perf_counter() - t0)
         self._prune(names)
 

@@ -79,15 +79,40 @@ def epsg_of(projection) -> int:
     return 0
 
 
+def _scale_metadata(scale, offset) -> str:
+    """Text of TIFF tag 42112 (GDAL_METADATA) for ``value = offset + scale *
+    sample``; the values as ``repr(float)``, which round-trips exactly."""
+    if scale is None and offset is None:
+        return ""
+    sc, of = float(1.0 if scale is None else scale), float(0.0 if offset is None else offset)
+    return (f'<GDALMetadata><Item name="OFFSET" sample="0" role="offset">{of!r}</Item>'
+            f'<Item name="SCALE" sample="0" role="scale">{sc!r}</Item></GDALMetadata>')
+
+
+def _parse_scale_metadata(text) -> tuple:
+    """(scale, offset) of a tag 42112 text; None where the item is absent."""
+    out = []
+    for role in ("scale", "offset"):
+        m = re.search(r'<Item\b[^>]*\brole="%s"[^>]*>([^<]*)</Item>' % role, text or "")
+        try:
+            out.append(float(m.group(1)) if m else None)
+        except ValueError:
+            out.append(None)
+    return tuple(out)
+
+
 def write_tiff(path, array, geotransform=None, projection: str | None = None, compress: str | None = "deflate",
                rows_per_strip: int = 64, bigtiff: bool | None = None, nodata=None, tile: int | None = 256,
-               level: int = 6, threads: int | None = None, predictor: int = 1, strategy: str | None = None):
+               level: int = 6, threads: int | None = None, predictor: int = 1, strategy: str | None = None,
+               scale=None, offset=None):
     """Write a 2-D raster or a (bands, H, W) stack.  Native path: tiled
     (``tile`` px) DEFLATE, parallel compression, EPSG GeoKeys from
     ``projection``; ``tile=None`` (or no extension) writes the striped Python
     layout.  ``predictor`` 2 (integers) / 3 (floats) is the TIFF horizontal
     predictor; ``strategy`` "rle" / "huffman" selects the zlib strategy (about
-    3x faster encoding of float rasters at a similar ratio)."""
+    3x faster encoding of float rasters at a similar ratio).  ``scale`` /
+    ``offset``: written as GDAL_METADATA (tag 42112) for scaled integer
+    samples, ``value = offset + scale * sample`` (``read_tiff_scaled``)."""
     a = np.ascontiguousarray(np.asarray(array))
     if a.dtype == np.bool_:
         a = a.astype(np.uint8)
@@ -98,34 +123,48 @@ def write_tiff(path, array, geotransform=None, projection: str | None = None, co
         bits, fmt = _NATIVE_FMT[a.dtype]
         gt = [float(v) for v in geotransform] if geotransform is not None else []
         big = -1 if bigtiff is None else int(bool(bigtiff))
+        meta = _scale_metadata(scale, offset)
         E.tiff_write(str(path), planes.ctypes.data, nb, H, W, bits, fmt, int(tile),
                      level if compress == "deflate" else 0, threads or _threads(), gt, epsg_of(projection),
                      "" if projection is None else str(projection), "" if nodata is None else str(nodata), big,
-                     int(predictor), _STRATEGY[strategy])
+                     int(predictor), _STRATEGY[strategy], *([meta] if meta else []))
         return
-    _write_tiff_py(path, a, geotransform, projection, compress, rows_per_strip, bigtiff, nodata)
+    _write_tiff_py(path, a, geotransform, projection, compress, rows_per_strip, bigtiff, nodata, scale, offset)
 
 
 def write_tiff_tiles(path, H: int, W: int, data, offsets, sizes, geotransform=None, projection: str | None = None,
-                     nodata=None, predictor: int = 3, bigtiff: bool | None = None, threads: int | None = None,
-                     tile: int = 256):
-    """A float32 GeoTIFF from tiles already encoded as zlib streams
+                     nodata=None, predictor: int | None = None, bigtiff: bool | None = None,
+                     threads: int | None = None, tile: int = 256, dtype: str = "float32", scale=None, offset=None):
+    """A GeoTIFF from tiles already encoded as zlib streams
     (``ops.kernels.TileEncoder``: tile i's ``sizes[i]`` bytes at ``data`` +
-    ``offsets[i]``, row-major tiles); only the file layout is written here."""
+    ``offsets[i]``, row-major tiles); only the file layout is written here.
+    ``dtype``: "float32" (predictor 3 unless given) or "uint16" (the encoder's
+    ``sample="uint16"``: 16-bit unsigned samples, predictor 2, nodata 65535
+    unless given, ``scale`` / ``offset`` in GDAL_METADATA)."""
+    if dtype not in ("float32", "uint16"):
+        raise ValueError("dtype must be 'float32' or 'uint16'")
+    u16 = dtype == "uint16"
+    if not u16 and (scale is not None or offset is not None):
+        raise ValueError("scale / offset belong to dtype='uint16'")
+    if predictor is None:
+        predictor = 2 if u16 else 3
+    if u16 and nodata is None:
+        nodata = 65535
+    meta = _scale_metadata(scale, offset)
     E = _native()
     if E is None or not hasattr(E, "tiff_write_tiles"):
         raise RuntimeError("write_tiff_tiles needs the native extension")
     ptr = data.data_ptr() if hasattr(data, "data_ptr") else np.asarray(data).ctypes.data
     gt = [float(v) for v in geotransform] if geotransform is not None else []
     big = -1 if bigtiff is None else int(bool(bigtiff))
-    E.tiff_write_tiles(str(path), ptr, int(H), int(W), 32, 3, int(tile), 8, int(predictor),
-                       [int(v) for v in offsets], [int(v) for v in sizes], threads or _threads(), gt,
+    E.tiff_write_tiles(str(path), ptr, int(H), int(W), 16 if u16 else 32, 1 if u16 else 3, int(tile), 8,
+                       int(predictor), [int(v) for v in offsets], [int(v) for v in sizes], threads or _threads(), gt,
                        epsg_of(projection), "" if projection is None else str(projection),
-                       "" if nodata is None else str(nodata), big)
+                       "" if nodata is None else str(nodata), big, *([meta] if meta else []))
 
 
 def _write_tiff_py(path, array, geotransform=None, projection: str | None = None, compress: str | None = "deflate",
-                   rows_per_strip: int = 64, bigtiff: bool | None = None, nodata=None):
+                   rows_per_strip: int = 64, bigtiff: bool | None = None, nodata=None, scale=None, offset=None):
     a = np.ascontiguousarray(np.asarray(array))
     if a.ndim not in (2, 3):
         raise ValueError("write_tiff writes 2-D rasters or (bands, H, W) stacks")
@@ -157,6 +196,9 @@ def _write_tiff_py(path, array, geotransform=None, projection: str | None = None
         keys = [1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 1026, 34737, len(cit), 0]
         tags.append((34735, SHORT, keys))
         tags.append((34737, ASCII, cit))
+    meta = _scale_metadata(scale, offset)
+    if meta:
+        tags.append((42112, ASCII, meta))
     if nodata is not None:
         tags.append((42113, ASCII, str(nodata)))
     # data first, IFD after
@@ -219,6 +261,7 @@ def _geo_from_native(info) -> dict:
             out["epsg"] = int(keys[i + 3])
     if info["nodata"]:
         out["nodata"] = info["nodata"]
+    out["scale"], out["offset"] = _parse_scale_metadata(info.get("gdal_metadata", ""))
     return out
 
 
@@ -374,4 +417,26 @@ def _read_tiff_py(path):
         info["geotransform"] = [tp[3] - tp[0] * sx, sx, 0.0, tp[4] + tp[1] * sy, 0.0, -sy]
     if 34737 in tags:
         info["projection"] = tags[34737].rstrip("|")
+    if 42113 in tags and tags[42113]:
+        info["nodata"] = tags[42113]
+    info["scale"], info["offset"] = _parse_scale_metadata(tags.get(42112, ""))
     return arr.astype(dtype.newbyteorder("=")), info
+
+
+def read_tiff_scaled(path):
+    """-> (float32 array, info): the samples of a scaled integer raster as
+    values, ``offset + scale * sample`` (GDAL_METADATA, tag 42112; scale 1 and
+    offset 0 where absent), computed in float64; nodata samples are NaN."""
+    arr, info = read_tiff(path)
+    sc = info.get("scale")
+    of = info.get("offset")
+    out = (float(0.0 if of is None else of) + float(1.0 if sc is None else sc) * arr.astype(np.float64)).astype(np.float32)
+    nd = info.get("nodata")
+    if nd not in (None, ""):
+        try:
+            ndv = float(nd)
+        except ValueError:
+            ndv = None
+        if ndv is not None:
+            out[arr == ndv] = np.nan
+    return out, info

@@ -1320,20 +1320,52 @@ class TileEncoder:
     token histogram (same tokens) and writes a dynamic block wherever that is
     strictly smaller, else the fixed block: a tile is never larger than in
     the fixed mode.  The dynamic mode tokenises every row twice and needs the
-    larger row scratch (15 instead of 9 bits per byte), allocated only then."""
+    larger row scratch (15 instead of 9 bits per byte), allocated only then.
+
+    ``sample``: "float32" (default) or "uint16".  "uint16" quantises every
+    sample in the encoder's row load to a scaled 16-bit integer over the
+    plane's ``(lo, hi)`` range (``quantiser``; NaN -> 65535) and encodes the
+    tile under predictor 2: 512-byte rows, half the scratch and tile bound,
+    both Huffman modes; ``encode`` then also returns the clamped samples per
+    plane."""
 
     MODES = ("fixed", "dynamic")
+    SAMPLES = ("float32", "uint16")
 
-    def __init__(self, huffman: str = "fixed"):
+    def __init__(self, huffman: str = "fixed", sample: str = "float32"):
         if huffman not in self.MODES:
             raise ValueError("huffman must be 'fixed' or 'dynamic'")
+        if sample not in self.SAMPLES:
+            raise ValueError("sample must be 'float32' or 'uint16'")
         self.huffman = huffman
+        self.sample = sample
         self._bufs = {}
+        self._qab = {}            # uint16: device (a, b) arrays by range set
 
     @staticmethod
     def tiles(H: int, W: int) -> tuple[int, int]:
         t = int(ext().DFL_TILE)
         return -(-int(W) // t), -(-int(H) // t)
+
+    @staticmethod
+    def quantiser(ranges):
+        """(a, b, scale, offset) of the uint16 samples of rasters with the
+        ``(lo, hi)`` ranges: ``q = clamp(rint(fma(v, a, b)), 0, 65534)`` with
+        the float32 arrays a = 65534 / (hi - lo), b = -lo 65534 / (hi - lo)
+        (formed in float64, rounded once), and the float64 lists
+        scale = (hi - lo) / 65534, offset = lo a reader applies as
+        ``offset + scale * q``.  ``ValueError`` for hi <= lo or non-finite bounds."""
+        lo = np.array([float(r[0]) for r in ranges], dtype=np.float64)
+        hi = np.array([float(r[1]) for r in ranges], dtype=np.float64)
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+            raise ValueError("ranges: finite (lo, hi) bounds")
+        if not (hi > lo).all():
+            raise ValueError("ranges: hi must be above lo")
+        a = (65534.0 / (hi - lo)).astype(np.float32)
+        b = (-lo * 65534.0 / (hi - lo)).astype(np.float32)
+        if not (np.isfinite(a).all() and np.isfinite(b).all()):
+            raise ValueError("ranges: 65534 / (hi - lo) and lo 65534 / (hi - lo) must be finite float32 values")
+        return a, b, [float(v) for v in (hi - lo) / 65534.0], [float(v) for v in lo]
 
     def _buf(self, key, n, dtype, device):
         b = self._bufs.get(key)
@@ -1341,27 +1373,64 @@ class TileEncoder:
             b = self._bufs[key] = torch.empty(n, dtype=dtype, device=device)
         return b[:n]
 
-    def encode(self, planes: torch.Tensor, H: int, W: int, packed: torch.Tensor | None = None, base=None):
+    def bound(self) -> int:
+        """Bytes reserved per encoded tile (the fixed-Huffman worst case)."""
+        return int(ext().DFL_BOUND16 if self.sample == "uint16" else ext().DFL_BOUND)
+
+    def encode(self, planes: torch.Tensor, H: int, W: int, packed: torch.Tensor | None = None, base=None,
+               ranges=None):
         """``packed``: the output buffer (default: the encoder's own); ``base``:
         an int64 scalar tensor added to the offsets (several rasters packed
-        into one buffer back to back, device-side: no host read-back)."""
+        into one buffer back to back, device-side: no host read-back).
+
+        ``sample="uint16"``: ``ranges`` = one ``(lo, hi)`` per plane (required;
+        rejected for float32).  The tiles then hold scaled 16-bit samples under
+        predictor 2 (``quantiser``; NaN -> 65535), and a fourth value comes
+        back: the int64 count per plane of the samples that were clamped, on
+        the planes' device."""
         if planes.dtype != torch.float32 or planes.dim() != 2 or planes.stride(1) != 1:
             raise ValueError("planes: [n, ld] float32 with unit column stride")
         n, ld = planes.shape
         if H * W > ld:
             raise ValueError(f"plane of {ld} values holds no {H} x {W} raster")
+        u16 = self.sample == "uint16"
+        if u16 and ranges is None:
+            raise ValueError("sample='uint16' needs ranges: one (lo, hi) per plane")
+        if not u16 and ranges is not None:
+            raise ValueError("ranges belong to sample='uint16'")
         tx, ty = self.tiles(H, W)
         nt = n * tx * ty
-        bound = int(ext().DFL_BOUND)
+        bound = self.bound()
         dev = planes.device
+        qa = qb = sat = None
+        if u16:
+            if len(ranges) != n:
+                raise ValueError(f"{len(ranges)} ranges for {n} planes")
+            a, b, _, _ = self.quantiser(ranges)
+            key = (a.tobytes(), b.tobytes(), dev)
+            qab = self._qab.get(key)               # the same few ranges every date: one upload each
+            if qab is None:
+                if len(self._qab) >= 16:
+                    self._qab.clear()
+                qab = self._qab[key] = torch.from_numpy(np.stack([a, b])).to(dev)
+            qa, qb = qab[0], qab[1]
+            sat = torch.zeros(n, dtype=torch.int32, device=dev)    # uint32 counts
         scratch = self._buf("scratch", nt * bound, torch.uint8, dev)
         sizes = self._buf("sizes", nt, torch.int32, dev)        # uint32 byte counts (< 2^31)
         dyn = self.huffman == "dynamic"
-        row_bytes = int(ext().DFL_ROW_SCRATCH_DYN if dyn else ext().DFL_ROW_SCRATCH)
+        if u16:
+            row_bytes = int(ext().DFL_ROW_SCRATCH16_DYN if dyn else ext().DFL_ROW_SCRATCH16)
+        else:
+            row_bytes = int(ext().DFL_ROW_SCRATCH_DYN if dyn else ext().DFL_ROW_SCRATCH)
         rows = self._buf("rows", nt * row_bytes, torch.uint8, dev) if _dev(planes) else None
-        ext().deflate_tiles(_ptr(planes), planes.stride(0), int(H), int(W), int(n), _ptr(scratch), _ptr(sizes),
-                            _dev(planes), _stream(planes), _ptr(rows),
-                            int(ext().DFL_MODE_DYNAMIC if dyn else ext().DFL_MODE_FIXED))
+        mode = int(ext().DFL_MODE_DYNAMIC if dyn else ext().DFL_MODE_FIXED)
+        if u16:
+            ext().deflate_tiles(_ptr(planes), planes.stride(0), int(H), int(W), int(n), _ptr(scratch), _ptr(sizes),
+                                _dev(planes), _stream(planes), _ptr(rows), mode, int(ext().DFL_FMT_U16), _ptr(qa),
+                                _ptr(qb), _ptr(sat))
+        else:
+            ext().deflate_tiles(_ptr(planes), planes.stride(0), int(H), int(W), int(n), _ptr(scratch), _ptr(sizes),
+                                _dev(planes), _stream(planes), _ptr(rows), mode)
         s64 = sizes.to(torch.int64)
         offs = torch.cumsum(s64, 0) - s64
         if base is not None:
@@ -1374,9 +1443,31 @@ class TileEncoder:
             dst = packed.numpy()
             for i in range(nt):
                 dst[of[i]:of[i] + sz[i]] = src[i, :sz[i]]
-            return packed, s64, offs
-        ext().deflate_pack(_ptr(scratch), _ptr(sizes), _ptr(offs), _ptr(packed), nt, _stream(planes))
+        else:
+            ext().deflate_pack(_ptr(scratch), _ptr(sizes), _ptr(offs), _ptr(packed), nt, _stream(planes), bound)
+        if u16:
+            return packed, s64, offs, sat.to(torch.int64) & 0xFFFFFFFF
         return packed, s64, offs
+
+
+def quantise_u16(planes, ranges):
+    """Host runner of the ``TileEncoder(sample="uint16")`` quantiser on CPU
+    planes [n, ld] (or [n, H, W]) float32 -> (uint16 array of the same shape,
+    saturated samples per plane): the samples the device encoder writes."""
+    p = planes if isinstance(planes, torch.Tensor) else torch.from_numpy(np.require(planes, np.float32, ["C", "W"]))
+    if p.is_cuda or p.dtype != torch.float32:
+        raise ValueError("quantise_u16: float32 CPU planes")
+    p = p.contiguous()
+    n = p.shape[0]
+    if len(ranges) != n:
+        raise ValueError(f"{len(ranges)} ranges for {n} planes")
+    a, b, _, _ = TileEncoder.quantiser(ranges)
+    per = p[0].numel() if n else 0
+    out = np.empty(tuple(p.shape), dtype=np.uint16)
+    sat = np.zeros(n, dtype=np.uint32)
+    if per:
+        ext().quantise_u16(p.data_ptr(), per, per, n, a.ctypes.data, b.ctypes.data, out.ctypes.data, sat.ctypes.data)
+    return out, sat.astype(np.int64)
 
 
 class TileDecoder:

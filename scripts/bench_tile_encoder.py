@@ -16,6 +16,14 @@ planes of an input.  One JSON line per raster, one per input and a total.
 
     python scripts/bench_tile_encoder.py dump/output_mean.npy dump/output_unc.npy
     python scripts/bench_tile_encoder.py out/*_A2017017*.tif --crop 3882 --device cuda
+
+``--sample uint16 --range LO HI`` adds the scaled 16-bit format
+(``TileEncoder(sample="uint16")``, predictor 2) next to the float32 numbers of
+the same run: bytes, bytes per pixel, ratio against the float32 raster and the
+event-timed encode, with the samples the range clamped (``saturated``).  One
+``--range`` serves every input; repeated, they go to the inputs in order.
+
+    python scripts/bench_tile_encoder.py out/TeLAI_A2017017.tif --sample uint16 --range 0 8
 """
 from __future__ import annotations
 
@@ -81,16 +89,18 @@ def zlib_bytes(plane):
     return out
 
 
-def encode(planes, device, reps):
-    """-> {mode: (per-plane bytes, ms per encode of all planes or None)}"""
+def encode(planes, device, reps, sample="float32", rng=None):
+    """-> {mode: (per-plane bytes, ms per encode of all planes or None[, saturated per plane])}"""
     n, H, W = planes.shape
     t = torch.from_numpy(planes.reshape(n, -1)).to(device)
     tiles = TileEncoder.tiles(H, W)
     per = tiles[0] * tiles[1]
     res = {}
+    kw = {"ranges": [tuple(rng)] * n} if sample == "uint16" else {}
     for mode in TileEncoder.MODES:
-        enc = TileEncoder(huffman=mode)
-        _, sizes, _ = enc.encode(t, H, W)
+        enc = TileEncoder(huffman=mode, sample=sample)
+        first = enc.encode(t, H, W, **kw)
+        sizes = first[1]
         ms = None
         if t.is_cuda:
             torch.cuda.synchronize()
@@ -98,12 +108,13 @@ def encode(planes, device, reps):
             for _ in range(reps):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                enc.encode(t, H, W)
+                enc.encode(t, H, W, **kw)
                 e1.record()
                 e1.synchronize()
                 times.append(e0.elapsed_time(e1))
             ms = [round(x, 3) for x in sorted(times)]
-        res[mode] = (sizes.cpu().numpy().reshape(n, per).sum(1), ms)
+        res[mode] = (sizes.cpu().numpy().reshape(n, per).sum(1), ms) + \
+            ((first[3].cpu().numpy(),) if sample == "uint16" else ())
     return res
 
 
@@ -115,32 +126,58 @@ def main():
     ap.add_argument("--crop", type=int, default=0, help="central crop x crop window of every raster (0: all of it)")
     ap.add_argument("--reps", type=int, default=5, help="timed encodes per mode (GPU)")
     ap.add_argument("--no-zlib", action="store_true", help="skip the zlib columns")
+    ap.add_argument("--sample", default="float32", choices=["float32", "uint16"],
+                    help="uint16: also encode the rasters as scaled 16-bit samples (needs --range)")
+    ap.add_argument("--range", nargs=2, type=float, action="append", default=None, metavar=("LO", "HI"),
+                    help="--sample uint16: the value range; once for all inputs, or once per input in order")
     a = ap.parse_args()
-    keys = ("raw", "fixed", "dynamic", "zlib1", "zlib1_rle")
+    u16 = a.sample == "uint16"
+    if u16 and (not a.range or len(a.range) not in (1, len(a.inputs))):
+        ap.error("--sample uint16 needs --range LO HI, once or once per input")
+    keys = ("raw", "fixed", "dynamic", "zlib1", "zlib1_rle") + (("u16_fixed", "u16_dynamic") if u16 else ())
     total = dict.fromkeys(keys, 0)
-    for path in a.inputs:
+    pixels = saturated = 0
+    for k_in, path in enumerate(a.inputs):
         planes, note = load(path, a.width, a.crop)
         n, H, W = planes.shape
         res = encode(planes, torch.device(a.device), a.reps)
+        rng = a.range[k_in % len(a.range)] if u16 else None
+        res16 = encode(planes, torch.device(a.device), a.reps, "uint16", rng) if u16 else None
         tx, ty = TileEncoder.tiles(H, W)
         sub = dict.fromkeys(keys, 0)
         for p in range(n):
             z = [0, 0] if a.no_zlib else zlib_bytes(planes[p])
             rec = {"raw": H * W * 4, "fixed": int(res["fixed"][0][p]),
                    "dynamic": int(res["dynamic"][0][p]), "zlib1": z[0], "zlib1_rle": z[1]}
+            if u16:
+                rec.update({"u16_fixed": int(res16["fixed"][0][p]), "u16_dynamic": int(res16["dynamic"][0][p])})
             for key in keys:
                 sub[key] += rec[key]
             print(json.dumps({"input": os.path.basename(path), "plane": p, "shape": [H, W], **rec,
-                              **{f"ratio_{m}": round(rec["raw"] / rec[m], 4) for m in keys[1:] if rec[m]}}))
+                              **{f"ratio_{m}": round(rec["raw"] / rec[m], 4) for m in keys[1:] if rec[m]},
+                              **({"range": list(rng), "saturated": int(res16["fixed"][2][p]),
+                                  **{f"bytes_per_px_{m}": round(rec[m] / (H * W), 4)
+                                     for m in ("fixed", "dynamic", "u16_fixed", "u16_dynamic")}} if u16 else {})}))
+            if u16:
+                saturated += int(res16["fixed"][2][p])
+        pixels += n * H * W
         for key in keys:
             total[key] += sub[key]
         print(json.dumps({"input": os.path.basename(path), "planes": n, "shape": [H, W], **sub,
                           **{f"ratio_{m}": round(sub["raw"] / sub[m], 4) for m in keys[1:] if sub[m]},
                           "encode_ms_fixed": res["fixed"][1], "encode_ms_dynamic": res["dynamic"][1],
+                          **({"encode_ms_u16_fixed": res16["fixed"][1], "encode_ms_u16_dynamic": res16["dynamic"][1],
+                              "range": list(rng)} if u16 else {}),
                           **({"note": note} if note else {})}))
     print(json.dumps({"total": True, **total,
                       **{f"ratio_{m}": round(total["raw"] / total[m], 4) for m in keys[1:] if total[m]},
-                      "dynamic_over_fixed": round(total["dynamic"] / total["fixed"], 4)}))
+                      "dynamic_over_fixed": round(total["dynamic"] / total["fixed"], 4),
+                      **({"saturated": saturated, "pixels": pixels,
+                          **{f"bytes_per_px_{m}": round(total[m] / pixels, 4)
+                             for m in ("fixed", "dynamic", "u16_fixed", "u16_dynamic")},
+                          "float32_over_u16_fixed": round(total["fixed"] / total["u16_fixed"], 4),
+                          "float32_over_u16_dynamic": round(total["dynamic"] / total["u16_dynamic"], 4)}
+                         if u16 else {})}))
 
 
 if __name__ == "__main__":
