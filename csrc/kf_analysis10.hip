@@ -5,10 +5,13 @@
 
 namespace kf {
 
-hipError_t dev_analysis_np10(const AnalysisArgs& a, int grid, hipStream_t s, int* n_part) {
-  l_analysis<10>(a, grid, s, n_part);
-  return hipGetLastError();
+static const LaunchRow<AnalysisArgs> k1_rows[] = {KF_K1_ROWS_10};
+
+hipError_t dev_analysis_np10(const AnalysisArgs& a, int grid, hipStream_t s) {
+  return launch_plan(k1_rows, analysis_plan(10, a), a, grid, s);
 }
+
+void launch_table_np10(std::vector<KernelPlan>& out) { table_plans(k1_rows, out); }
 
 #ifdef KF_PHASE_CLOCKS
 // the phase counters of this translation unit's (10-parameter) analysis kernels

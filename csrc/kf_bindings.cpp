@@ -29,6 +29,17 @@ static void check_host(int rc, const char* what) {
   if (rc != 0) throw std::runtime_error(std::string(what) + ": unsupported n_params on host runner");
 }
 
+// a KernelPlan (kf_plan.h) as a dict: its kernel's template-id, the template's name and the fields
+static py::dict plan_dict(const KernelPlan& p) {
+  const std::string name = plan_name(p);
+  py::dict d;
+  d["name"] = name;
+  d["family"] = name.substr(0, name.find('<'));
+  d["np"] = p.np, d["fd"] = p.fd, d["obs"] = p.obs, d["bs"] = p.bs, d["minw"] = p.minw, d["layout"] = p.layout;
+  d["il"] = p.il, d["spec"] = p.spec, d["mixlo"] = p.mixlo, d["pf"] = p.pf, d["rows"] = p.rows, d["out"] = p.out;
+  return d;
+}
+
 template <typename A, size_t N>
 static void set_arr(A (&dst)[N], const std::vector<A>& v, const char* name) {
   if (v.size() > N) throw std::runtime_error(std::string(name) + " too long");
@@ -317,6 +328,16 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
   }, py::arg("n_params") = 7, py::arg("reset") = false);
 #endif
   m.def("set_gp_unroll", [](int n) { set_gp_unroll(n); });
+
+  // the kernel a device launch of these arguments takes (kf_plan.h; family "NONE": the launch raises);
+  // no device needed.  launch_table: the names of every line of the launchers' tables
+  m.def("analysis_plan", [](int np, const AnalysisArgs& a) { return plan_dict(analysis_plan(np, a)); });
+  m.def("gain_plan", [](int np, const GainArgs& a) { return plan_dict(gain_plan(np, a)); });
+  m.def("launch_table", []() {
+    std::vector<std::string> names;
+    for (const KernelPlan& p : dev_launch_table()) names.push_back(plan_name(p));
+    return names;
+  });
 
   // -> norm partial entries written (device: workgroups or 64-slot tiles; host: workgroups)
   m.def("analysis", [](int np, const AnalysisArgs& a, int grid, bool device, uintptr_t stream) {

@@ -309,7 +309,7 @@ enum AnalysisVariant : int32_t {
   AV_BLOCK_ORDER = 16,       // exponent MFMAs block by block (gpm_il_default's other order)
   AV_GENERIC_SPEC = 18,      // fused forecast through the generic launch instead of SPEC_PROP
   AV_DENSE_SOLVE = 20,       // the dense solve where a_struct would select the structure-aware kernels / host path
-  AV_MIXLO_SPLIT = 22,       // lo half of m by v_fma_mixlo/mixhi_f16 (gpm_exp_split MIXLO; kf_device.h mixlo_split_analysis)
+  AV_MIXLO_SPLIT = 22,       // lo half of m by v_fma_mixlo/mixhi_f16 (gpm_exp_split MIXLO; kf_plan.h analysis_plan)
   AV_LOOPED_TIP = 24         // the SPEC_PROP_TIP kernels where the launch has the straight-line kernel's shape (TipConst)
 };
 
@@ -1698,7 +1698,7 @@ struct GainArgs {
   // host hint as AnalysisArgs.band_layout (BAND_LAYOUT_SHARED_X: one exponent
   // operand per iteration in the global-table kernel); 0: runtime
   int32_t band_layout;
-  int32_t split_mixlo;   // 1: AV_MIXLO_SPLIT's kernels (kf_device.h mixlo_split_gain)
+  int32_t split_mixlo;   // 1: AV_MIXLO_SPLIT's kernels (kf_plan.h gain_plan)
 };
 
 KF_HD int64_t visit_count(const GainArgs& a) { return visit_bounded(a.n_visit, a.N, a.n_visit_dev); }
@@ -2767,5 +2767,17 @@ KF_HD bool gp_hessian_dispatch(const BandDesc& bd, const float (&x)[NP], float& 
     return false;
   }
 }
+
+// Sizes of the matrix-core GP tables (kf_gp_mfma.h), shared with the host-side
+// kernel choice (kf_plan.h).
+// exponent K steps of 16 slots (3D + 2 used)
+KF_HD constexpr int gpm_k_steps(int D) { return (3 * D + 2 + 15) / 16; }
+// sums fragments per (q, h): the lanes whose row is used (hi and lo rows)
+KF_HD constexpr int gpm_sum_rows(int D) { return 2 * (D + 1); }
+// 16-byte fragments per 32-point chunk
+KF_HD constexpr int gpm_frags_per_chunk(int D) { return 64 * gpm_k_steps(D) + 4 * gpm_sum_rows(D); }
+constexpr int GPM_MAX_D = 10;
+// bands whose sums are held across the record loops (larger tables fall back to VALU)
+constexpr int GPM_MAX_BANDS = 4;
 
 }  // namespace kf

@@ -242,36 +242,6 @@ __global__ __launch_bounds__(BLOCK, 3) void analysis_tip_sl_kernel(AnalysisArgs 
 #endif
 }
 
-template <typename K>
-static void gpm_lds_attr(K kernel, size_t bytes);
-
-template <int ROWS, int OUT>
-static void launch_tip_sl(size_t lds, const AnalysisArgs& a, int grid, hipStream_t s, int* n_part) {
-  constexpr bool IL = true;   // gpm_il_default<7, BAND_LAYOUT_TIP>()
-  gpm_lds_attr(analysis_tip_sl_kernel<IL, ROWS, OUT>, lds);
-  *n_part = grid;
-  hipLaunchKernelGGL((analysis_tip_sl_kernel<IL, ROWS, OUT>), dim3(grid), dim3(BLOCK), lds, s, a);
-}
-
-static bool l_analysis_tip_sl(size_t lds, const AnalysisArgs& a, int grid, hipStream_t s, int* n_part) {
-#define KF_TIP_SL_GO(R_, O_)                               \
-  if (a.tc.rows == R_ && a.tc.out == O_) {                 \
-    launch_tip_sl<R_, O_>(lds, a, grid, s, n_part);        \
-    return true;                                           \
-  }
-  KF_TIP_SL_GO(TIP_ROWS_NONE, TIP_OUT_NONE)
-  KF_TIP_SL_GO(TIP_ROWS_NONE, TIP_OUT_UNC)
-  KF_TIP_SL_GO(TIP_ROWS_NONE, TIP_OUT_MEAN)
-  KF_TIP_SL_GO(TIP_ROWS_DIAG, TIP_OUT_NONE)
-  KF_TIP_SL_GO(TIP_ROWS_DIAG, TIP_OUT_UNC)
-  KF_TIP_SL_GO(TIP_ROWS_DIAG, TIP_OUT_MEAN)
-  KF_TIP_SL_GO(TIP_ROWS_ALL, TIP_OUT_NONE)
-  KF_TIP_SL_GO(TIP_ROWS_ALL, TIP_OUT_UNC)
-  KF_TIP_SL_GO(TIP_ROWS_ALL, TIP_OUT_MEAN)
-#undef KF_TIP_SL_GO
-  return false;
-}
-
 // K1 on the matrix cores with every band's table read from global memory
 // (gp_mfma_sums_g): many-band GP states (PROSAIL: ten bands, 358-716 KiB of
 // tables) whose tables exceed the LDS.  No LDS, so the waves per SIMD follow
@@ -314,15 +284,6 @@ __global__ __launch_bounds__(BLOCK, 2) void analysis_mfma_g_kernel(AnalysisArgs 
 template <int NP, int D, int FOBS, bool PF = false, bool IL = false, int SPEC = SPEC_ANY>
 __global__ __launch_bounds__(BLOCK, 2) void analysis_mfma_g_mixlo_kernel(AnalysisArgs a) {
   analysis_mfma_g_body<NP, D, FOBS, PF, IL, SPEC, true>(a);
-}
-
-// dynamic LDS above the 64 KiB default (tables of several bands, up to the
-// 160 KiB of a gfx950 CU)
-template <typename K>
-static void gpm_lds_attr(K kernel, size_t bytes) {
-  if (bytes > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)bytes);
 }
 
 // K1g with the GP on the matrix cores (JRC-TIP: tables staged in LDS once per
@@ -428,55 +389,6 @@ __global__ __launch_bounds__(BLOCK) void gain_kernel(GainArgs a) {
   }
   if (a.partials_first) block_partials2<BLOCK>(acc, acc1, a.partials, a.partials_first);
   else if (a.partials) block_partial(acc, a.partials);
-}
-
-// K1g launch: the all-GP fast instantiations (as l_analysis) or the generic kernel.
-template <int NP>
-static void l_gain(const GainArgs& a, int grid, hipStream_t s) {
-#define KF_GAIN_FAST(D_)                                                                                 \
-  if (a.fast_d == D_) {                                                                                 \
-    if (a.fast_obs == OBS_DN16) {                                                                       \
-      hipLaunchKernelGGL((gain_kernel<NP, D_, OBS_DN16>), dim3(grid), dim3(BLOCK), 0, s, a);            \
-      return;                                                                                           \
-    }                                                                                                   \
-    if (a.fast_obs == OBS_F32) {                                                                        \
-      hipLaunchKernelGGL((gain_kernel<NP, D_, OBS_F32>), dim3(grid), dim3(BLOCK), 0, s, a);             \
-      return;                                                                                           \
-    }                                                                                                   \
-  }
-  if constexpr (NP == 7) {
-    if (a.fast_d == 4 && a.gpm_frags > 0 && a.n_bands <= GPM_MAX_BANDS &&
-        (a.fast_obs == OBS_DN16 || a.fast_obs == OBS_F32)) {
-      const size_t lds = (size_t)a.gpm_frags * sizeof(kf_h8);
-      if (a.fast_obs == OBS_DN16 && a.split_mixlo) {   // AV_MIXLO_SPLIT (mixlo_split_gain)
-        gpm_lds_attr(gain_mfma_mixlo_kernel<NP, 4, OBS_DN16>, lds);
-        hipLaunchKernelGGL((gain_mfma_mixlo_kernel<NP, 4, OBS_DN16>), dim3(grid), dim3(BLOCK), lds, s, a);
-      } else if (a.fast_obs == OBS_DN16) {
-        gpm_lds_attr(gain_mfma_kernel<NP, 4, OBS_DN16>, lds);
-        hipLaunchKernelGGL((gain_mfma_kernel<NP, 4, OBS_DN16>), dim3(grid), dim3(BLOCK), lds, s, a);
-      } else {
-        gpm_lds_attr(gain_mfma_kernel<NP, 4, OBS_F32>, lds);
-        hipLaunchKernelGGL((gain_mfma_kernel<NP, 4, OBS_F32>), dim3(grid), dim3(BLOCK), lds, s, a);
-      }
-      return;
-    }
-    KF_GAIN_FAST(4)
-  } else if constexpr (NP == 10) {
-    // full-state GP bands with global tables (ops/kernels.py:gain sets
-    // gpm_global unless the VALU oracle is selected)
-    if (a.gpm_global && a.fast_d == NP && (a.fast_obs == OBS_DN16 || a.fast_obs == OBS_F32)) {
-      if (a.fast_obs == OBS_DN16 && a.split_mixlo)   // AV_MIXLO_SPLIT (mixlo_split_gain)
-        hipLaunchKernelGGL((gain_mfma_g_mixlo_kernel<NP, NP, OBS_DN16>), dim3(grid), dim3(BLOCK), 0, s, a);
-      else if (a.fast_obs == OBS_DN16)
-        hipLaunchKernelGGL((gain_mfma_g_kernel<NP, NP, OBS_DN16>), dim3(grid), dim3(BLOCK), 0, s, a);
-      else
-        hipLaunchKernelGGL((gain_mfma_g_kernel<NP, NP, OBS_F32>), dim3(grid), dim3(BLOCK), 0, s, a);
-      return;
-    }
-    KF_GAIN_FAST(10)
-  }
-#undef KF_GAIN_FAST
-  hipLaunchKernelGGL(gain_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
 }
 
 // MODE < 0: runtime a.mode (prepare / classic: Cholesky-sized registers);
@@ -667,224 +579,123 @@ inline int grid_for(int64_t N, int max_blocks) {
     default: return hipErrorInvalidValue;         \
   }
 
-// Interleaved exponent MFMAs (gpm_chunk IL: both column blocks' exponent
-// MFMAs before the first block's exponentials) by default where the second
-// live block costs no waves per SIMD and no scratch (ISA lint,
-// tests/test_isa_lint.py): the JRC-TIP layout kernel (156 -> 168 VGPRs, 3
-// waves either way) and 10-parameter states (2 waves either way); +0.5% tip7,
-// +1.0% prosail10 interleaved on one box (profiles/r4_v2_ab_fixed_tip7T.jsonl).
-// Elsewhere (7-parameter runtime layout: 8-24 B scratch; 3-4 parameters: 4 ->
-// 3 waves) the block-by-block order stays.
-template <int NP, int LAYOUT>
-constexpr bool gpm_il_default() {
-  return (NP == 7 && LAYOUT == BAND_LAYOUT_TIP) || NP >= 10;
-}
+// K1 / K1g launch tables.  Which kernel a launch takes is decided by
+// analysis_plan / gain_plan (kf_plan.h); the lists below are the
+// instantiations that exist, one KF_ROW line each: the kernel's name and its
+// template arguments, from which both the plan the line answers to and the
+// kernel's address are formed.  Each translation unit builds one table from
+// the lists of its state sizes (kf_kernels.hip, kf_analysis7.hip,
+// kf_analysis10.hip, kf_gain10.hip), which is what instantiates its kernels.
+template <typename A>
+struct LaunchRow {
+  KernelPlan plan;
+  void (*kernel)(A);
+};
+#define KF_ROW(K, ...) {plan_##K(__VA_ARGS__), K<__VA_ARGS__>},
 
-// AV_MIXLO_SPLIT (gpm_exp_split's MIXLO flag: the split of m before
-// profiles/split_issue_probe.jsonl) is instantiated for the kernels its test
-// and its A/B run, DN16 observations only: the JRC-TIP LDS-table kernel (the
-// first date's generic launch and the structure-aware fused forecast without a
-// regulariser) and the 10-parameter global-table kernel, in both analysis
-// forms.  Any other launch with it is an error (dev_analysis / dev_gain), not
-// another kernel.
-inline bool mixlo_split_analysis(int np, const AnalysisArgs& a) {
-  if (a.fast_obs != OBS_DN16) return false;
-  const bool lds = a.gpm_frags > 0 && a.n_bands <= GPM_MAX_BANDS;
-  if (np == 7)
-    return lds && a.fast_d == 4 && a.band_layout == BAND_LAYOUT_TIP && a.n_bands == 2 &&
-           (!a.prop || ((a.a_struct & A_STRUCT_TIP) && !a.reg_v));
-  if (np == 10) return !lds && a.fast_d == 10 && a.gpm_global;
-  return false;
-}
-inline bool mixlo_split_gain(int np, const GainArgs& a) {
-  if (a.fast_obs != OBS_DN16) return false;
-  if (np == 7) return a.fast_d == 4 && a.gpm_frags > 0 && a.n_bands <= GPM_MAX_BANDS;
-  if (np == 10) return a.fast_d == 10 && a.gpm_global;
-  return false;
-}
+// any bands (the generic kernel), all-precomputed and all-linear operators
+#define KF_K1_ROWS_ANY(NP)                            \
+  KF_ROW(analysis_kernel, NP, 0, 0)                   \
+  KF_ROW(analysis_kernel, NP, FD_PRECOMP, OBS_DN16)   \
+  KF_ROW(analysis_kernel, NP, FD_PRECOMP, OBS_F32)    \
+  KF_ROW(analysis_kernel, NP, FD_PRECOMP, OBS_BF16)   \
+  KF_ROW(analysis_kernel, NP, FD_PRECOMP, OBS_BF16Y)  \
+  KF_ROW(analysis_kernel, NP, FD_LINEAR, OBS_DN16)    \
+  KF_ROW(analysis_kernel, NP, FD_LINEAR, OBS_F32)     \
+  KF_ROW(analysis_kernel, NP, FD_LINEAR, OBS_BF16)    \
+  KF_ROW(analysis_kernel, NP, FD_LINEAR, OBS_BF16Y)
+// GP bands of FD inputs each: the VALU kernels and the LDS-table matrix-core
+// kernels of the runtime layout, in both exponent orders
+#define KF_K1_ROWS_GP(NP, FD, MINW)                                                                \
+  KF_ROW(analysis_kernel, NP, FD, OBS_DN16)                                                        \
+  KF_ROW(analysis_kernel, NP, FD, OBS_F32)                                                         \
+  KF_ROW(analysis_mfma_kernel, NP, FD, OBS_DN16, BLOCK, MINW, BAND_LAYOUT_RUNTIME, false, SPEC_ANY) \
+  KF_ROW(analysis_mfma_kernel, NP, FD, OBS_DN16, BLOCK, MINW, BAND_LAYOUT_RUNTIME, true, SPEC_ANY)  \
+  KF_ROW(analysis_mfma_kernel, NP, FD, OBS_F32, BLOCK, MINW, BAND_LAYOUT_RUNTIME, false, SPEC_ANY)  \
+  KF_ROW(analysis_mfma_kernel, NP, FD, OBS_F32, BLOCK, MINW, BAND_LAYOUT_RUNTIME, true, SPEC_ANY)
+// full-state GP bands with the tables in global memory (IL0: gpm_il_default)
+#define KF_K1_ROWS_GLOBAL(NP, IL0)                                          \
+  KF_ROW(analysis_mfma_g_kernel, NP, NP, OBS_DN16, false, false, SPEC_ANY)  \
+  KF_ROW(analysis_mfma_g_kernel, NP, NP, OBS_DN16, false, true, SPEC_ANY)   \
+  KF_ROW(analysis_mfma_g_kernel, NP, NP, OBS_DN16, false, true, SPEC_PROP)  \
+  KF_ROW(analysis_mfma_g_kernel, NP, NP, OBS_DN16, true, false, SPEC_ANY)   \
+  KF_ROW(analysis_mfma_g_kernel, NP, NP, OBS_F32, false, IL0, SPEC_ANY)
+// the JRC-TIP layout (two 4-input bands, LDS tables)
+#define KF_K1_ROWS_TIP_SPEC(K, SPEC) KF_ROW(K, 7, 4, OBS_DN16, BLOCK, 3, BAND_LAYOUT_TIP, true, SPEC)
+#define KF_K1_ROWS_TIP                                                                   \
+  KF_ROW(analysis_mfma_kernel, 7, 4, OBS_DN16, BLOCK, 3, BAND_LAYOUT_TIP, false, SPEC_ANY) \
+  KF_ROW(analysis_mfma_kernel, 7, 4, OBS_F32, BLOCK, 3, BAND_LAYOUT_TIP, false, SPEC_ANY)  \
+  KF_ROW(analysis_mfma_kernel, 7, 4, OBS_F32, BLOCK, 3, BAND_LAYOUT_TIP, true, SPEC_ANY)   \
+  KF_K1_ROWS_TIP_SPEC(analysis_mfma_kernel, SPEC_ANY)                                    \
+  KF_K1_ROWS_TIP_SPEC(analysis_mfma_kernel, SPEC_PROP)                                   \
+  KF_K1_ROWS_TIP_SPEC(analysis_mfma_kernel, SPEC_PROP_REG)                               \
+  KF_K1_ROWS_TIP_SPEC(analysis_mfma_kernel, SPEC_PROP_PF)                                \
+  KF_K1_ROWS_TIP_SPEC(analysis_mfma_kernel, SPEC_PROP_TIP)                               \
+  KF_K1_ROWS_TIP_SPEC(analysis_mfma_kernel, SPEC_PROP_REG_TIP)                           \
+  KF_K1_ROWS_TIP_SPEC(analysis_mfma_kernel, SPEC_PROP_PF_TIP)                            \
+  KF_K1_ROWS_TIP_SPEC(analysis_mfma_mixlo_kernel, SPEC_ANY)                              \
+  KF_K1_ROWS_TIP_SPEC(analysis_mfma_mixlo_kernel, SPEC_PROP_TIP)                         \
+  KF_K1_ROWS_TIP_SPEC(analysis_mfma_mixlo_kernel, SPEC_PROP_PF_TIP)                      \
+  KF_ROW(analysis_tip_sl_kernel, true, TIP_ROWS_NONE, TIP_OUT_NONE)                      \
+  KF_ROW(analysis_tip_sl_kernel, true, TIP_ROWS_NONE, TIP_OUT_UNC)                       \
+  KF_ROW(analysis_tip_sl_kernel, true, TIP_ROWS_NONE, TIP_OUT_MEAN)                      \
+  KF_ROW(analysis_tip_sl_kernel, true, TIP_ROWS_DIAG, TIP_OUT_NONE)                      \
+  KF_ROW(analysis_tip_sl_kernel, true, TIP_ROWS_DIAG, TIP_OUT_UNC)                       \
+  KF_ROW(analysis_tip_sl_kernel, true, TIP_ROWS_DIAG, TIP_OUT_MEAN)                      \
+  KF_ROW(analysis_tip_sl_kernel, true, TIP_ROWS_ALL, TIP_OUT_NONE)                       \
+  KF_ROW(analysis_tip_sl_kernel, true, TIP_ROWS_ALL, TIP_OUT_UNC)                        \
+  KF_ROW(analysis_tip_sl_kernel, true, TIP_ROWS_ALL, TIP_OUT_MEAN)
 
-// Launch of a matrix-core analysis kernel on the static grid-stride mapping
-// (partials per workgroup; the hardware dispatcher hands a finished
-// workgroup's slot to the next one, which balances the cloud-skip load).
+// the tables' lists by state size: full-state GPs for small states, JRC-TIP
+// (7 params, 4-input band GPs), PROSAIL (10 params, full-state GPs)
+#define KF_K1_ROWS_SMALL(NP) KF_K1_ROWS_ANY(NP) KF_K1_ROWS_GP(NP, NP, 3)
+#define KF_K1_ROWS_7 \
+  KF_K1_ROWS_ANY(7) KF_K1_ROWS_GP(7, 4, 3) KF_K1_ROWS_GP(7, 7, 3) KF_K1_ROWS_GLOBAL(7, false) KF_K1_ROWS_TIP
+#define KF_K1_ROWS_10                                                              \
+  KF_K1_ROWS_ANY(10) KF_K1_ROWS_GP(10, 10, 1) KF_K1_ROWS_GLOBAL(10, true)          \
+  KF_ROW(analysis_mfma_g_mixlo_kernel, 10, 10, OBS_DN16, false, true, SPEC_ANY)    \
+  KF_ROW(analysis_mfma_g_mixlo_kernel, 10, 10, OBS_DN16, false, true, SPEC_PROP)
+
+#define KF_K1G_ROWS_SMALL(NP) KF_ROW(gain_kernel, NP, 0, 0)
+#define KF_K1G_ROWS_GP(NP, FD) \
+  KF_K1G_ROWS_SMALL(NP) KF_ROW(gain_kernel, NP, FD, OBS_DN16) KF_ROW(gain_kernel, NP, FD, OBS_F32)
+#define KF_K1G_ROWS_7                            \
+  KF_K1G_ROWS_GP(7, 4)                           \
+  KF_ROW(gain_mfma_kernel, 7, 4, OBS_DN16)       \
+  KF_ROW(gain_mfma_kernel, 7, 4, OBS_F32)        \
+  KF_ROW(gain_mfma_mixlo_kernel, 7, 4, OBS_DN16)
+#define KF_K1G_ROWS_10                              \
+  KF_K1G_ROWS_GP(10, 10)                            \
+  KF_ROW(gain_mfma_g_kernel, 10, 10, OBS_DN16)      \
+  KF_ROW(gain_mfma_g_kernel, 10, 10, OBS_F32)       \
+  KF_ROW(gain_mfma_g_mixlo_kernel, 10, 10, OBS_DN16)
+
+// Launch of the table's kernel for a plan, hipErrorInvalidValue where it has
+// none (PLAN_NONE included), on the static grid-stride mapping: norm partials
+// per workgroup (grid entries); the hardware dispatcher hands a finished
+// workgroup's slot to the next one, which balances the cloud-skip load.
 // Round 5's persistent tile queue with per-XCD counters measured within
 // 0.5 % of it at 10980^2, 3882^2 and for PROSAIL and was removed in round 6.
-// *n_part: the partial entries written.
-template <typename KernT>
-static void launch_tiles(KernT kernel, int bs, size_t lds, const AnalysisArgs& a, int grid, hipStream_t s,
-                         int* n_part) {
-  *n_part = grid;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(bs), lds, s, a);
+template <typename A, size_t N>
+static hipError_t launch_plan(const LaunchRow<A> (&rows)[N], const KernelPlan& p, const A& a, int grid,
+                              hipStream_t s) {
+  for (const LaunchRow<A>& r : rows) {
+    if (!(r.plan == p)) continue;
+    const size_t lds = plan_lds_tables(p) ? (size_t)a.gpm_frags * sizeof(kf_h8) : 0;
+    // dynamic LDS above the 64 KiB default (tables of several bands, up to the
+    // 160 KiB of a gfx950 CU)
+    if (lds > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(r.kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds);
+    hipLaunchKernelGGL(r.kernel, dim3(grid), dim3(p.bs), lds, s, a);
+    return hipGetLastError();
+  }
+  return hipErrorInvalidValue;
 }
 
-template <int NP, int FD>
-static bool l_analysis_fast(const AnalysisArgs& a, int grid, hipStream_t s, int* n_part) {
-  *n_part = grid;
-  // GP on the matrix cores when the host attached split-f16 tables to every band
-  // (AV_VALU_ORACLE: the f32 VALU record loop, the tests' second device path)
-  if constexpr (FD > 0 && FD <= GPM_MAX_D) {
-    if (a.gpm_frags > 0 && a.variant != AV_VALU_ORACLE && a.n_bands <= GPM_MAX_BANDS) {
-      const size_t lds = (size_t)a.gpm_frags * sizeof(kf_h8);
-#define KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_)                                                        \
-  {                                                                                                           \
-    gpm_lds_attr(analysis_mfma_kernel<NP, FD, OBS_, BS_, MINW_, LAY_, IL_, SPEC_>, lds);                      \
-    launch_tiles(analysis_mfma_kernel<NP, FD, OBS_, BS_, MINW_, LAY_, IL_, SPEC_>, BS_, lds, a, grid, s, n_part); \
-  }
-#define KF_MFMA_GO1M(OBS_, BS_, MINW_, LAY_, IL_, SPEC_)                                                        \
-  {                                                                                                           \
-    gpm_lds_attr(analysis_mfma_mixlo_kernel<NP, FD, OBS_, BS_, MINW_, LAY_, IL_, SPEC_>, lds);                \
-    launch_tiles(analysis_mfma_mixlo_kernel<NP, FD, OBS_, BS_, MINW_, LAY_, IL_, SPEC_>, BS_, lds, a, grid, s, n_part); \
-  }
-      // Both column blocks' exponent MFMAs issued before the first block's
-      // exponentials (gpm_chunk IL) where that costs no occupancy
-      // (gpm_il_default); AV_BLOCK_ORDER: the other order
-#define KF_MFMA_GO(OBS_, BS_, MINW_, LAY_)                                   \
-  {                                                                         \
-    if (gpm_il_default<NP, LAY_>() != (a.variant == AV_BLOCK_ORDER))        \
-      KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, true, SPEC_ANY)                   \
-    else KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, false, SPEC_ANY)               \
-  }
-      // JRC-TIP layout with the forecast fused (every date after the first):
-      // the launch's paths fixed at compile time (SPEC_PROP / SPEC_PROP_REG,
-      // kf_core.h); AV_GENERIC_SPEC: the generic kernel.  With the JRC-TIP zero
-      // structure of the forecast precision (AnalysisArgs.a_struct, checked on
-      // the host) their SPEC_*_TIP twins with the structure-aware solve;
-      // AV_DENSE_SOLVE: the dense kernels all the same
-#define KF_MFMA_GO_SPEC(OBS_, BS_, MINW_, LAY_)                                                      \
-  {                                                                                                 \
-    constexpr bool IL_ = gpm_il_default<NP, LAY_>();                                                \
-    const bool tips = (a.a_struct & A_STRUCT_TIP) && a.variant != AV_DENSE_SOLVE;                   \
-    if (a.variant == AV_MIXLO_SPLIT) { /* mixlo_split_analysis: no prop, or tips and no reg_v */    \
-      if (!a.prop) KF_MFMA_GO1M(OBS_, BS_, MINW_, LAY_, IL_, SPEC_ANY)                              \
-      else if (small) KF_MFMA_GO1M(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_PF_TIP)                   \
-      else KF_MFMA_GO1M(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_TIP)                                 \
-    }                                                                                               \
-    else if (!a.prop || a.variant == AV_BLOCK_ORDER || a.variant == AV_GENERIC_SPEC)                \
-      KF_MFMA_GO(OBS_, BS_, MINW_, LAY_)                                                            \
-    else if (a.reg_v && tips) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_REG_TIP)          \
-    else if (a.reg_v) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_REG)                      \
-    else if (small && tips) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_PF_TIP)              \
-    else if (small) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_PF)                          \
-    else if (tips) KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP_TIP)                          \
-    else KF_MFMA_GO1(OBS_, BS_, MINW_, LAY_, IL_, SPEC_PROP)                                        \
-  }
-      // Launch bound of 3 workgroups per CU (MINW = 3, as the LDS tables
-      // allow) up to 7 parameters: the compiler holds the kernel to <= 168
-      // VGPRs itself (A/B neutral against landing there unconstrained,
-      // profiles/r3_v13_*); 10 parameters would spill, so no bound there.
-      constexpr int MW = NP <= 7 ? 3 : 1;
-      // JRC-TIP band layout (AnalysisArgs.band_layout, checked on the host):
-      // band loop unrolled over the two compile-time maps (AV_RUNTIME_LAYOUT:
-      // the runtime-layout kernel, its oracle)
-      bool tip = false;
-      // small emulators (<= 4 chunks of 32 training points per band): the GP
-      // loop is too short to hide the next group's forecast loads, so the
-      // SPEC_PROP_PF kernel loads them ahead (T = 32: -2.2 %; at T = 500 the
-      // extra registers cost +0.5 %, profiles/r5_forecast_prefetch_ab.jsonl)
-      const bool small = a.gpm_frags <= 4 * a.n_bands * gpm_frags_per_chunk(FD) + 1;
-      (void)small;
-      if constexpr (NP == 7 && FD == 4)
-        tip = a.band_layout == BAND_LAYOUT_TIP && a.n_bands == 2 && a.variant != AV_RUNTIME_LAYOUT;
-      if (a.fast_obs == OBS_DN16) {
-        if constexpr (NP == 7 && FD == 4) {
-          // the launch shape of the straight-line kernel (a.tc filled by the host: tip_const_fill);
-          // AV_LOOPED_TIP: the SPEC_PROP_TIP kernels below for the same launch (its oracle)
-          if (tip && a.tc.on && a.variant == AV_DEFAULT && l_analysis_tip_sl(lds, a, grid, s, n_part)) return true;
-          if (tip) {
-            KF_MFMA_GO_SPEC(OBS_DN16, BLOCK, 3, BAND_LAYOUT_TIP)
-            return true;
-          }
-        }
-        KF_MFMA_GO(OBS_DN16, BLOCK, MW, BAND_LAYOUT_RUNTIME)
-      } else if (a.fast_obs == OBS_F32) {
-        if constexpr (NP == 7 && FD == 4) {
-          if (tip) {
-            KF_MFMA_GO(OBS_F32, BLOCK, 3, BAND_LAYOUT_TIP)
-            return true;
-          }
-        }
-        KF_MFMA_GO(OBS_F32, BLOCK, MW, BAND_LAYOUT_RUNTIME)
-      } else {
-        return false;
-      }
-#undef KF_MFMA_GO_SPEC
-#undef KF_MFMA_GO
-#undef KF_MFMA_GO1
-#undef KF_MFMA_GO1M
-      return true;
-    }
-    if constexpr (FD == NP && NP >= 7) {
-      if (a.gpm_global && a.variant != AV_VALU_ORACLE) {
-        // AV_GT_PREFETCH: register double buffer (next chunk's fragments
-        // loaded under the current one): 191.7 vs 191.6 ms/step without, so
-        // the default leaves the latency to the other wave
-        constexpr bool IL = gpm_il_default<NP, BAND_LAYOUT_RUNTIME>();
-        if (a.fast_obs == OBS_DN16 && a.variant == AV_GT_PREFETCH)
-          launch_tiles(analysis_mfma_g_kernel<NP, FD, OBS_DN16, true>, BLOCK, 0, a, grid, s, n_part);
-        else if (NP == 10 && a.fast_obs == OBS_DN16 && a.variant == AV_MIXLO_SPLIT && a.prop && !a.reg_v) {
-          if constexpr (NP == 10)
-            launch_tiles(analysis_mfma_g_mixlo_kernel<NP, FD, OBS_DN16, false, true, SPEC_PROP>, BLOCK, 0, a, grid, s,
-                         n_part);
-        } else if (NP == 10 && a.fast_obs == OBS_DN16 && a.variant == AV_MIXLO_SPLIT) {
-          if constexpr (NP == 10)
-            launch_tiles(analysis_mfma_g_mixlo_kernel<NP, FD, OBS_DN16, false, true>, BLOCK, 0, a, grid, s, n_part);
-        }
-        else if (a.fast_obs == OBS_DN16 && a.prop && !a.reg_v && a.variant == AV_DEFAULT && IL)
-          // fused forecast, no regulariser: the launch's paths fixed at compile time (SPEC_PROP)
-          launch_tiles(analysis_mfma_g_kernel<NP, FD, OBS_DN16, false, true, SPEC_PROP>, BLOCK, 0, a, grid, s, n_part);
-        else if (a.fast_obs == OBS_DN16 && (a.variant == AV_BLOCK_ORDER) != IL)
-          launch_tiles(analysis_mfma_g_kernel<NP, FD, OBS_DN16, false, true>, BLOCK, 0, a, grid, s, n_part);
-        else if (a.fast_obs == OBS_DN16)
-          launch_tiles(analysis_mfma_g_kernel<NP, FD, OBS_DN16>, BLOCK, 0, a, grid, s, n_part);
-        else if (a.fast_obs == OBS_F32)
-          launch_tiles(analysis_mfma_g_kernel<NP, FD, OBS_F32, false, IL>, BLOCK, 0, a, grid, s, n_part);
-        else
-          return false;
-        return true;
-      }
-    }
-  }
-  if (a.fast_obs == OBS_DN16) {
-    hipLaunchKernelGGL((analysis_kernel<NP, FD, OBS_DN16>), dim3(grid), dim3(BLOCK), 0, s, a);
-  } else if (a.fast_obs == OBS_F32) {
-    hipLaunchKernelGGL((analysis_kernel<NP, FD, OBS_F32>), dim3(grid), dim3(BLOCK), 0, s, a);
-  } else if constexpr (FD <= 0) {
-    // bf16 (y, w) observations: precomputed / linear operators only
-    if (a.fast_obs == OBS_BF16)
-      hipLaunchKernelGGL((analysis_kernel<NP, FD, OBS_BF16>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else if (a.fast_obs == OBS_BF16Y)
-      hipLaunchKernelGGL((analysis_kernel<NP, FD, OBS_BF16Y>), dim3(grid), dim3(BLOCK), 0, s, a);
-    else
-      return false;
-  } else {
-    return false;
-  }
-  return true;
+template <typename A, size_t N>
+static void table_plans(const LaunchRow<A> (&rows)[N], std::vector<KernelPlan>& out) {
+  for (const LaunchRow<A>& r : rows) out.push_back(r.plan);
 }
 
-// Fast-path instantiations: JRC-TIP (7 params, 4-input band GPs), PROSAIL
-// (10 params, full-state GPs) and full-state GPs for small states.
-template <int NP>
-static void l_analysis(const AnalysisArgs& a, int grid, hipStream_t s, int* n_part) {
-  bool done = false;
-  *n_part = grid;
-  if (a.fast_d > 0) {
-    if constexpr (NP == 7) {
-      if (a.fast_d == 4) done = l_analysis_fast<7, 4>(a, grid, s, n_part);
-      else if (a.fast_d == 7) done = l_analysis_fast<7, 7>(a, grid, s, n_part);
-    } else if constexpr (NP == 10) {
-      if (a.fast_d == 10) done = l_analysis_fast<10, 10>(a, grid, s, n_part);
-    } else if constexpr (NP <= 4) {
-      if (a.fast_d == NP) done = l_analysis_fast<NP, NP>(a, grid, s, n_part);
-    }
-  }
-  else if (a.fast_d == FD_PRECOMP) {
-    done = l_analysis_fast<NP, FD_PRECOMP>(a, grid, s, n_part);
-  } else if (a.fast_d == FD_LINEAR) {
-    done = l_analysis_fast<NP, FD_LINEAR>(a, grid, s, n_part);
-  }
-  if (!done) {
-    *n_part = grid;
-    hipLaunchKernelGGL(analysis_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
-  }
-}
 }  // namespace kf

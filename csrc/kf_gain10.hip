@@ -6,9 +6,12 @@
 
 namespace kf {
 
+static const LaunchRow<GainArgs> k1g_rows[] = {KF_K1G_ROWS_10};
+
 hipError_t dev_gain_np10(const GainArgs& a, int grid, hipStream_t s) {
-  l_gain<10>(a, grid, s);
-  return hipGetLastError();
+  return launch_plan(k1g_rows, gain_plan(10, a), a, grid, s);
 }
+
+void launch_table_gain_np10(std::vector<KernelPlan>& out) { table_plans(k1g_rows, out); }
 
 }  // namespace kf

@@ -51,17 +51,10 @@ typedef float kf_f16v __attribute__((ext_vector_type(16)));
 typedef uint32_t kf_u4 __attribute__((ext_vector_type(4)));
 typedef __fp16 kf_hp2 __attribute__((ext_vector_type(2)));
 
-// exponent K steps of 16 slots (3D + 2 used)
-KF_HD constexpr int gpm_k_steps(int D) { return (3 * D + 2 + 15) / 16; }
+// (gpm_k_steps, gpm_sum_rows, gpm_frags_per_chunk, GPM_MAX_D, GPM_MAX_BANDS: kf_core.h, the
+// table sizes the host-side kernel choice of kf_plan.h reads as well)
 // first row of the lo half of the sums operand
 KF_HD constexpr int gpm_lo_row(int D) { return D + 1 <= 8 ? 8 : 16; }
-// sums fragments per (q, h): the lanes whose row is used (hi and lo rows)
-KF_HD constexpr int gpm_sum_rows(int D) { return 2 * (D + 1); }
-// 16-byte fragments per 32-point chunk
-KF_HD constexpr int gpm_frags_per_chunk(int D) { return 64 * gpm_k_steps(D) + 4 * gpm_sum_rows(D); }
-constexpr int GPM_MAX_D = 10;
-// bands whose sums are held across the record loops (larger tables fall back to VALU)
-constexpr int GPM_MAX_BANDS = 4;
 // waves per workgroup of the global-table kernels (analysis_mfma_g_kernel,
 // BLOCK = 256): the sizes of their per-wave LDS transpose buffers
 constexpr int GPM_G_WAVES = 4;

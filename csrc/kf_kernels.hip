@@ -608,32 +608,33 @@ bool gp_operator_supported(int np, int d) {
   return (np == 10 && (d == 10 || d == 4)) || (np == 7 && (d == 7 || d == 4)) || (np == d && np >= 2 && np <= 4);
 }
 
+// K1 / K1g: plan (kf_plan.h), look up, launch (kf_device.h launch_plan).  This unit's
+// tables: the analysis kernels up to 4 parameters, the gain kernels up to 7.
+static const LaunchRow<AnalysisArgs> k1_rows[] = {KF_K1_ROWS_SMALL(1) KF_K1_ROWS_SMALL(2) KF_K1_ROWS_SMALL(3)
+                                                      KF_K1_ROWS_SMALL(4)};
+static const LaunchRow<GainArgs> k1g_rows[] = {KF_K1G_ROWS_SMALL(1) KF_K1G_ROWS_SMALL(2) KF_K1G_ROWS_SMALL(3)
+                                                   KF_K1G_ROWS_SMALL(4) KF_K1G_ROWS_7};
+
 hipError_t dev_analysis(int np, const AnalysisArgs& a, int grid, hipStream_t s, int* n_part) {
-  if (a.variant == AV_MIXLO_SPLIT && !mixlo_split_analysis(np, a)) return hipErrorInvalidValue;
-  switch (np) {
-    case 7: return dev_analysis_np7(a, grid, s, n_part);     // kf_analysis7.hip
-    case 10: return dev_analysis_np10(a, grid, s, n_part);   // kf_analysis10.hip
-    case 1: l_analysis<1>(a, grid, s, n_part); break;
-    case 2: l_analysis<2>(a, grid, s, n_part); break;
-    case 3: l_analysis<3>(a, grid, s, n_part); break;
-    case 4: l_analysis<4>(a, grid, s, n_part); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  *n_part = grid;
+  if (np == 7) return dev_analysis_np7(a, grid, s);     // kf_analysis7.hip
+  if (np == 10) return dev_analysis_np10(a, grid, s);   // kf_analysis10.hip
+  return launch_plan(k1_rows, analysis_plan(np, a), a, grid, s);
 }
 
 hipError_t dev_gain(int np, const GainArgs& a, int grid, hipStream_t s) {
-  if (a.split_mixlo && !mixlo_split_gain(np, a)) return hipErrorInvalidValue;
   if (np == 10) return dev_gain_np10(a, grid, s);   // kf_gain10.hip
-  switch (np) {
-    case 1: l_gain<1>(a, grid, s); break;
-    case 2: l_gain<2>(a, grid, s); break;
-    case 3: l_gain<3>(a, grid, s); break;
-    case 4: l_gain<4>(a, grid, s); break;
-    case 7: l_gain<7>(a, grid, s); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_plan(k1g_rows, gain_plan(np, a), a, grid, s);
+}
+
+std::vector<KernelPlan> dev_launch_table() {
+  std::vector<KernelPlan> out;
+  table_plans(k1_rows, out);
+  launch_table_np7(out);
+  launch_table_np10(out);
+  table_plans(k1g_rows, out);
+  launch_table_gain_np10(out);
+  return out;
 }
 hipError_t dev_jacobi(int np, const JacobiArgs& a, int grid, hipStream_t s) {
   KF_NP_SWITCH(np, l_jacobi, a, grid, s);

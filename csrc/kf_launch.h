@@ -2,7 +2,9 @@
 // host: kf_host.cpp).
 #pragma once
 #include <stdint.h>
+#include <vector>
 #include "kf_core.h"
+#include "kf_plan.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #else
@@ -25,14 +27,19 @@ void set_gp_unroll(int n);
 int get_max_blocks();
 // *n_part: norm partial entries written (workgroups of the grid-stride launch)
 hipError_t dev_analysis(int np, const AnalysisArgs& a, int grid, hipStream_t s, int* n_part);
-hipError_t dev_analysis_np7(const AnalysisArgs& a, int grid, hipStream_t s, int* n_part);
-hipError_t dev_analysis_np10(const AnalysisArgs& a, int grid, hipStream_t s, int* n_part);
+hipError_t dev_analysis_np7(const AnalysisArgs& a, int grid, hipStream_t s);
+hipError_t dev_analysis_np10(const AnalysisArgs& a, int grid, hipStream_t s);
 #ifdef KF_PHASE_CLOCKS
 hipError_t phase_clocks_np7(unsigned long long* out, bool reset);
 hipError_t phase_clocks_np10(unsigned long long* out, bool reset);
 #endif
 hipError_t dev_gain(int np, const GainArgs& a, int grid, hipStream_t s);
 hipError_t dev_gain_np10(const GainArgs& a, int grid, hipStream_t s);
+// the plan of every line of the K1 / K1g launch tables (kf_device.h KF_ROW), all translation units
+std::vector<KernelPlan> dev_launch_table();
+void launch_table_np7(std::vector<KernelPlan>& out);
+void launch_table_np10(std::vector<KernelPlan>& out);
+void launch_table_gain_np10(std::vector<KernelPlan>& out);
 hipError_t dev_jacobi(int np, const JacobiArgs& a, int grid, hipStream_t s);
 hipError_t dev_propagate(int np, const PropArgs& a, hipStream_t s);
 hipError_t dev_invert(int np, const float* src, float* dst, int64_t N, int64_t ld, uint8_t* st, hipStream_t s);

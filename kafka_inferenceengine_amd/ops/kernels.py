@@ -180,8 +180,8 @@ class Variant(IntEnum):
     DENSE_SOLVE = 20         # the dense solve where the JRC-TIP structure would select the structure-aware one
     # lo half of the GP values by v_fma_mixlo/mixhi_f16 (kf_gp_mfma.h gpm_exp_split MIXLO: the split
     # before profiles/split_issue_probe.jsonl, the same bits).  Built for the JRC-TIP LDS-table and
-    # the 10-parameter global-table kernels with DN16 observations, both forms (kf_device.h
-    # mixlo_split_analysis / mixlo_split_gain); any other launch with it raises.
+    # the 10-parameter global-table kernels with DN16 observations, both forms (kf_plan.h
+    # analysis_plan / gain_plan: no kernel for any other launch with it, which raises).
     MIXLO_SPLIT = 22
     # the SPEC_PROP_TIP kernels where the launch has the shape of the straight-line JRC-TIP kernel
     # (kf_core.h tip_sl_shape): that kernel's oracle and the other arm of its A/B
@@ -362,14 +362,25 @@ STRUCT_LAUNCHES = {"tip": 0, "dense": 0}
 # of the "tip" launches: "straight" took the straight-line kernel (AnalysisArgs.tc filled: the launch
 # has its shape, kf_core.h tip_sl_shape), "looped" the SPEC_*_TIP kernels
 TIP_SL_LAUNCHES = {"straight": 0, "looped": 0}
+# the kernel the last analysis() launch on a device took (ext().analysis_plan: name, family, template arguments)
+LAST_PLAN = None
 
 
-def _count_launch(a):
+SPEC_PROP_TIP = 4   # kf_core.h: the first of the SPEC_*_TIP kernels (structure-aware solve)
+TIP_SL_KERNEL = "analysis_tip_sl_kernel"
+
+
+def _count_launch(a, plan):
+    """``plan``: the kernel the device launcher takes for ``a`` (``ext().analysis_plan``, kf_plan.h);
+    None on the host runner, whose structure-aware path keys on ``a_struct`` (kf_host.cpp h_analysis)."""
+    global LAST_PLAN
+    LAST_PLAN = plan
     if a.prop:
-        tip = bool(getattr(a, "a_struct", 0))
+        straight = plan is not None and plan["family"] == TIP_SL_KERNEL
+        tip = bool(a.a_struct) if plan is None else straight or plan["spec"] >= SPEC_PROP_TIP
         STRUCT_LAUNCHES["tip" if tip else "dense"] += 1
         if tip:
-            TIP_SL_LAUNCHES["straight" if getattr(a, "tc_on", False) else "looped"] += 1
+            TIP_SL_LAUNCHES["straight" if straight else "looped"] += 1
 
 
 def _tri(n, i, j):
@@ -485,8 +496,8 @@ def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=
                LINE_TABLES if line is None else bool(line))
         hit = _ANALYSIS_MEMO.get(key)
         if hit is not None:
-            a, grid = hit
-            _count_launch(a)
+            a, grid, plan = hit
+            _count_launch(a, plan)
             n_part = ext().analysis(n_params, a, grid, _dev(ref), _stream(ref))
             _set_valid(partials, n_part)
             _set_valid(partials_first if gn_fused == 2 else None, n_part)
@@ -625,7 +636,8 @@ def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=
     # the straight-line JRC-TIP kernel: its constant block, filled where the launch has its shape
     if dev.type == "cuda" and prop is not None and getattr(a, "a_struct", 0) and hasattr(ext(), "tip_const_fill"):
         ext().tip_const_fill(n_params, a, prop.args, list(bands.descs))
-    _count_launch(a)
+    plan = ext().analysis_plan(n_params, a) if dev.type == "cuda" else None
+    _count_launch(a, plan)
     grid = grid_for(nv)
     if partials is not None and partials.numel() < grid:
         raise ValueError("partials must hold one entry per workgroup (partials_buffer)")
@@ -633,7 +645,7 @@ def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=
     if key is not None:
         if len(_ANALYSIS_MEMO) >= 64:
             _ANALYSIS_MEMO.clear()
-        _ANALYSIS_MEMO[key] = (a, grid)
+        _ANALYSIS_MEMO[key] = (a, grid, plan)
     _set_valid(partials, n_part)
     _set_valid(partials_first if gn_fused == 2 else None, n_part)
     return partials
