@@ -398,6 +398,16 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     else check_host(host_unpack(np, P<const float>(x), P<const float>(a), N, ld, P<const int64_t>(idx),
                                 P<float>(mean), P<float>(unc), plane), "unpack");
   });
+  // marginal std rasters: sqrt(diag(P)) from the precision (MARG_PRECISION) or covariance rows
+  m.attr("MARG_PRECISION") = MARG_PRECISION;
+  m.attr("MARG_COVARIANCE") = MARG_COVARIANCE;
+  m.def("marginal", [](int np, uintptr_t x, uintptr_t p, int kind, int64_t N, int64_t ld, uintptr_t idx,
+                       uintptr_t mean, uintptr_t unc, int64_t plane, bool device, uintptr_t stream) {
+    if (device) check_hip(dev_marginal(np, P<const float>(x), P<const float>(p), kind, N, ld, P<const int64_t>(idx),
+                                       P<float>(mean), P<float>(unc), plane, (hipStream_t)stream), "marginal");
+    else check_host(host_marginal(np, P<const float>(x), P<const float>(p), kind, N, ld, P<const int64_t>(idx),
+                                  P<float>(mean), P<float>(unc), plane), "marginal");
+  });
   // GeoTIFF tile encoder (predictor 3 + one zlib stream per 256^2 tile; mode:
   // fixed Huffman, or a dynamic table per tile where that is smaller)
   m.attr("DFL_TILE") = DFL_TILE;

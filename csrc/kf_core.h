@@ -752,6 +752,73 @@ KF_HD void chol_inverse(const float (&U)[ntri(NP)], float (&Ainv)[ntri(NP)]) {
   }
 }
 
+// diag(A^-1) from the Cholesky factor of chol_packed, without forming the
+// inverse: A^-1 = U^-1 U^-T, so (A^-1)_cc = |z|^2 with U^T z = e_c.  z is zero
+// before row c, so the substitution starts there (NP (NP+1) (NP+2) / 6 FMAs in
+// all, half of chol_inverse's, and no second packed array).
+template <int NP>
+KF_HD void chol_inv_diag(const float (&U)[ntri(NP)], float (&d)[NP]) {
+#pragma unroll
+  for (int c = 0; c < NP; ++c) {
+    float z[NP];
+    z[c] = U[tri(NP, c, c)];
+    float s = z[c] * z[c];
+#pragma unroll
+    for (int i = c + 1; i < NP; ++i) {
+      float t = 0.f;
+#pragma unroll
+      for (int k = c; k < i; ++k) t = fmaf(-U[tri(NP, k, i)], z[k], t);
+      z[i] = t * U[tri(NP, i, i)];
+      s = fmaf(z[i], z[i], s);
+    }
+    d[c] = s;
+  }
+}
+
+// Marginal posterior standard deviation of pixel p, sqrt(diag(P)), scattered
+// onto the raster with the mean (the unpack pass writes the conditional one,
+// 1/sqrt(diag(P^-1))).  kind: what the packed rows p_in hold.
+//   MARG_PRECISION: P^-1, every row read (rows an analysis kernel leaves out
+//     are stored as exact zeros), factorised and diag(P) formed by
+//     chol_inv_diag.  A pixel whose block is not SPD, or yields a variance that
+//     is not finite and positive, gets NaN in all NP planes.
+//   MARG_COVARIANCE: P itself (the gain form's state); only the diagonal rows
+//     are read, NaN where an entry is not finite and positive.
+// idx == nullptr: the identity raster map.
+constexpr int MARG_PRECISION = 0;
+constexpr int MARG_COVARIANCE = 1;
+template <int NP>
+KF_HD void pixel_marginal(const float* x, const float* p_in, int kind, int64_t N, int64_t ld, const int64_t* idx,
+                          float* mean, float* unc, int64_t plane, int64_t p) {
+  constexpr int NT = ntri(NP);
+  KF_DCHECK(p >= 0 && p < N && N <= ld);
+  (void)N;
+  const int64_t r = idx ? idx[p] : p;
+  KF_DCHECK(r >= 0 && r < plane);
+  if (mean) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) mean[j * plane + r] = x[j * ld + p];
+  }
+  if (!unc) return;
+  float d[NP];
+  bool ok = true;
+  if (kind == MARG_COVARIANCE) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) d[j] = p_in[tri(NP, j, j) * ld + p];
+  } else {
+    float U[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) U[t] = p_in[t * ld + p];
+    ok = chol_packed<NP>(U);
+    chol_inv_diag<NP>(U, d);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) ok = ok && (d[j] > 0.f) && finitef(d[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < NP; ++j)
+    unc[j * plane + r] = (ok && (d[j] > 0.f) && finitef(d[j])) ? sqrtf(d[j]) : __builtin_nanf("");
+}
+
 template <int NP, class M = StructDense>
 KF_HD void symv(const float (&A)[ntri(NP)], const float (&x)[NP], float (&y)[NP]) {
 #pragma unroll

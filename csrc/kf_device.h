@@ -548,6 +548,18 @@ __global__ __launch_bounds__(BLOCK) void unpack_kernel(const float* x, const flo
   }
 }
 
+// Marginal output: mean and sqrt(diag(P)) onto the raster, from the stored
+// precision (factorised per pixel) or covariance rows (pixel_marginal).  One
+// pixel per thread; every SoA row is read coalesced.
+template <int NP>
+__global__ __launch_bounds__(BLOCK) void marginal_kernel(const float* x, const float* p_in, int kind, int64_t N,
+                                                        int64_t ld, const int64_t* idx, float* mean, float* unc,
+                                                        int64_t plane) {
+  const int64_t stride = (int64_t)gridDim.x * BLOCK;
+  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < N; p += stride)
+    pixel_marginal<NP>(x, p_in, kind, N, ld, idx, mean, unc, plane, p);
+}
+
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void gather_kernel(const T* src, const int64_t* idx, T* dst, int64_t n,
                                                       int rows, int64_t src_ld, int64_t dst_ld) {

@@ -179,6 +179,13 @@ static int h_unpack(const float* x, const float* a, int64_t N, int64_t ld, const
   }
   return 0;
 }
+template <int NP>
+static int h_marginal(const float* x, const float* p_in, int kind, int64_t N, int64_t ld, const int64_t* idx,
+                      float* mean, float* unc, int64_t plane) {
+#pragma omp parallel for schedule(static)
+  for (int64_t p = 0; p < N; ++p) pixel_marginal<NP>(x, p_in, kind, N, ld, idx, mean, unc, plane, p);
+  return 0;
+}
 
 // GeoTIFF tiles on the host: the same row encoder as dfl_tile_kernel, rows in
 // order into one byte stream per tile (bit-identical streams).  Dynamic mode:
@@ -463,6 +470,11 @@ int host_hessian(int np, const BandDesc* b, int nb, const float* x, float* a, in
 int host_unpack(int np, const float* x, const float* a, int64_t N, int64_t ld, const int64_t* idx, float* mean,
                 float* unc, int64_t plane) {
   KF_HOST_NP_SWITCH(np, h_unpack, x, a, N, ld, idx, mean, unc, plane);
+}
+int host_marginal(int np, const float* x, const float* p, int kind, int64_t N, int64_t ld, const int64_t* idx,
+                  float* mean, float* unc, int64_t plane) {
+  if (kind != MARG_PRECISION && kind != MARG_COVARIANCE) return -1;
+  KF_HOST_NP_SWITCH(np, h_marginal, x, p, kind, N, ld, idx, mean, unc, plane);
 }
 int host_obs_order(const BandDesc* bands, const int32_t* grp, int nb, int G, int64_t N, int32_t* order, bool local) {
   if (G < 1 || G > 3) return -1;

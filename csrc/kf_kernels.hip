@@ -123,6 +123,11 @@ static void l_unpack(const float* x, const float* a, int64_t N, int64_t ld, cons
                      float* unc, int64_t plane, int grid, hipStream_t s) {
   hipLaunchKernelGGL(unpack_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, x, a, N, ld, idx, mean, unc, plane);
 }
+template <int NP>
+static void l_marginal(const float* x, const float* p, int kind, int64_t N, int64_t ld, const int64_t* idx,
+                       float* mean, float* unc, int64_t plane, int grid, hipStream_t s) {
+  hipLaunchKernelGGL(marginal_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, x, p, kind, N, ld, idx, mean, unc, plane);
+}
 
 // Grid cap for the per-pixel kernels (one f64 partial per workgroup).  The
 // default keeps grid-stride loops; raising it to >= N/256 gives one pixel per
@@ -680,6 +685,14 @@ hipError_t dev_hessian(int np, const BandDesc* b, int nb, const float* x, float*
 hipError_t dev_unpack(int np, const float* x, const float* a, int64_t N, int64_t ld, const int64_t* idx,
                       float* mean, float* unc, int64_t plane, hipStream_t s) {
   KF_NP_SWITCH(np, l_unpack, x, a, N, ld, idx, mean, unc, plane, grid_for(N, KF_MAX_BLOCKS), s);
+  return hipGetLastError();
+}
+// grid capped by set_max_blocks (default KF_MAX_BLOCKS), so a test can make every
+// thread walk the grid-stride loop
+hipError_t dev_marginal(int np, const float* x, const float* p, int kind, int64_t N, int64_t ld, const int64_t* idx,
+                        float* mean, float* unc, int64_t plane, hipStream_t s) {
+  if (kind != MARG_PRECISION && kind != MARG_COVARIANCE) return hipErrorInvalidValue;
+  KF_NP_SWITCH(np, l_marginal, x, p, kind, N, ld, idx, mean, unc, plane, grid_for(N, g_max_blocks), s);
   return hipGetLastError();
 }
 // Fixed-order f64 sum of a launch's norm partials: one workgroup (at most

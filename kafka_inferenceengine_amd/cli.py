@@ -176,9 +176,9 @@ def _build(args, comm):
                             args.out, prefix=args.prefix, level=args.out_level, gather=args.out_gather,
                             predictor=3 if args.out_fast else 1, strategy="rle" if args.out_fast else None,
                             keep_timesteps=args.out_keep, encoder=args.out_encoder,
-                            huffman=args.out_huffman, **scaled)
+                            huffman=args.out_huffman, uncertainty=args.out_unc, **scaled)
     else:
-        out = k.DeviceOutput(params)
+        out = k.DeviceOutput(params, uncertainty=args.out_unc)
     kf = k.LinearKalman(obs, out, mask, factory, params, state_propagation=prop,
                         prior=None if prop is not None else prior, config=cfg, comm=comm, partition=part)
     kf.set_trajectory_model()
@@ -340,6 +340,10 @@ def main(argv=None):
     r.add_argument("--out-encoder", default="auto", choices=["auto", "device", "host"],
                    help="DEFLATE tiles encoded on the GPU (device: predictor 3 + fixed-Huffman run-length streams, "
                         "only compressed tiles cross PCIe) or by the host thread pool; auto: device on a GPU")
+    r.add_argument("--out-unc", default="conditional", choices=["conditional", "marginal"],
+                   help="the _unc rasters: conditional, 1/sqrt(diag(P^-1)) (what the reference writes: every other "
+                        "parameter of the pixel held fixed), or marginal, sqrt(diag(P)) (the posterior std of the "
+                        "parameter itself; a separate pass over the stored state on every output date)")
     r.add_argument("--in-decoder", default="host", choices=["host", "device"],
                    help="--s2-folder granules: DEFLATE tiles inflated by the host thread pool (host), or shipped "
                         "compressed and inflated on the GPU (device: 256 x 256 tiles, 16-bit samples, predictor 1 / 2; "

@@ -264,6 +264,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin):
         final analysis state (device).  ``resume_from`` restarts from a checkpoint."""
         from ..input_output.checkpoint import CheckpointManager
 
+        self._check_marginal_output()
         ckpt = CheckpointManager(self.config.checkpoint_dir, self) if self.config.checkpoint_dir else None
         self.checkpointer = ckpt
         if self.config.gc_freeze:
@@ -321,6 +322,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin):
         already is the forecast), assimilate every date in ``locate_times``,
         dump.  Returns the analysis state."""
         self.current_timestep = timestep
+        self._check_marginal_output()
         t0 = time.perf_counter()
         forecast = state
         if advance:
@@ -864,7 +866,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin):
         plain = not (gain or precomp or split or bp or cfg.spatial_gamma > 0 or cfg.hessian_correction)
         spatial = cfg.spatial_gamma > 0 and not (gain or precomp or bp or cfg.hessian_correction)
         out_t = None
-        if ((plain or spatial or (gain and not precomp)) and N and cfg.fuse_output
+        if ((plain or spatial or (gain and not precomp)) and N and cfg.fuse_output and not self._marginal_output()
                 and hasattr(self.output, "device_targets")):
             # plain and spatial paths: the final state's x doubles as the mean raster (dense strips)
             out_t = self.output.device_targets(self, self.device, alias=plain or spatial or gain)
@@ -954,8 +956,10 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin):
         if (cfg.store_precision == "always" or self._full_precision_step or not last_of_step or not more_dates
                 or cfg.band_sequential or cfg.hessian_correction or cfg.return_innovations):
             return None
-        if not (cfg.fuse_output and hasattr(self.output, "device_targets")) and self.output is not None:
-            return None            # the dump reads the precision diagonal (observations.py:392-393)
+        if not (cfg.fuse_output and not self._marginal_output()
+                and hasattr(self.output, "device_targets")) and self.output is not None:
+            # the dump reads the precision diagonal (observations.py:392-393); a marginal dump every row
+            return None
         if cfg.analysis_form == "gain":
             # the gain form stores the rows as precision diagonal entries, which only
             # its fused forecast reads (a light propagator without a prior blend:
@@ -1228,8 +1232,33 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin):
                 self.output.dump_data(timestep, x, P, prec.to_reference()[1], self.partition.local_mask,
                                       self.n_params)
 
-    def unc(self, state: KFState) -> torch.Tensor:
-        """1/sqrt(diag(P^-1)) per parameter, [n_p, N] (observations.py:392-393)."""
+    def _marginal_output(self) -> bool:
+        """The output writes marginal std rasters (``uncertainty="marginal"``): no
+        analysis kernel produces them, so nothing is fused into the analysis and
+        every row of the state is stored for ``dump_state``'s pass."""
+        return getattr(self.output, "uncertainty", "conditional") == "marginal"
+
+    def _check_marginal_output(self):
+        unc = getattr(self.output, "uncertainty", "conditional")
+        if unc not in ("conditional", "marginal"):
+            raise ValueError("output.uncertainty must be 'conditional' or 'marginal'")
+        if unc == "marginal" and self.config.spatial_gamma > 0:
+            raise ValueError("uncertainty='marginal' with spatial_gamma > 0: under the spatial (GMRF) prior the "
+                             "marginal std is not a per-pixel quantity")
+
+    def unc(self, state: KFState, kind: str = "conditional") -> torch.Tensor:
+        """Per-parameter std, [n_p, N].  "conditional": 1/sqrt(diag(P^-1))
+        (observations.py:392-393); "marginal": sqrt(diag(P)), NaN over a pixel
+        whose precision is not SPD."""
+        if kind == "marginal":
+            st = self._materialize(state)
+            st.require_full("unc")
+            out = torch.empty((self.n_params, max(self.N, 1)), dtype=torch.float32, device=st.x.device)
+            if self.N:
+                K.marginal(self.n_params, st.x, st.P, None, out, N=self.N, kind=st.kind)
+            return out[:, :self.N]
+        if kind != "conditional":
+            raise ValueError("kind must be 'conditional' or 'marginal'")
         prec = self._as_kind(state, PRECISION)
         prec.require_full("unc")
         idx = [tri_pos(self.n_params, j, j) for j in range(self.n_params)]

@@ -118,6 +118,13 @@ def _synergy_date(fname):
     return datetime.datetime.strptime(os.path.basename(fname).split(".")[1][1:], "%Y%j")
 
 
+def _sibling(fname, old, new):
+    """``fname`` with ``old`` replaced in its file name only (a directory of
+    the path may hold the same characters)."""
+    head, tail = os.path.split(fname)
+    return os.path.join(head, tail.replace(old, new))
+
+
 class SynergyKernels:
     """Linear kernel-weight stacks from the Synergy chain (``observations.py:150-211``).
 
@@ -138,8 +145,8 @@ class SynergyKernels:
             date = _synergy_date(fname)
             keep = (start_time >= date) if reference_quirks else (start_time <= date)
             if keep and (end_time is None or date <= end_time):
-                self.add_observations(date, fname, fname.replace("kernel_weights", "kernel_unc"),
-                                      fname.replace("_b0_kernel_weights", "mask"))
+                self.add_observations(date, fname, _sibling(fname, "kernel_weights", "kernel_unc"),
+                                      _sibling(fname, "_b0_kernel_weights", "mask"))
         self.emulator = emulator
 
     @property
@@ -158,9 +165,9 @@ class SynergyKernels:
         date_idx = self.dates.index(the_date)
         bhr, var = [], []
         for band in range(7):
-            k = read_tiff(self.kernels[date_idx].replace("b0", "b%d" % band))[0].astype(np.float64)
+            k = read_tiff(_sibling(self.kernels[date_idx], "_b0_kernel_", "_b%d_kernel_" % band))[0].astype(np.float64)
             bhr.append(np.sum(k * TO_BHR[:, None, None], axis=0))
-            ufile = self.uncertainties[date_idx].replace("b0", "b%d" % band)
+            ufile = _sibling(self.uncertainties[date_idx], "_b0_kernel_", "_b%d_kernel_" % band)
             if os.path.exists(ufile):   # independent kernel errors
                 u = read_tiff(ufile)[0].astype(np.float64)
                 var.append(np.sum((u * TO_BHR[:, None, None]) ** 2, axis=0))

@@ -1,7 +1,8 @@
 """Output writers (plug-in point L1: ``dump_data`` / device ``dump_state``).
 
 * ``KafkaOutput`` — per parameter and timestep a Float32 GeoTIFF of the mean
-  and one of 1/sqrt(diag(P^-1)) (the conditional std), file names
+  and one of 1/sqrt(diag(P^-1)) (the conditional std; ``uncertainty="marginal"``:
+  sqrt(diag(P)), the marginal std), file names
   ``{param}_A%Y%j[_{prefix}].tif`` / ``..._unc.tif`` (``observations.py:338-394``).
   Rasters are produced on the device by the unpack kernel and written by a
   background thread.
@@ -22,6 +23,45 @@ import torch
 
 from ..ops import kernels as K
 from .tiff import write_tiff
+
+
+UNCERTAINTY_KINDS = ("conditional", "marginal")
+
+
+def _check_uncertainty(uncertainty):
+    if uncertainty not in UNCERTAINTY_KINDS:
+        raise ValueError("uncertainty must be 'conditional' or 'marginal'")
+    return uncertainty
+
+
+def _marginal_from_blocks(P, P_inv, n):
+    """sqrt(diag(P)) per pixel block in float64, [N, n]: from the covariance
+    where it was handed in, else from the inverse of each n x n precision
+    block (NaN over a block that cannot be inverted to positive variances)."""
+    if P is not None:
+        d = np.asarray(P.diagonal(), dtype=np.float64).reshape(-1, n)
+    else:
+        from ..utils.blocks import sparse_to_blocks
+        blocks = P_inv.blocks() if hasattr(P_inv, "blocks") else sparse_to_blocks(P_inv, n)
+        blocks = np.asarray(blocks, dtype=np.float64)
+        d = np.full((blocks.shape[0], n), np.nan)
+        good = np.nonzero(np.isfinite(blocks).all(axis=(1, 2)))[0]
+        try:                                     # SPD everywhere (the usual case): one batched call
+            np.linalg.cholesky(blocks[good])
+        except np.linalg.LinAlgError:
+            keep = []
+            for i in good:
+                try:
+                    np.linalg.cholesky(blocks[i])
+                    keep.append(i)
+                except np.linalg.LinAlgError:
+                    pass
+            good = np.asarray(keep, dtype=np.int64)
+        if good.size:
+            d[good] = np.diagonal(np.linalg.inv(blocks[good]), axis1=1, axis2=2)
+        d[~(np.isfinite(d) & (d > 0)).all(axis=1)] = np.nan
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isfinite(d) & (d > 0), np.sqrt(np.where(d > 0, d, 1.0)), np.nan)
 
 
 def _fname(folder, param, timestep, prefix, suffix=""):
@@ -129,13 +169,23 @@ class KafkaOutput:
     quantises in its row load (csrc/kf_deflate.h: ``dfl_quantise``); with
     ``encoder="host"`` (or CPU planes) the host runner of the same quantiser
     produces the same samples and ``write_tiff`` encodes them.  Values outside
-    a range are clamped and counted: ``writer_stats()["saturated"]``."""
+    a range are clamped and counted: ``writer_stats()["saturated"]``.
+
+    ``uncertainty``: what the ``_unc`` rasters hold.  "conditional" (default,
+    the reference's): 1/sqrt(diag(P^-1)), the spread of a parameter with every
+    other parameter of the pixel held fixed.  "marginal": sqrt(diag(P)), the
+    posterior std of the parameter on its own (never smaller), computed per
+    pixel from the stored analysis state by ``ops.kernels.marginal``; the
+    engine then dumps the state after the analysis instead of fusing the
+    rasters into it.  A pixel whose precision is not SPD is NaN.  The files
+    keep their names and carry an ``UNCERTAINTY`` item in GDAL_METADATA."""
 
     def __init__(self, parameter_list, geotransform, projection, folder, prefix=None, fmt="GTiff",
                  compress="deflate", asynchronous=True, level: int = 6, tile: int = 256, gather: bool = False,
                  threads: int | None = None, predictor: int = 1, strategy: str | None = None,
                  keep_timesteps: int | None = None, encoder: str = "auto", huffman: str = "fixed",
-                 sample_type: str = "float32", ranges=None, unc_ranges=None):
+                 sample_type: str = "float32", ranges=None, unc_ranges=None, uncertainty: str = "conditional"):
+        self.uncertainty = _check_uncertainty(uncertainty)
         if encoder not in ("auto", "device", "host"):
             raise ValueError("encoder must be 'auto', 'device' or 'host'")
         if huffman not in ("fixed", "dynamic"):
@@ -224,12 +274,13 @@ class KafkaOutput:
                 if u16:
                     write_tiff(fn, planes[ii], gt, self.projection, self.compress, level=self.level, tile=self.tile,
                                threads=self.threads, predictor=2, strategy=self.strategy, nodata=65535,
-                               scale=scale[ii], offset=offset[ii])
+                               scale=scale[ii], offset=offset[ii], metadata=self._metadata(suffix))
                     sat_last[os.path.basename(fn)] = int(sat[ii])
                     self.saturated += int(sat[ii])
                 else:
                     write_tiff(fn, planes[ii], gt, self.projection, self.compress, level=self.level, tile=self.tile,
-                               threads=self.threads, predictor=self.predictor, strategy=self.strategy)
+                               threads=self.threads, predictor=self.predictor, strategy=self.strategy,
+                               metadata=self._metadata(suffix))
                 self.written.append(fn)
                 names.append(fn)
                 self.bytes_in += planes[ii].nbytes
@@ -238,6 +289,10 @@ class KafkaOutput:
             self.saturated_last = sat_last
         self.write_s.append(time.perf_counter() - t0)
         self._prune(names)
+
+    def _metadata(self, suffix):
+        """Further GDAL_METADATA items of a file: marginal ``_unc`` rasters say so."""
+        return {"UNCERTAINTY": "marginal"} if (suffix == "_unc" and self.uncertainty == "marginal") else None
 
     def _prune(self, names):
         if self.keep_timesteps is not None:
@@ -262,7 +317,7 @@ class KafkaOutput:
                "ratio": round(self.bytes_in / self.bytes_out, 3) if self.bytes_out else None,
                "slot_wait_s": round(self.slot_wait_s, 6), "d2h_s": round(self.d2h_s, 6),
                "prune_s": round(self.prune_s, 6), "deflate_backend": self.deflate_backend(),
-               "sample_type": self.sample_type,
+               "sample_type": self.sample_type, "uncertainty": self.uncertainty,
                "saturated": {"total": int(self.saturated), "last": dict(self.saturated_last)}}
         if w is not None:
             out.update({"queue_depth_last": w.depth[-1] if w.depth else 0,
@@ -288,7 +343,7 @@ class KafkaOutput:
     # ------------------------------------------------------- device path
     def device_targets(self, engine, dev, alias: bool = True):
         if self._dev is None:
-            self._dev = DeviceOutput(self.parameter_list)
+            self._dev = DeviceOutput(self.parameter_list, uncertainty=self.uncertainty)
         return self._dev.device_targets(engine, dev, alias)
 
     def mark_written(self, timestep, state, engine):
@@ -297,7 +352,7 @@ class KafkaOutput:
 
     def dump_state(self, timestep, state, engine):
         if self._dev is None:
-            self._dev = DeviceOutput(self.parameter_list)
+            self._dev = DeviceOutput(self.parameter_list, uncertainty=self.uncertainty)
         self._dev.dump_state(timestep, state, engine)
         self._ship(timestep, engine)
 
@@ -465,12 +520,13 @@ class KafkaOutput:
                 sl = slice(ii * per, (ii + 1) * per)
                 if u16:
                     write_tiff_tiles(fn, H, W, host, offs[sl], sizes[sl], gt, self.projection, threads=self.threads,
-                                     dtype="uint16", scale=scale[ii], offset=offset[ii])
+                                     dtype="uint16", scale=scale[ii], offset=offset[ii],
+                                     metadata=self._metadata(suffix))
                     sat_last[os.path.basename(fn)] = int(sat[ii])
                     self.saturated += int(sat[ii])
                 else:
                     write_tiff_tiles(fn, H, W, host, offs[sl], sizes[sl], gt, self.projection, predictor=3,
-                                     threads=self.threads)
+                                     threads=self.threads, metadata=self._metadata(suffix))
                 self.written.append(fn)
                 names.append(fn)
                 self.bytes_in += H * W * (2 if u16 else 4)
@@ -521,10 +577,13 @@ class KafkaOutput:
         sm = np.asarray(state_mask).astype(bool)
         mean = np.zeros((n_params,) + sm.shape, dtype=np.float32)
         unc = np.zeros_like(mean)
-        d = P_analysis_inv.diagonal()
+        if self.uncertainty == "marginal":
+            sd = _marginal_from_blocks(P_analysis, P_analysis_inv, n_params)
+        else:
+            d = P_analysis_inv.diagonal()
         for ii in range(n_params):
             mean[ii][sm] = x_analysis[ii::n_params]
-            unc[ii][sm] = 1. / np.sqrt(d[ii::n_params])
+            unc[ii][sm] = sd[:, ii] if self.uncertainty == "marginal" else 1. / np.sqrt(d[ii::n_params])
         self._write_all(timestep, mean, unc, self.geotransform, self.prefix)
 
     def flush(self):
@@ -537,14 +596,20 @@ class KafkaOutput:
 class KafkaOutputMemory:
     """In-memory output (kafka_test.py:135-145)."""
 
-    def __init__(self, parameter_list):
+    def __init__(self, parameter_list, uncertainty: str = "conditional"):
         self.parameter_list = list(parameter_list)
+        self.uncertainty = _check_uncertainty(uncertainty)
         self.output = {}
 
     def dump_data(self, timestep, x_analysis, P_analysis, P_analysis_inv, state_mask, n_params=None):
         n = n_params or len(self.parameter_list)
         sol = {p: np.asarray(x_analysis)[ii::n].copy() for ii, p in enumerate(self.parameter_list)}
-        if P_analysis_inv is not None:
+        if self.uncertainty == "marginal":
+            if P_analysis is not None or P_analysis_inv is not None:
+                sd = _marginal_from_blocks(P_analysis, P_analysis_inv, n)
+                for ii, p in enumerate(self.parameter_list):
+                    sol[p + "_unc"] = sd[:, ii].copy()
+        elif P_analysis_inv is not None:
             d = P_analysis_inv.diagonal()
             for ii, p in enumerate(self.parameter_list):
                 sol[p + "_unc"] = 1. / np.sqrt(d[ii::n])
@@ -565,10 +630,19 @@ class DeviceOutput:
     buffer pairs, so a reader of one date's planes (``KafkaOutput``'s
     device-to-host copy) runs under the next date's analysis;
     ``device_targets`` makes the analysis wait only for a reader of the pair it
-    is about to overwrite (``release``)."""
+    is about to overwrite (``release``).
 
-    def __init__(self, parameter_list, keep_history: bool = False, alias_state: bool = True):
+    ``uncertainty="marginal"``: the uncertainty planes hold sqrt(diag(P))
+    instead of 1/sqrt(diag(P^-1)) (see ``KafkaOutput``).  No analysis kernel
+    writes that, so the engine does not ask for ``device_targets``: every date
+    goes through ``dump_state``, one ``ops.kernels.marginal`` pass over the
+    stored state (precision or, for the gain form, covariance) that writes the
+    mean planes as well."""
+
+    def __init__(self, parameter_list, keep_history: bool = False, alias_state: bool = True,
+                 uncertainty: str = "conditional"):
         self.parameter_list = list(parameter_list)
+        self.uncertainty = _check_uncertainty(uncertainty)
         self.keep_history = keep_history
         self.alias_state = bool(alias_state)
         self.mean = None
@@ -646,11 +720,16 @@ class DeviceOutput:
     def dump_state(self, timestep, state, engine):
         n = engine.n_params
         self._ensure(engine, state.x.device)
-        prec = engine._as_kind(state, "precision")
+        marginal = self.uncertainty == "marginal"
+        # marginal: the state as it is (a covariance state holds the variances on its diagonal rows)
+        st = engine._materialize(state) if marginal else engine._as_kind(state, "precision")
         unc = self._next_unc(state.x.device)
         mean = self._own_mean()
-        if state.N:
-            K.unpack(n, prec.x, prec.P, mean, unc, idx=None if self._identity else self._idx, N=state.N)
+        idx = None if self._identity else self._idx
+        if state.N and marginal:
+            K.marginal(n, st.x, st.P, mean, unc, idx=idx, N=state.N, kind=st.kind)
+        elif state.N:
+            K.unpack(n, st.x, st.P, mean, unc, idx=idx, N=state.N)
         self._pending, self._alias = unc, False
         self.mark_written(timestep, state, engine)
 

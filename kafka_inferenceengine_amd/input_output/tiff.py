@@ -79,14 +79,28 @@ def epsg_of(projection) -> int:
     return 0
 
 
-def _scale_metadata(scale, offset) -> str:
+def _scale_metadata(scale, offset, items=None) -> str:
     """Text of TIFF tag 42112 (GDAL_METADATA) for ``value = offset + scale *
-    sample``; the values as ``repr(float)``, which round-trips exactly."""
-    if scale is None and offset is None:
+    sample``; the values as ``repr(float)``, which round-trips exactly.
+    ``items``: further name -> text items of the dataset (``_parse_item``)."""
+    if scale is None and offset is None and not items:
         return ""
-    sc, of = float(1.0 if scale is None else scale), float(0.0 if offset is None else offset)
-    return (f'<GDALMetadata><Item name="OFFSET" sample="0" role="offset">{of!r}</Item>'
-            f'<Item name="SCALE" sample="0" role="scale">{sc!r}</Item></GDALMetadata>')
+    body = ""
+    if scale is not None or offset is not None:
+        sc, of = float(1.0 if scale is None else scale), float(0.0 if offset is None else offset)
+        body = (f'<Item name="OFFSET" sample="0" role="offset">{of!r}</Item>'
+                f'<Item name="SCALE" sample="0" role="scale">{sc!r}</Item>')
+    for name, text in (items or {}).items():
+        if not re.fullmatch(r"[A-Za-z0-9_]+", str(name)) or not re.fullmatch(r"[^<>&]*", str(text)):
+            raise ValueError("metadata items: plain names and texts without markup")
+        body += f'<Item name="{name}">{text}</Item>'
+    return f'<GDALMetadata>{body}</GDALMetadata>'
+
+
+def _parse_item(text, name):
+    """Text of the item ``name`` of a tag 42112 text; None where absent."""
+    m = re.search(r'<Item\b[^>]*\bname="%s"[^>]*>([^<]*)</Item>' % re.escape(name), text or "")
+    return m.group(1) if m else None
 
 
 def _parse_scale_metadata(text) -> tuple:
@@ -104,7 +118,7 @@ def _parse_scale_metadata(text) -> tuple:
 def write_tiff(path, array, geotransform=None, projection: str | None = None, compress: str | None = "deflate",
                rows_per_strip: int = 64, bigtiff: bool | None = None, nodata=None, tile: int | None = 256,
                level: int = 6, threads: int | None = None, predictor: int = 1, strategy: str | None = None,
-               scale=None, offset=None):
+               scale=None, offset=None, metadata=None):
     """Write a 2-D raster or a (bands, H, W) stack.  Native path: tiled
     (``tile`` px) DEFLATE, parallel compression, EPSG GeoKeys from
     ``projection``; ``tile=None`` (or no extension) writes the striped Python
@@ -112,7 +126,8 @@ def write_tiff(path, array, geotransform=None, projection: str | None = None, co
     predictor; ``strategy`` "rle" / "huffman" selects the zlib strategy (about
     3x faster encoding of float rasters at a similar ratio).  ``scale`` /
     ``offset``: written as GDAL_METADATA (tag 42112) for scaled integer
-    samples, ``value = offset + scale * sample`` (``read_tiff_scaled``)."""
+    samples, ``value = offset + scale * sample`` (``read_tiff_scaled``);
+    ``metadata``: further GDAL_METADATA items, name -> text."""
     a = np.ascontiguousarray(np.asarray(array))
     if a.dtype == np.bool_:
         a = a.astype(np.uint8)
@@ -123,24 +138,27 @@ def write_tiff(path, array, geotransform=None, projection: str | None = None, co
         bits, fmt = _NATIVE_FMT[a.dtype]
         gt = [float(v) for v in geotransform] if geotransform is not None else []
         big = -1 if bigtiff is None else int(bool(bigtiff))
-        meta = _scale_metadata(scale, offset)
+        meta = _scale_metadata(scale, offset, metadata)
         E.tiff_write(str(path), planes.ctypes.data, nb, H, W, bits, fmt, int(tile),
                      level if compress == "deflate" else 0, threads or _threads(), gt, epsg_of(projection),
                      "" if projection is None else str(projection), "" if nodata is None else str(nodata), big,
                      int(predictor), _STRATEGY[strategy], *([meta] if meta else []))
         return
-    _write_tiff_py(path, a, geotransform, projection, compress, rows_per_strip, bigtiff, nodata, scale, offset)
+    _write_tiff_py(path, a, geotransform, projection, compress, rows_per_strip, bigtiff, nodata, scale, offset,
+                   metadata)
 
 
 def write_tiff_tiles(path, H: int, W: int, data, offsets, sizes, geotransform=None, projection: str | None = None,
                      nodata=None, predictor: int | None = None, bigtiff: bool | None = None,
-                     threads: int | None = None, tile: int = 256, dtype: str = "float32", scale=None, offset=None):
+                     threads: int | None = None, tile: int = 256, dtype: str = "float32", scale=None, offset=None,
+                     metadata=None):
     """A GeoTIFF from tiles already encoded as zlib streams
     (``ops.kernels.TileEncoder``: tile i's ``sizes[i]`` bytes at ``data`` +
     ``offsets[i]``, row-major tiles); only the file layout is written here.
     ``dtype``: "float32" (predictor 3 unless given) or "uint16" (the encoder's
     ``sample="uint16"``: 16-bit unsigned samples, predictor 2, nodata 65535
-    unless given, ``scale`` / ``offset`` in GDAL_METADATA)."""
+    unless given, ``scale`` / ``offset`` in GDAL_METADATA).  ``metadata``:
+    further GDAL_METADATA items, name -> text."""
     if dtype not in ("float32", "uint16"):
         raise ValueError("dtype must be 'float32' or 'uint16'")
     u16 = dtype == "uint16"
@@ -150,7 +168,7 @@ def write_tiff_tiles(path, H: int, W: int, data, offsets, sizes, geotransform=No
         predictor = 2 if u16 else 3
     if u16 and nodata is None:
         nodata = 65535
-    meta = _scale_metadata(scale, offset)
+    meta = _scale_metadata(scale, offset, metadata)
     E = _native()
     if E is None or not hasattr(E, "tiff_write_tiles"):
         raise RuntimeError("write_tiff_tiles needs the native extension")
@@ -164,7 +182,8 @@ def write_tiff_tiles(path, H: int, W: int, data, offsets, sizes, geotransform=No
 
 
 def _write_tiff_py(path, array, geotransform=None, projection: str | None = None, compress: str | None = "deflate",
-                   rows_per_strip: int = 64, bigtiff: bool | None = None, nodata=None, scale=None, offset=None):
+                   rows_per_strip: int = 64, bigtiff: bool | None = None, nodata=None, scale=None, offset=None,
+                   metadata=None):
     a = np.ascontiguousarray(np.asarray(array))
     if a.ndim not in (2, 3):
         raise ValueError("write_tiff writes 2-D rasters or (bands, H, W) stacks")
@@ -196,7 +215,7 @@ def _write_tiff_py(path, array, geotransform=None, projection: str | None = None
         keys = [1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 1026, 34737, len(cit), 0]
         tags.append((34735, SHORT, keys))
         tags.append((34737, ASCII, cit))
-    meta = _scale_metadata(scale, offset)
+    meta = _scale_metadata(scale, offset, metadata)
     if meta:
         tags.append((42112, ASCII, meta))
     if nodata is not None:
@@ -262,6 +281,8 @@ def _geo_from_native(info) -> dict:
     if info["nodata"]:
         out["nodata"] = info["nodata"]
     out["scale"], out["offset"] = _parse_scale_metadata(info.get("gdal_metadata", ""))
+    if _parse_item(info.get("gdal_metadata", ""), "UNCERTAINTY") is not None:
+        out["uncertainty"] = _parse_item(info.get("gdal_metadata", ""), "UNCERTAINTY")
     return out
 
 
@@ -420,6 +441,8 @@ def _read_tiff_py(path):
     if 42113 in tags and tags[42113]:
         info["nodata"] = tags[42113]
     info["scale"], info["offset"] = _parse_scale_metadata(tags.get(42112, ""))
+    if _parse_item(tags.get(42112, ""), "UNCERTAINTY") is not None:
+        info["uncertainty"] = _parse_item(tags.get(42112, ""), "UNCERTAINTY")
     return arr.astype(dtype.newbyteorder("=")), info
 
 

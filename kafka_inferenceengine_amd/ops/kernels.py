@@ -1569,6 +1569,38 @@ def unpack(n_params, x, a, mean=None, unc=None, idx=None, N=None):
                  _stream(x))
 
 
+MARGINAL_KINDS = ("precision", "covariance")
+
+
+def marginal(n_params, x, p, mean=None, unc=None, idx=None, N=None, kind="precision"):
+    """Scatter mean and the marginal std sqrt(diag(P)) onto raster planes
+    [n_p, H*W].  ``p`` holds the packed rows of P^-1 (``kind="precision"``:
+    factorised per pixel; a block that is not SPD gives NaN in all its planes)
+    or of P itself (``kind="covariance"``: the diagonal rows are read)."""
+    check_np(n_params)
+    if kind not in MARGINAL_KINDS:
+        raise ValueError("kind must be 'precision' or 'covariance'")
+    N = int(x.shape[1] if N is None else N)
+    _check_soa(x, n_params, N, "x")
+    if unc is not None:
+        _check_soa(p, ntri(n_params), N, "p", device=x.device)
+        if p.shape[1] != x.shape[1]:
+            raise ValueError("x and p must share their row stride")
+    plane = (mean if mean is not None else unc).shape[1]
+    for t in (mean, unc):
+        if t is not None:
+            _check_soa(t, n_params, 0, "out", device=x.device)
+            if t.shape[1] != plane:
+                raise ValueError("mean and unc planes differ in size")
+    if idx is not None:
+        _check_vec(idx, N, "idx", torch.int64, x.device)
+    elif plane < N:
+        raise ValueError("output plane smaller than N without an index map")
+    e = ext()
+    e.marginal(n_params, _ptr(x), _ptr(p), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION, N,
+               x.shape[1], _ptr(idx), _ptr(mean), _ptr(unc), plane, _dev(x), _stream(x))
+
+
 def reduce_partials(partials: torch.Tensor, out: torch.Tensor | None = None):
     """Fixed-order f64 sum of the partials the last producer wrote (device:
     one workgroup)."""
