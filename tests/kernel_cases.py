@@ -766,3 +766,338 @@ def lut_launch(lut, pts, N, device):
     x = padded(np.asarray(pts)[:N].T, ld, device, fill=1e6)
     K.lut_nearest(torch.from_numpy(np.asarray(lut, dtype=np.float32)).to(device), x, out=out, N=N)
     return out.cpu()
+
+
+# --------------------------------------------------------------------------
+# The non-GP analysis and gain kernels (tests/test_nongp_kernels.py): linear,
+# precomputed and mixed band tables in every observation encoding, built from
+# raw bits, with a float64 model of decode_obs, of the operators and (through
+# info_model / gain_blocks) of the analysis and its status byte.
+ENCODINGS = (K.OBS_DN16, K.OBS_F32, K.OBS_BF16, K.OBS_BF16Y)
+ENC_NAME = {K.OBS_DN16: "dn16", K.OBS_F32: "f32", K.OBS_BF16: "bf16", K.OBS_BF16Y: "bf16y"}
+# DN 65535 is a reflectance of 0.655: the clean observations (<= 0.6) use the whole uint16 range
+NONGP_SCALE, NONGP_REL, NONGP_FLOOR = 1e-5, 0.05, 2.5e-3
+STATUS_FILL = 0xA5
+
+
+def bf16_bits(a):
+    """float32 values -> bf16 bit patterns (uint16), round to nearest even; Inf and NaN keep their class."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    nan = np.isnan(np.asarray(a, dtype=np.float32))
+    return np.where(nan, np.uint16(0x7FC0), r).astype(np.uint16)
+
+
+def bf16_value(bits):
+    """bf16 bit patterns (uint16) -> their values as float64: the bits shifted left by 16, read as float32."""
+    return (np.asarray(bits, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+
+
+def decode_model(enc, raw, scale=NONGP_SCALE, rel_unc=NONGP_REL, unc_floor=NONGP_FLOOR):
+    """float64 model of kf_core.h decode_obs from the raw bits of one band:
+    ``raw["dn"]`` uint16 digital numbers, or ``raw["y"]`` / ``raw["w"]`` float32
+    values (OBS_F32) or bf16 bit patterns (OBS_BF16; OBS_BF16Y has y only), and
+    ``raw["mask"]`` uint8 or None.  Returns (y, w), both 0 where the band has no
+    observation:
+
+    DN16   y = f32(DN scale); sigma = max(rel_unc y, floor); kept where DN > 0
+           and sigma > 0 with w = 1 / sigma^2 (y is kept wherever DN > 0)
+    F32    kept where the mask (if any) is set, w > 0, w and y finite
+    BF16   as F32 on the values of the bit patterns
+    BF16Y  sigma = max(rel_unc |y|, floor); kept where the mask is set, y is
+           finite and sigma > 0, w = 1 / sigma^2
+
+    The weight 1 / sigma^2 is taken in float64 from the float32-rounded y and
+    the float32-rounded scalars."""
+    s, r, fl = (float(np.float32(v)) for v in (scale, rel_unc, unc_floor))
+    with np.errstate(all="ignore"):
+        if enc == K.OBS_DN16:
+            dn = np.asarray(raw["dn"], dtype=np.uint16).astype(np.float64)
+            y = f32(dn * s)
+            sig = np.maximum(r * y, fl)
+            ok = (dn > 0) & (sig > 0)
+            return np.where(dn > 0, y, 0.0), np.where(ok, 1.0 / np.where(ok, sig * sig, 1.0), 0.0)
+        m = np.ones(len(raw["y"]), bool) if raw.get("mask") is None else np.asarray(raw["mask"]) != 0
+        if enc == K.OBS_BF16Y:
+            y = bf16_value(raw["y"])
+            sig = np.maximum(r * np.abs(y), fl)
+            ok = m & np.isfinite(y) & (sig > 0)
+            return np.where(ok, y, 0.0), np.where(ok, 1.0 / np.where(ok, sig * sig, 1.0), 0.0)
+        if enc == K.OBS_BF16:
+            y, w = bf16_value(raw["y"]), bf16_value(raw["w"])
+        else:
+            y, w = (np.asarray(raw[key], dtype=np.float32).astype(np.float64) for key in ("y", "w"))
+        ok = m & (w > 0) & np.isfinite(w) & np.isfinite(y)
+        return np.where(ok, y, 0.0), np.where(ok, w, 0.0)
+
+
+# decode edges, planted in every band at pixel 1 + i and in band i % nb alone at
+# pixel 20 + i (the pixel is then still observed by the other bands).  Each
+# entry replaces fields of the encoded observation: dn, y, w (values), mask.
+DECODE_EDGES = {
+    K.OBS_DN16: (dict(dn=0), dict(dn=1), dict(dn=32768), dict(dn=40000), dict(dn=65535)),
+    K.OBS_F32: (dict(w=0.0), dict(w=-4.0), dict(w=np.inf), dict(w=np.nan), dict(w=-np.inf), dict(y=np.nan),
+                dict(y=np.inf), dict(y=-np.inf), dict(mask=0), dict(w=2.0 ** 20)),
+    K.OBS_BF16Y: (dict(y=np.nan), dict(y=np.inf), dict(y=-np.inf), dict(y=-0.3125), dict(y=0.0), dict(mask=0)),
+}
+DECODE_EDGES[K.OBS_BF16] = DECODE_EDGES[K.OBS_F32]
+EDGE_ALL, EDGE_ONE = 1, 20      # first pixel of the two plant runs
+DARK_LANE, LIT_LANE = 40, 41    # of every 64-pixel block: no band observed / every band observed
+
+
+def encode_band(enc, y, sigma, rng, edges=True, band=0, nb=1, mask_plane=True):
+    """One band's raw observation arrays in encoding ``enc`` from clean values
+    ``y`` (in (0, 0.65)) with standard deviations ``sigma``: a quarter of the pixels
+    dropped at random through the encoding's own nodata value, the decode edges
+    planted, lanes DARK_LANE / LIT_LANE of every 64-pixel block unobserved /
+    observed (a block of one pixel, the tail of N = 65 or 513, is observed).
+    Returns the raw dict of ``decode_model``."""
+    N = len(y)
+    drop = rng.random(N) < 0.25
+    lane, blk = np.arange(N) % 64, np.arange(N) // 64
+    single = np.bincount(blk)[blk] == 1
+    drop[(lane == LIT_LANE) | single] = False
+    drop[(lane == DARK_LANE) & ~single] = True
+    f = dict(dn=np.clip(np.round(y / NONGP_SCALE), 1, 65535), y=np.array(y, dtype=np.float64),
+             w=1.0 / np.asarray(sigma, dtype=np.float64) ** 2, mask=np.ones(N))
+    # the nodata value of the encoding; with a mask plane every other dropped pixel goes through it alone
+    via_mask = drop & (np.arange(N) % 2 == 0) & (enc != K.OBS_DN16) & mask_plane
+    f["mask"][via_mask] = 0
+    hard = drop & ~via_mask
+    f["dn"][hard] = 0
+    if enc == K.OBS_BF16Y:
+        f["y"][hard] = np.nan
+    else:
+        f["w"][hard] = 0.0
+    if edges:
+        for i, e in enumerate(DECODE_EDGES[enc]):
+            for p in (EDGE_ALL + i,) + ((EDGE_ONE + i,) if band == i % nb else ()):
+                if p >= N:
+                    continue
+                # a clean observation, then the edge
+                f["dn"][p], f["y"][p], f["w"][p], f["mask"][p] = max(round(y[p] / NONGP_SCALE), 1), y[p], \
+                    1.0 / sigma[p] ** 2, 1
+                for key, v in e.items():
+                    if key == "mask" and not mask_plane:
+                        key, v = ("y", np.nan) if enc == K.OBS_BF16Y else ("w", 0.0)
+                    f[key][p] = v
+    mask = f["mask"].astype(np.uint8) if (mask_plane and enc != K.OBS_DN16) else None
+    if enc == K.OBS_DN16:
+        return dict(dn=f["dn"].astype(np.uint16), mask=None)
+    with np.errstate(all="ignore"):
+        y32, w32 = f["y"].astype(np.float32), f["w"].astype(np.float32)
+    if enc == K.OBS_F32:
+        return dict(y=y32, w=w32, mask=mask)
+    if enc == K.OBS_BF16:
+        return dict(y=bf16_bits(y32), w=bf16_bits(w32), mask=mask)
+    return dict(y=bf16_bits(y32), mask=mask)
+
+
+def _np_vec(a, ld, device, fill, dtype):
+    t = torch.full((ld,), fill, dtype=dtype)
+    t[:len(a)] = torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
+    return t.to(device)
+
+
+def device_band(enc, raw, ld, device, aux=None):
+    """``raw`` (encode_band) as a DeviceBand whose vectors are ld long (the
+    padding holds values a kernel reading past N would turn into observations)."""
+    mask = None if raw.get("mask") is None else _np_vec(raw["mask"], ld, device, 1, torch.uint8)
+    kw = dict(scale=NONGP_SCALE, rel_unc=NONGP_REL, unc_floor=NONGP_FLOOR, mask=mask,
+              aux=None if aux is None else _np_vec(aux, ld, device, 30.0, torch.float32))
+    if enc == K.OBS_DN16:
+        return DeviceBand(enc, dn=_np_vec(raw["dn"].view(np.int16), ld, device, 5000, torch.int16), **kw)
+    if enc == K.OBS_F32:
+        return DeviceBand(enc, y=_np_vec(raw["y"], ld, device, 0.5, torch.float32),
+                          w=_np_vec(raw["w"], ld, device, 1e4, torch.float32), **kw)
+    one = int(bf16_bits(np.float32([0.5])).view(np.int16)[0])
+    y = _np_vec(raw["y"].view(np.int16), ld, device, one, torch.int16)
+    if enc == K.OBS_BF16Y:
+        return DeviceBand(enc, y=y, **kw)
+    return DeviceBand(enc, y=y, w=_np_vec(raw["w"].view(np.int16), ld, device,
+                                          int(bf16_bits(np.float32([1e4])).view(np.int16)[0]), torch.int16), **kw)
+
+
+_NONGP_CASES: dict = {}
+_SMALL_GP: dict = {}
+
+
+def small_gp(n):
+    """A 64-point synthetic emulator over all n states (the "small" emulator of test_gpu_launch_plan.py)."""
+    from kafka_inferenceengine_amd.models.gp import GaussianProcessEmulator
+    if n not in _SMALL_GP:
+        _SMALL_GP[n] = GaussianProcessEmulator.synthetic(
+            lambda X: 0.3 + 0.2 * np.sin(2 * X[:, 0]) + 0.15 * X[:, 1 % n] * X[:, n - 1], np.zeros(n), np.ones(n),
+            64, 5, name="small")
+    return _SMALL_GP[n]
+
+
+def nongp_case(n, N, bands, seed=0, fused=False, bad_op=True):
+    """One analysis problem over ``bands`` = ((operator, encoding), ...) with
+    operator in "linear", "precomp", "sar", "gp", built once per argument set
+    and never changed.  Every input is float32-valued; ``evals`` holds the
+    float64 model (H0, h, y, w) of every band at the linearisation point ``x0``
+    and ``obs_w`` the decoded weights [nb, N].
+
+    linear   dense positive coefficients over all n states and an offset > 0
+    precomp  per-pixel rows pre_h0 [N] / pre_h [n, N]; with ``bad_op`` NaN / Inf
+             planted at lanes 45-48 of the first block: 45 pre_h0 of band 0, 46
+             one pre_h entry of band 1 (or 0), 47 pre_h0 of every band (the
+             pixel then has no usable band), 48 pre_h0 of band 0 at a pixel
+             where that band is masked (no flag)
+    sar      the water-cloud model on states (0, 1), per-pixel incidence angle
+    gp       small_gp(n) over all states
+
+    The forecast precision ``Pf`` is a random SPD block per pixel and ``Pcov``
+    its float64 inverse rounded to float32 (the gain form's forecast covariance).
+
+    ``fused``: the forecast is the partial prior reset the kernel computes from
+    a previous analysis (``xa``, precision ``pa``; ``spec`` for K.prop_args): the
+    last parameter propagated with m = 1, x_f = reset mean elsewhere, P_f^-1 =
+    the reset precision with that parameter's diagonal 1 / (1 / pa_jj + q_j), in
+    float64 from the float32 inputs; linearised at the forecast (x0 = xf)."""
+    from kafka_inferenceengine_amd.models.operators import OP_LINEAR, OP_PRECOMP, OperatorSpec, _sar_device_spec
+    from kafka_inferenceengine_amd.utils.blocks import pack_matrix, unpack_matrix
+    key = (n, N, tuple(bands), seed, fused, bad_op)
+    if key in _NONGP_CASES:
+        return _NONGP_CASES[key]
+    nb = len(bands)
+    rng = np.random.default_rng([seed, n, N] + [("linear", "precomp", "sar", "gp").index(o) * 8 + e for o, e in bands])
+    extra = {}
+    if fused:
+        j, q = n - 1, f32(np.full(n, 0.04))
+        mu, xa, pa = f32(rng.uniform(0.25, 0.75, n)), f32(rng.uniform(0.25, 0.75, (N, n))), \
+            sym32(spd_blocks(rng, N, n, 10.0))
+        R = rng.uniform(-0.15, 0.15, (n, n))
+        R = 0.5 * (R + R.T)
+        np.fill_diagonal(R, 0.0)
+        R += np.diag(2.0 + np.abs(R).sum(1))
+        R = unpack_matrix(f32(pack_matrix(R)), n)
+        xf, Pf = np.tile(mu, (N, 1)), np.tile(R, (N, 1, 1))
+        xf[:, j] = xa[:, j]
+        Pf[:, j, j] = 1.0 / (1.0 / pa[:, j, j] + q[j])
+        x0 = xf
+        extra = dict(xa=xa, pa=pa, spec={"mode": 1, "m": np.ones(n), "q": q, "prop_mask": 1 << j, "reset_mean": mu,
+                                         "reset_cinv": pack_matrix(R)})
+    else:
+        xf = f32(rng.uniform(0.25, 0.75, (N, n)))
+        x0 = f32(xf + 0.03 * rng.normal(size=(N, n)))
+        Pf = sym32(spd_blocks(rng, N, n, 10.0))
+    xt = xf + 0.05 * rng.normal(size=(N, n))
+    Pcov = sym32(np.linalg.inv(Pf))
+    th = f32(rng.uniform(25, 45, N))
+    specs, raws, pre, aux, evals, obs_w = [], [], [], [], [], []
+    lane0 = np.arange(N)
+    for b, (op, enc) in enumerate(bands):
+        p_h0 = p_h = a = None
+        if op == "linear":
+            c, off = f32(rng.uniform(0.05, 0.3, n) * min(1.0, 2.0 / n)), float(f32(rng.uniform(0.05, 0.2)))
+            specs.append(OperatorSpec(OP_LINEAR, list(range(n)), [float(v) for v in c], [], off))
+            H0, h = off + x0 @ c, np.tile(c, (N, 1))
+            clean = off + xt @ c
+        elif op == "precomp":
+            p_h0, p_h = f32(rng.uniform(0.1, 0.6, N)), f32(0.3 * rng.normal(size=(N, n)))
+            specs.append(OperatorSpec(OP_PRECOMP, list(range(n)), [0.0] * n))
+            clean = p_h0 + ((xt - x0) * p_h).sum(1)
+            H0, h = p_h0.copy(), p_h.copy()
+        elif op == "sar":
+            pol = ("VV", "VH")[b % 2]
+            specs.append(_sar_device_spec(n, None, None, b % 2))
+            H0, g = k.sar_observation_operator(x0[:, :2], th, pol)
+            h = np.zeros((N, n))
+            h[:, :2] = g
+            clean, a = k.sar_observation_operator(xt[:, :2], th, pol)[0], th
+        else:
+            em = small_gp(n)
+            specs.append(k.gp_spec(em, np.arange(n)))
+            H0, h = em.predict(x0)
+            clean = em.predict(xt)[0]
+        sigma = rng.uniform(0.005, 0.02, N)
+        clean = np.clip(clean + sigma * rng.normal(size=N), 2e-3, 0.6)
+        raw = encode_band(enc, clean, sigma, rng, band=b, nb=nb, mask_plane=not (nb >= 3 and b == nb - 1))
+        y, w = decode_model(enc, raw)
+        if op == "precomp" and bad_op:
+            def at(lane):
+                return lane0[lane:lane + 1] if lane < N else lane0[:0]
+            if b == 0:
+                p_h0[at(45)] = np.nan
+                p_h0[at(48)] = np.inf
+            if b == min(1, nb - 1):
+                p_h[at(46), n - 1] = -np.inf
+            p_h0[at(47)] = np.nan
+            H0, h = p_h0.copy(), p_h.copy()
+        raws.append(raw)
+        pre.append(None if p_h0 is None else (p_h0, p_h))
+        aux.append(a)
+        evals.append((H0, h, y, w))
+        obs_w.append(w)
+    obs_w = np.array(obs_w)
+    if bad_op and N > 48:
+        # lanes 45-47 carry the operator faults at observed pixels, lane 48 at a pixel masked in band 0
+        for b, (op, enc) in enumerate(bands):
+            if op != "precomp":
+                continue
+            lit = encode_band(enc, np.full(N, 0.4), np.full(N, 0.01), np.random.default_rng(1), edges=False,
+                              mask_plane=raws[b].get("mask") is not None)
+            for key in raws[b]:
+                if raws[b][key] is None:
+                    continue
+                raws[b][key][45:48] = lit[key][LIT_LANE]
+                raws[b][key][48] = lit[key][LIT_LANE if b else DARK_LANE]
+            y, w = decode_model(enc, raws[b])
+            evals[b] = (evals[b][0], evals[b][1], y, w)
+            obs_w[b] = w
+    c = dict(n=n, N=N, nb=nb, bands=tuple(bands), specs=specs, raws=raws, pre=pre, aux=aux, x0=x0, xf=xf, Pf=Pf,
+             Pcov=Pcov, evals=evals, obs_w=obs_w, **extra)
+    _NONGP_CASES[key] = c
+    return c
+
+
+def coverage(c):
+    """Every 64-pixel block of the case with more than one pixel holds an observed
+    and an unobserved pixel, and a block of one pixel is observed (model weights)."""
+    seen = (c["obs_w"] > 0).any(0)
+    for s in range(0, c["N"], 64):
+        blk = seen[s:s + 64]
+        if not (blk.any() and (len(blk) == 1 or not blk.all())):
+            return False
+    return True
+
+
+def nongp_table(c, device, pad, h0_out=False, bands=None):
+    """The case's band table on ``device`` with ld = N + pad for the observation
+    vectors and pre_ld = ld + 3 for the precomputed rows; -> (table, h0 planes
+    or None).  ``bands``: the indices of a subset (band chunks)."""
+    N, n = c["N"], c["n"]
+    ld = N + pad
+    idx = list(range(c["nb"])) if bands is None else list(bands)
+    db = [device_band(c["bands"][i][1], c["raws"][i], ld, device, c["aux"][i]) for i in idx]
+    pre = [None if c["pre"][i] is None else (_np_vec(c["pre"][i][0], ld, device, 0.25, torch.float32),
+                                             padded(c["pre"][i][1].T, ld + 3, device, fill=0.25)) for i in idx]
+    h0 = [sentinel(1, ld, device)[0] for _ in idx] if h0_out else None
+    return build_table([c["specs"][i] for i in idx], db, n, RecordCache(), device, h0, pre), h0
+
+
+def gain_model(c):
+    """float64 model of a gain-form launch of the case: ``gain_blocks`` over the
+    bands that are observed and whose operator is finite, and the status byte
+    (ST_BAD_OP: an observed band whose value or Jacobian is not finite;
+    ST_NO_OBS: no band left).  -> dict(x, P, status, strong): ``strong`` the
+    pixels where sum_b w_b h_b^T P_f h_b exceeds 1e2 (the update cancels all but
+    1e-2 of the forecast variance along h)."""
+    from kafka_inferenceengine_amd.inference import gain_blocks
+    N = c["N"]
+    st, nobs, used, gain = np.zeros(N, np.uint8), np.zeros(N, int), [], np.zeros(N)
+    with np.errstate(all="ignore"):
+        for H, h, y, w in c["evals"]:
+            use = w > 0
+            ok = np.isfinite(H) & np.isfinite(h).all(1)
+            st[use & ~ok] |= K.ST_BAD_OP
+            u = use & ok
+            nobs += u
+            hu, wu = np.where(u[:, None], h, 0.0), np.where(u, w, 0.0)
+            used.append((np.where(u, H, 0.0), hu, y, wu))
+            gain += wu * np.einsum("ni,nij,nj->n", hu, c["Pcov"], hu)
+    st[nobs == 0] |= K.ST_NO_OBS
+    x, P = gain_blocks(c["x0"], c["xf"], c["Pcov"], used)
+    return dict(x=x, P=P, status=st, strong=gain > 1e2)
