@@ -408,6 +408,34 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     else check_host(host_marginal(np, P<const float>(x), P<const float>(p), kind, N, ld, P<const int64_t>(idx),
                                   P<float>(mean), P<float>(unc), plane), "marginal");
   });
+  // RTS smoother, one backward step: filtered (x_a, p_a of `kind`) and the next step's smoothed
+  // (x_next, covariance p_next) -> smoothed (x_out, covariance p_out), status 1 where a pixel fell back
+  m.def("smooth", [](int np, uintptr_t x_a, uintptr_t p_a, int kind, uintptr_t x_next, uintptr_t p_next,
+                     uintptr_t x_out, uintptr_t p_out, uintptr_t status, int64_t N, int64_t ld, uint32_t prop_mask,
+                     const std::vector<float>& mv, const std::vector<float>& qv, uintptr_t q_pix, bool device,
+                     uintptr_t stream) {
+    if (np < 1 || np > MAX_D || (int)mv.size() != np || (int)qv.size() != np)
+      throw std::invalid_argument("smooth: m and q need one entry per parameter");
+    SmoothArgs a{};
+    a.N = N;
+    a.ld = ld;
+    a.kind = kind;
+    a.prop_mask = prop_mask;
+    a.x_a = P<const float>(x_a);
+    a.p_a = P<const float>(p_a);
+    a.x_next = P<const float>(x_next);
+    a.p_next = P<const float>(p_next);
+    a.q_pix = P<const float>(q_pix);
+    a.x_out = P<float>(x_out);
+    a.p_out = P<float>(p_out);
+    a.status = P<uint8_t>(status);
+    for (int j = 0; j < np; ++j) {
+      a.m[j] = mv[j];
+      a.q[j] = qv[j];
+    }
+    if (device) check_hip(dev_smooth(np, a, (hipStream_t)stream), "smooth");
+    else check_host(host_smooth(np, a), "smooth");
+  });
   // GeoTIFF tile encoder (predictor 3 + one zlib stream per 256^2 tile; mode:
   // fixed Huffman, or a dynamic table per tile where that is smaller)
   m.attr("DFL_TILE") = DFL_TILE;

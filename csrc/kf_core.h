@@ -831,6 +831,239 @@ KF_HD void symv(const float (&A)[ntri(NP)], const float (&x)[NP], float (&y)[NP]
   }
 }
 
+// Scheduling barrier between the independent per-row solves of pixel_smooth:
+// left free, the scheduler interleaves all NP float64 solves and holds their
+// NP x NP intermediate values at once.
+KF_HD void smooth_row_done() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_sched_barrier(0);
+#endif
+}
+// float64 twins of chol_packed / chol_solve for the smoother: a float32
+// factorisation is off by the block's condition number times 2^-24, which the
+// smoother's differences of covariances then amplify; the blocks are factorised
+// and solved in float64 and the results rounded once.
+template <int NP>
+KF_HD bool chol_packed_f64(double (&A)[ntri(NP)]) {
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    double s = A[tri(NP, j, j)];
+#pragma unroll
+    for (int k = 0; k < j; ++k) s = fma(-A[tri(NP, k, j)], A[tri(NP, k, j)], s);
+    ok = ok && (s > 0.0) && __builtin_isfinite(s);
+    s = s > 0.0 ? s : 1.0;
+    const double inv = 1.0 / sqrt(s);
+    A[tri(NP, j, j)] = inv;   // 1 / U_jj, as chol_packed
+#pragma unroll
+    for (int i = j + 1; i < NP; ++i) {
+      double t = A[tri(NP, j, i)];
+#pragma unroll
+      for (int k = 0; k < j; ++k) t = fma(-A[tri(NP, k, j)], A[tri(NP, k, i)], t);
+      A[tri(NP, j, i)] = t * inv;
+    }
+  }
+  return ok;
+}
+template <int NP>
+KF_HD void chol_solve_f64(const double (&U)[ntri(NP)], double (&b)[NP]) {
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    double t = b[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) t = fma(-U[tri(NP, k, i)], b[k], t);
+    b[i] = t * U[tri(NP, i, i)];
+  }
+#pragma unroll
+  for (int i = NP - 1; i >= 0; --i) {
+    double t = b[i];
+#pragma unroll
+    for (int k = i + 1; k < NP; ++k) t = fma(-U[tri(NP, i, k)], b[k], t);
+    b[i] = t * U[tri(NP, i, i)];
+  }
+}
+// Packed float32 inverse of a float32 SPD matrix through them; false when A is not SPD.
+template <int NP>
+KF_HD bool spd_inverse_f64(const float (&A)[ntri(NP)], float (&Ainv)[ntri(NP)]) {
+  double U[ntri(NP)];
+#pragma unroll
+  for (int t = 0; t < ntri(NP); ++t) U[t] = (double)A[t];
+  const bool ok = chol_packed_f64<NP>(U);
+#pragma unroll
+  for (int c = 0; c < NP; ++c) {
+    double e[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) e[i] = (i == c) ? 1.0 : 0.0;
+    chol_solve_f64<NP>(U, e);
+#pragma unroll
+    for (int i = 0; i <= c; ++i) Ainv[tri(NP, i, c)] = (float)e[i];
+    smooth_row_done();
+  }
+  return ok;
+}
+
+// Fixed-interval (RTS) smoother, one backward step of pixel p: the filtered
+// state (x_a, rows of kind MARG_PRECISION / MARG_COVARIANCE) of step t and the
+// smoothed (x_next, covariance rows p_next) of step t + 1 give the smoothed
+// (x_out, covariance rows p_out) of step t.  J = prop_mask is the set of
+// parameters the propagator carries to t + 1, Mt = diag(m) with zeros outside J:
+//   x_p = Mt x_a,  P_p = Mt P_a Mt + diag(q) on J,  G = P_a Mt P_p^-1,
+//   x_s = x_a + G (x_next - x_p),  P_s = P_a + G (P_next - P_p) G^T.
+// One dense path serves every J: P_p is embedded in NP x NP with a unit
+// diagonal outside J, so its factor is block diagonal and, Mt being zero
+// outside J, so are the gain's columns there (exact zeros).  Row i of G is the
+// Cholesky solve P_p g = Mt P_a[:, i] (a product with an explicit P_p^-1 loses
+// a factor of the condition number against it); P_s[i, k] = P_a[i, k] +
+// (D g_i) . g_k with D = P_next - P_p, stored as formed.
+// Fallback (status 1, else 0): an input that is not finite, a block of the
+// filtered state or P_p that is not SPD, or a result that is not finite gives
+// x_s = x_a and P_s = P_a (NaN rows where the filtered block is not SPD).
+struct SmoothArgs {
+  int64_t N, ld;
+  int32_t kind;          // MARG_PRECISION / MARG_COVARIANCE: what p_a holds
+  uint32_t prop_mask;    // J, bits as PropArgs.prop_mask
+  const float* x_a;      // [NP][ld]
+  const float* p_a;      // [NT][ld]
+  const float* x_next;   // [NP][ld]
+  const float* p_next;   // [NT][ld] covariance
+  const float* q_pix;    // optional per-pixel Q [NP][ld]
+  float* x_out;          // [NP][ld]
+  float* p_out;          // [NT][ld] covariance
+  uint8_t* status;       // [N]
+  float m[MAX_D];
+  float q[MAX_D];
+};
+// a launch's arguments: every pointer but q_pix set, N within the rows, J within the state
+inline bool smooth_args_ok(int np, const SmoothArgs& a) {
+  if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return false;
+  if (a.N < 0 || a.N > a.ld || np < 1 || np > MAX_D || (a.prop_mask >> np)) return false;
+  return a.x_a && a.p_a && a.x_next && a.p_next && a.x_out && a.p_out && a.status;
+}
+
+// entry (i, j) of the embedded P_p = Mt P_a Mt + diag(q) on J, unit diagonal outside J
+template <int NP>
+KF_HD double smooth_pp(const SmoothArgs& a, int64_t p, const float (&mt)[NP], const float (&Pa)[ntri(NP)], int i,
+                       int j) {
+  double pp = ((double)mt[i] * (double)mt[j]) * (double)Pa[tri(NP, i, j)];
+  if (i == j) {
+    const bool on = (a.prop_mask >> j) & 1u;
+    const float q = a.q_pix ? a.q_pix[j * a.ld + p] : a.q[j];
+    pp = on ? pp + (double)q : 1.0;
+  }
+  return pp;
+}
+
+template <int NP>
+KF_HD void pixel_smooth(const SmoothArgs& a, int64_t p) {
+  constexpr int NT = ntri(NP);
+  KF_DCHECK(p >= 0 && p < a.N && a.N <= a.ld);
+  const int64_t ld = a.ld;
+  const uint32_t J = a.prop_mask;
+  // one opaque copy of p per phase: its row addresses are formed where they are used, not all
+  // hoisted to the top of the grid-stride loop and held (2 VGPRs each) across the pixel
+  const int64_t p0 = opaque_lane(p);
+  bool ok = true;
+  float xa[NP], mt[NP], d[NP];
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    xa[j] = a.x_a[j * ld + p0];
+    const float xn = a.x_next[j * ld + p0];
+    const bool on = (J >> j) & 1u;
+    mt[j] = on ? a.m[j] : 0.f;
+    d[j] = on ? fmaf(-a.m[j], xa[j], xn) : 0.f;
+    const float q = a.q_pix ? a.q_pix[j * ld + p0] : a.q[j];
+    ok = ok && finitef(xa[j]) && finitef(xn) && finitef(mt[j]) && (!on || finitef(q));
+  }
+  // P_a: the covariance rows, or the inverse of the precision rows
+  float Pa[NT];
+  bool spd_a;
+  const int64_t p1 = opaque_lane(p);
+  if (a.kind == MARG_COVARIANCE) {
+    float U[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      Pa[t] = a.p_a[t * ld + p1];
+      U[t] = Pa[t];
+      ok = ok && finitef(Pa[t]);
+    }
+    spd_a = chol_packed<NP>(U);
+  } else {
+    float L[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      L[t] = a.p_a[t * ld + p1];
+      ok = ok && finitef(L[t]);
+    }
+    spd_a = spd_inverse_f64<NP>(L, Pa);
+  }
+  // G rows from U = chol(P_p) in float64, P_p embedded with a unit diagonal outside J
+  float G[NP][NP];
+  {
+    double U[NT];
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+#pragma unroll
+      for (int j = i; j < NP; ++j) U[tri(NP, i, j)] = smooth_pp<NP>(a, p, mt, Pa, i, j);
+    const bool spd_p = chol_packed_f64<NP>(U);
+    ok = ok && spd_a && spd_p;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      double g[NP];
+#pragma unroll
+      for (int j = 0; j < NP; ++j) g[j] = (double)mt[j] * (double)Pa[sym<NP>(i, j)];
+      chol_solve_f64<NP>(U, g);
+#pragma unroll
+      for (int j = 0; j < NP; ++j) G[i][j] = (float)g[j];
+      smooth_row_done();
+    }
+  }
+  // D = P_next - P_p
+  float D[NT];
+  const int64_t p2 = opaque_lane(p);
+#pragma unroll
+  for (int i = 0; i < NP; ++i)
+#pragma unroll
+    for (int j = i; j < NP; ++j) {
+      const int t = tri(NP, i, j);
+      const float sn = a.p_next[t * ld + p2];
+      ok = ok && finitef(sn);
+      D[t] = (float)((double)sn - smooth_pp<NP>(a, p, mt, Pa, i, j));
+    }
+  // x_s = x_a + G d
+  float xs[NP];
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) s = fmaf(G[i][j], d[j], s);
+    xs[i] = xa[i] + s;
+    ok = ok && finitef(xs[i]);
+  }
+  // P_s rows, stored as formed; a pixel that falls back overwrites them below
+  const int64_t p3 = opaque_lane(p);
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    float h[NP];
+    symv<NP>(D, G[i], h);
+#pragma unroll
+    for (int k = i; k < NP; ++k) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < NP; ++j) s = fmaf(h[j], G[k][j], s);
+      const float v = Pa[tri(NP, i, k)] + s;
+      ok = ok && finitef(v);
+      a.p_out[tri(NP, i, k) * ld + p3] = v;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NP; ++j) a.x_out[j * ld + p3] = ok ? xs[j] : xa[j];
+  if (!ok) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) a.p_out[t * ld + p3] = spd_a ? Pa[t] : __builtin_nanf("");
+  }
+  a.status[p3] = ok ? 0 : 1;
+}
+
 KF_HD float bf16_to_f32(uint16_t b) {
   const uint32_t u = (uint32_t)b << 16;
   float f;

@@ -560,6 +560,14 @@ __global__ __launch_bounds__(BLOCK) void marginal_kernel(const float* x, const f
     pixel_marginal<NP>(x, p_in, kind, N, ld, idx, mean, unc, plane, p);
 }
 
+// RTS smoother, one backward step (pixel_smooth): one pixel per thread, every
+// SoA row read and written coalesced.
+template <int NP>
+__global__ __launch_bounds__(BLOCK) void smooth_kernel(const SmoothArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * BLOCK;
+  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < a.N; p += stride) pixel_smooth<NP>(a, p);
+}
+
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void gather_kernel(const T* src, const int64_t* idx, T* dst, int64_t n,
                                                       int rows, int64_t src_ld, int64_t dst_ld) {

@@ -128,6 +128,10 @@ static void l_marginal(const float* x, const float* p, int kind, int64_t N, int6
                        float* mean, float* unc, int64_t plane, int grid, hipStream_t s) {
   hipLaunchKernelGGL(marginal_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, x, p, kind, N, ld, idx, mean, unc, plane);
 }
+template <int NP>
+static void l_smooth(const SmoothArgs& a, int grid, hipStream_t s) {
+  hipLaunchKernelGGL(smooth_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
+}
 
 // Grid cap for the per-pixel kernels (one f64 partial per workgroup).  The
 // default keeps grid-stride loops; raising it to >= N/256 gives one pixel per
@@ -693,6 +697,13 @@ hipError_t dev_marginal(int np, const float* x, const float* p, int kind, int64_
                         float* mean, float* unc, int64_t plane, hipStream_t s) {
   if (kind != MARG_PRECISION && kind != MARG_COVARIANCE) return hipErrorInvalidValue;
   KF_NP_SWITCH(np, l_marginal, x, p, kind, N, ld, idx, mean, unc, plane, grid_for(N, g_max_blocks), s);
+  return hipGetLastError();
+}
+// grid capped by set_max_blocks, as dev_marginal
+hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s) {
+  if (!smooth_args_ok(np, a)) return hipErrorInvalidValue;
+  if (a.N == 0) return hipSuccess;
+  KF_NP_SWITCH(np, l_smooth, a, grid_for(a.N, g_max_blocks), s);
   return hipGetLastError();
 }
 // Fixed-order f64 sum of a launch's norm partials: one workgroup (at most

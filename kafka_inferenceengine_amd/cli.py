@@ -20,6 +20,7 @@ import argparse
 import datetime as dt
 import json
 import logging
+import os
 import sys
 
 import numpy as np
@@ -78,6 +79,11 @@ def _engine_config(args):
     from .engine.config import EngineConfig
 
     cfg = EngineConfig.from_args(args)
+    if getattr(args, "smooth_out", None):
+        # the backward pass reads every step's filtered state
+        cfg.checkpoint_every, cfg.checkpoint_keep = 1, 0
+        if not cfg.checkpoint_dir:
+            cfg.checkpoint_dir = os.path.join(args.smooth_out, "checkpoints")
     explicit = getattr(args, "convergence_chunk", None) is not None
     if not explicit and getattr(args, "config_file", None):
         import yaml
@@ -154,7 +160,12 @@ def _build(args, comm):
         projection, geotransform = obs.define_output()
     else:
         projection, geotransform = info.get("projection", ""), info.get("geotransform", [0, 1, 0, 0, 0, -1])
-    if args.out:
+
+    def make_out(folder):
+        """The run's output class and options, writing into ``folder`` (None: device-resident)."""
+        if not folder:
+            return k.DeviceOutput(params, uncertainty=args.out_unc)
+
         def _ranges(items, flag):
             rg = {}
             for name, lo, hi in items or []:
@@ -172,13 +183,13 @@ def _build(args, comm):
                           unc_ranges=_ranges(args.out_unc_range, "--out-unc-range"))
         elif args.out_range or args.out_unc_range:
             raise SystemExit("--out-range / --out-unc-range belong to --out-sample uint16")
-        out = k.KafkaOutput(params, geotransform, projection,
-                            args.out, prefix=args.prefix, level=args.out_level, gather=args.out_gather,
-                            predictor=3 if args.out_fast else 1, strategy="rle" if args.out_fast else None,
-                            keep_timesteps=args.out_keep, encoder=args.out_encoder,
-                            huffman=args.out_huffman, uncertainty=args.out_unc, **scaled)
-    else:
-        out = k.DeviceOutput(params, uncertainty=args.out_unc)
+        return k.KafkaOutput(params, geotransform, projection,
+                             folder, prefix=args.prefix, level=args.out_level, gather=args.out_gather,
+                             predictor=3 if args.out_fast else 1, strategy="rle" if args.out_fast else None,
+                             keep_timesteps=args.out_keep, encoder=args.out_encoder,
+                             huffman=args.out_huffman, uncertainty=args.out_unc, **scaled)
+
+    out = make_out(args.out)
     kf = k.LinearKalman(obs, out, mask, factory, params, state_propagation=prop,
                         prior=None if prop is not None else prior, config=cfg, comm=comm, partition=part)
     kf.set_trajectory_model()
@@ -187,7 +198,7 @@ def _build(args, comm):
     dates = sorted(obs.dates)
     n = min(args.steps, len(dates)) if args.steps else len(dates)
     grid = [dates[0] - dt.timedelta(days=1)] + [dates[0] + dt.timedelta(days=step * (i + 1) - 1) for i in range(n)]
-    return kf, prior, grid, out
+    return kf, prior, grid, out, make_out
 
 
 def cmd_run(args):
@@ -202,7 +213,7 @@ def cmd_run(args):
         import torch
         dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
         comm = Comm.single(dev if dev != "cuda" else torch.device("cuda", torch.cuda.current_device()))
-    kf, prior, grid, out = _build(args, comm)
+    kf, prior, grid, out, make_out = _build(args, comm)
     import time
     t_run = time.perf_counter()
     start = None
@@ -217,6 +228,14 @@ def cmd_run(args):
     if hasattr(out, "flush"):
         out.flush()
     t_end = time.perf_counter()
+    smooth_recs = None
+    if args.smooth_out:
+        sm_out = make_out(args.smooth_out)
+        _, smooth_recs = kf.smooth(output=sm_out)
+        if hasattr(sm_out, "flush"):
+            sm_out.flush()
+        fb = [comm.sum_int(r["fallback_pixels"]) for r in smooth_recs]
+        t_smooth = time.perf_counter()
     if comm.rank == 0:
         rec = {"timesteps": len(kf.history), "pixels": kf.n_total,
                "gn_iterations": [h.get("gn_iterations") for h in kf.history],
@@ -241,6 +260,12 @@ def cmd_run(args):
             # writer telemetry: queue depth, engine waits on the writer, encode time, bytes
             rec["output"] = {"files": len(out.written), "write_ms": [round(1e3 * t, 1) for t in out.write_s],
                              **out.writer_stats()}
+        if smooth_recs is not None:
+            rec["smooth"] = {"out": args.smooth_out, "wall_s": round(t_smooth - t_end, 3),
+                             "timesteps": [r["timestep"] for r in smooth_recs], "fallback_pixels": fb,
+                             **{k_: [round(1e3 * r.get(k_, 0.0), 1) for r in smooth_recs]
+                                for k_ in ("read_s", "h2d_s", "kernel_s", "output_s")},
+                             "files": len(getattr(sm_out, "written", []))}
         print(json.dumps(rec))
     comm.destroy()
 
@@ -364,6 +389,10 @@ def main(argv=None):
                    help="keep only the newest N timesteps' output files on local disk")
     r.add_argument("--out-gather", action="store_true", help="gather strips to rank 0 and write one raster")
     r.add_argument("--resume", default=None, help="checkpoint directory (latest) or checkpoint path")
+    r.add_argument("--smooth-out", default=None, metavar="DIR",
+                   help="after the forward run, smooth backward over the steps (RTS) and write the smoothed rasters, "
+                        "under the same file names, into DIR; checkpoints every step (into DIR/checkpoints unless "
+                        "--checkpoint-dir is given)")
     r.add_argument("--log-level", default="WARNING")
     EngineConfig.add_arguments(r)
     r.set_defaults(fn=cmd_run)

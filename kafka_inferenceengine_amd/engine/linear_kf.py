@@ -38,6 +38,7 @@ from ..utils.metrics import MetricsLogger, PhaseTimer
 from .bands import DeviceBand, RecordCache, TableCache, build_table
 from .config import EngineConfig
 from .gn import GaussNewtonMixin, _GNRun
+from .smoother import SmootherMixin
 from .spatial import SpatialPriorMixin
 from .state import COVARIANCE, PRECISION, KFState, LazyForecast
 
@@ -85,7 +86,7 @@ def _jacobian_blocks(Hm, N: int, n: int) -> np.ndarray:
     return h
 
 
-class LinearKalman(GaussNewtonMixin, SpatialPriorMixin):
+class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
     """Iterated (Gauss-Newton) information-form Kalman filter over rasters."""
 
     def __init__(self, observations, output, state_mask, create_observation_operator, parameters_list,

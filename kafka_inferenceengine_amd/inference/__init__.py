@@ -7,7 +7,7 @@ from .kf_tools import (NoHessianMethod, PropagatorSpec, blend_prior, hessian_cor
                        make_no_propagation, make_partial_prior_propagator, no_propagation,
                        propagate_and_blend_prior, propagate_information_filter, propagate_information_filter_approx_SLOW,
                        propagate_information_filter_LAI, propagate_information_filter_SLOW, propagate_standard_kalman,
-                       tip_prior_full, tip_prior_noLAI)
+                       rts_smooth_blocks, tip_prior_full, tip_prior_noLAI)
 from .solvers import (analysis_blocks, gain_blocks, sort_band_data, variational_kalman,  # noqa: F401
                       variational_kalman_multiband)
 from .utils import (block_diag, create_linear_observation_operator, create_nonlinear_observation_operator,  # noqa

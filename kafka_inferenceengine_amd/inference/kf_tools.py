@@ -234,6 +234,64 @@ def identity_propagation(x_analysis, P_analysis, P_analysis_inverse, M_matrix, Q
 identity_propagation.device_spec = PropagatorSpec(PROP_IDENTITY)
 
 
+# ---------------------------------------------------------------- smoother
+def _mask_indices(mask, n):
+    """Propagated parameter indices from a bit mask (bit j: parameter j) or a sequence of indices."""
+    if isinstance(mask, (int, np.integer)):
+        if mask < 0 or int(mask) >> n:
+            raise ValueError(f"mask {int(mask):#x} has a bit at or above n={n}")
+        return np.array([j for j in range(n) if (int(mask) >> j) & 1], dtype=np.int64)
+    J = np.unique(np.asarray(list(mask), dtype=np.int64))
+    if J.size and (J[0] < 0 or J[-1] >= n):
+        raise ValueError(f"mask holds an index outside 0..{n - 1}")
+    return J
+
+
+def rts_smooth_blocks(x_a, blocks_a, x_next, P_next, mask, m, q, kind="precision"):
+    """One backward step of the fixed-interval (Rauch-Tung-Striebel) smoother,
+    per pixel, in float64 (no reference counterpart: the reference only filters).
+
+    ``x_a`` [N, n] and ``blocks_a`` [N, n, n]: the filtered state of step t, the
+    blocks holding P_a^-1 (``kind="precision"``) or P_a (``"covariance"``);
+    ``x_next`` [N, n] and ``P_next`` [N, n, n]: the smoothed mean and covariance
+    of step t + 1.  ``mask``: the parameters J the propagator carries from t to
+    t + 1, as a bit mask or a sequence of indices; ``m`` [n]: the diagonal
+    trajectory model; ``q`` [n] or [N, n]: the model error.  With M = diag(m)
+    restricted to J::
+
+        x_p = M x_a[J]                      P_p = M P_a[J, J] M + diag(q[J])
+        G   = P_a[:, J] M P_p^-1
+        x_s = x_a + G (x_next[J] - x_p)     P_s = P_a + G (P_next[J, J] - P_p) G^T
+
+    Returns ``(x_s [N, n], P_s [N, n, n])``.  With an empty J nothing links the
+    steps and the filtered moments are returned.  For the propagators whose
+    forecast is exactly (x_p, P_p) -- standard, exact information filter,
+    identity -- this is the classical RTS step and the chain of steps gives the
+    batch posterior of the whole series."""
+    if kind not in ("precision", "covariance"):
+        raise ValueError("kind must be 'precision' or 'covariance'")
+    x_a = np.asarray(x_a, dtype=np.float64)
+    N, n = x_a.shape
+    A = np.asarray(blocks_a, dtype=np.float64).reshape(N, n, n)
+    P_a = np.linalg.inv(A) if kind == "precision" else A.copy()
+    J = _mask_indices(mask, n)
+    if J.size == 0:
+        return x_a.copy(), P_a
+    x_next = np.asarray(x_next, dtype=np.float64).reshape(N, n)
+    P_next = np.asarray(P_next, dtype=np.float64).reshape(N, n, n)
+    mJ = np.broadcast_to(np.asarray(m, dtype=np.float64), (n,))[J]
+    qJ = np.broadcast_to(np.asarray(q, dtype=np.float64), (N, n))[:, J]
+    x_p = x_a[:, J] * mJ
+    P_p = P_a[:, J][:, :, J] * mJ[:, None] * mJ[None, :]
+    P_p[:, np.arange(J.size), np.arange(J.size)] += qJ
+    C = P_a[:, :, J] * mJ[None, None, :]                                  # P_a[:, J] M
+    G = np.linalg.solve(P_p, C.transpose(0, 2, 1)).transpose(0, 2, 1)     # P_p symmetric
+    x_s = x_a + np.einsum("pij,pj->pi", G, x_next[:, J] - x_p)
+    D = P_next[:, J][:, :, J] - P_p
+    P_s = P_a + np.einsum("pij,pjk,plk->pil", G, D, G)
+    return x_s, 0.5 * (P_s + P_s.transpose(0, 2, 1))
+
+
 # ------------------------------------------------------- Hessian correction
 def hessian_correction_pixel(gp, x0, C_obs_inv, innovation, band, nparams):
     selecta = band_selecta(band)

@@ -184,7 +184,11 @@ class CheckpointManager:
 
     @staticmethod
     def load(path, engine):
-        """-> (KFState on this rank, timestep datetime)."""
+        """-> (KFState on this rank, timestep datetime).  ``engine.last_checkpoint_load``
+        holds what the load took: ``{"read_s", "h2d_s", "bytes"}`` (file read, copy to the device)."""
+        import time
+
+        t0 = time.perf_counter()
         path = Path(path)
         man = CheckpointManager.read_manifest(path)
         n = int(man["n_params"])
@@ -211,8 +215,13 @@ class CheckpointManager:
         x = np.concatenate(xs, 1) if xs else np.zeros((n, 0), "<f4")
         P = np.concatenate(Ps, 1) if Ps else np.zeros((nt, 0), "<f4")
         dev = engine.device
-        st = KFState(torch.from_numpy(np.ascontiguousarray(x)).to(dev), torch.from_numpy(np.ascontiguousarray(P)).to(dev),
-                     man["kind"], x.shape[1])
+        x, P = np.ascontiguousarray(x), np.ascontiguousarray(P)
+        t1 = time.perf_counter()
+        st = KFState(torch.from_numpy(x).to(dev), torch.from_numpy(P).to(dev), man["kind"], x.shape[1])
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        engine.last_checkpoint_load = {"read_s": t1 - t0, "h2d_s": time.perf_counter() - t1,
+                                       "bytes": int(x.nbytes + P.nbytes)}
         st = engine._as_kind(st, engine._analysis_kind())
         return st, dt.datetime.fromisoformat(man["timestep"])
 
@@ -230,6 +239,19 @@ class CheckpointManager:
         if last is None:
             raise FileNotFoundError(f"no committed checkpoint (manifest.json) at or under {path}")
         return last
+
+    @staticmethod
+    def committed(root) -> list:
+        """Every committed checkpoint under ``root`` in time order:
+        ``[(timestep, directory), ...]`` (the smoother's backward pass walks them)."""
+        root = Path(root)
+        if not root.is_dir():
+            return []
+        out = []
+        for p in root.glob("A*"):
+            if (p / "manifest.json").exists():
+                out.append((dt.datetime.fromisoformat(CheckpointManager.read_manifest(p)["timestep"]), p))
+        return sorted(out, key=lambda e: e[0])
 
     @staticmethod
     def latest(root):

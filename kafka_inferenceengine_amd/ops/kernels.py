@@ -1601,6 +1601,45 @@ def marginal(n_params, x, p, mean=None, unc=None, idx=None, N=None, kind="precis
                x.shape[1], _ptr(idx), _ptr(mean), _ptr(unc), plane, _dev(x), _stream(x))
 
 
+def smooth(n_params, x_a, p_a, x_next, p_next, x_out, p_out, status, *, kind, prop_mask, m, q, q_pix=None, N=None):
+    """One backward step of the fixed-interval (RTS) smoother, per pixel
+    (csrc/kf_core.h ``pixel_smooth``).  ``x_a`` / ``p_a``: the filtered state of
+    step t, ``p_a`` the packed rows of P^-1 (``kind="precision"``) or of P
+    (``kind="covariance"``); ``x_next`` / ``p_next``: the smoothed state of step
+    t + 1, ``p_next`` its packed covariance.  ``prop_mask``: bit j set when the
+    propagator carries parameter j to the next step; ``m`` / ``q``: the diagonal
+    trajectory model and model error per parameter, ``q_pix`` [n_p, ld] a
+    per-pixel model error instead.  Writes the smoothed mean ``x_out``, packed
+    covariance ``p_out`` and ``status`` (uint8 [>= N]): 1 where the pixel fell
+    back to its filtered state (an input or result that is not finite, a block
+    that is not SPD), else 0.  Every [rows, ld] tensor shares one row stride."""
+    check_np(n_params)
+    if kind not in MARGINAL_KINDS:
+        raise ValueError("kind must be 'precision' or 'covariance'")
+    prop_mask = int(prop_mask)
+    if prop_mask < 0 or prop_mask >> n_params:
+        raise ValueError(f"prop_mask {prop_mask:#x} has a bit at or above n_params={n_params}")
+    N = int(x_a.shape[1] if N is None else N)
+    dev = x_a.device
+    _check_soa(x_a, n_params, N, "x_a")
+    for t, rows, name in ((p_a, ntri(n_params), "p_a"), (x_next, n_params, "x_next"), (p_next, ntri(n_params), "p_next"),
+                          (x_out, n_params, "x_out"), (p_out, ntri(n_params), "p_out"), (q_pix, n_params, "q_pix")):
+        if t is None and name != "q_pix":
+            raise ValueError(f"{name} is required")
+        _check_soa(t, rows, N, name, device=dev)
+        if t is not None and t.shape[1] != x_a.shape[1]:
+            raise ValueError(f"x_a and {name} must share their row stride")
+    _check_vec(status, N, "status", torch.uint8, dev)
+    if status is None:
+        raise ValueError("status is required")
+    mv = [float(v) for v in np.broadcast_to(np.asarray(m, dtype=np.float64), (n_params,))]
+    qv = [float(v) for v in np.broadcast_to(np.asarray(q, dtype=np.float64), (n_params,))]
+    e = ext()
+    e.smooth(n_params, _ptr(x_a), _ptr(p_a), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION,
+             _ptr(x_next), _ptr(p_next), _ptr(x_out), _ptr(p_out), _ptr(status), N, x_a.shape[1], prop_mask, mv, qv,
+             _ptr(q_pix), _dev(x_a), _stream(x_a))
+
+
 def reduce_partials(partials: torch.Tensor, out: torch.Tensor | None = None):
     """Fixed-order f64 sum of the partials the last producer wrote (device:
     one workgroup)."""
