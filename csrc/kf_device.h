@@ -66,11 +66,66 @@ __device__ __forceinline__ void block_partials2(double v, double v1, double* par
   }
 }
 
-template <int BS = BLOCK>
-__device__ __forceinline__ void analysis_partials(const AnalysisArgs& a, double acc, double acc1) {
+// ---------------------------------------------------------------------------
+// Launch scaffolding of the K1 / K1g kernels (AnalysisArgs or GainArgs): the
+// visiting order with n_visit / n_visit_dev, dn_out, the two norm partials of
+// gn_fused and the LDS staging of the GP tables are written here once; the
+// matrix-core kernels below differ in their per-pixel bodies only.  (The two
+// thread-per-pixel kernels write their loop out: through a helper of
+// wave_tiles' shape analysis_kernel spills a different number of SGPRs.)
+
+// The launch's norm partials: both of a fused two-iteration launch, else one.
+template <int BS = BLOCK, typename A>
+__device__ __forceinline__ void launch_partials(const A& a, double acc, double acc1) {
   if (a.partials_first) block_partials2<BS>(acc, acc1, a.partials, a.partials_first);
   else if (a.partials) block_partial<BS>(acc, a.partials);
 }
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// Every band's split-f16 table into LDS, back to back, the shared zero
+// fragment in the last slot (a.gpm_frags - 1), then the workgroup's barrier.
+// n_bands: a.n_bands, or a constant so that the band loop unrolls.
+template <int BS, int D, typename A>
+__device__ __forceinline__ void stage_tables(const A& a, int n_bands, kf_h8* gpm_lds) {
+  int off = 0;
+  for (int bi = 0; bi < n_bands; ++bi) {
+    const KF_CONST_AS BandDesc* bd = cptr(a.bands) + bi;
+    const int n = bd->gpm_nchunk * gpm_frags_per_chunk(D);
+    const kf_h8* src = (const kf_h8*)bd->gpm;
+    for (int i = threadIdx.x; i < n; i += BS) gpm_lds[off + i] = src[i];
+    off += n;
+  }
+  if (threadIdx.x == 0) gpm_lds[a.gpm_frags - 1] = kf_h8{};   // shared zero fragment
+  __syncthreads();
+}
+
+// The walk of the matrix-core kernels: each wave takes 64 visiting slots at a
+// time, grid-stride, and all 64 lanes call f(p, act, dn1) -> dn (the GP sums
+// are wave-cooperative).  act = false for the tail lanes past the visit count:
+// they run on the last slot's pixel, store nothing and add nothing.
+template <int BS, typename A, typename F>
+__device__ __forceinline__ void wave_tiles(const A& a, double& acc, double& acc1, F&& f) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * BS;
+  const int64_t nv = visit_count(a);
+  for (int64_t base = (int64_t)blockIdx.x * BS + (threadIdx.x - lane); base < nv; base += stride) {
+    const int64_t q = base + lane;
+    const bool act = q < nv;
+    const int64_t p = visit_px(a.order, act ? q : nv - 1);
+    float dn1;
+    const float dn = f(p, act, dn1);
+    acc += act ? (double)dn : 0.0;
+    acc1 += act ? (double)dn1 : 0.0;
+  }
+}
+
+// AnalysisArgs.dn_out of an active lane (K1g stores it in gain_pixel's tail).
+__device__ __forceinline__ void store_dn_out(int64_t p, bool act, float dn) {
+  // re-read through the opaque kernarg pointer: not pinned in SGPRs across the GP loop
+  float* dno = opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->dn_out;
+  if (act && dno) KF_PX(dno, 0, p) = dn;
+}
+#endif
 
 template <int NP, int FD = 0, int FOBS = 0, int UNR = 4, bool FOLD = false>
 __global__ __launch_bounds__(BLOCK) void analysis_kernel(AnalysisArgs a) {
@@ -85,7 +140,7 @@ __global__ __launch_bounds__(BLOCK) void analysis_kernel(AnalysisArgs a) {
     acc += (double)dn;
     acc1 += (double)dn1;
   }
-  analysis_partials(a, acc, acc1);
+  launch_partials(a, acc, acc1);
 }
 
 // K1 with the GP on the matrix cores (kf_gp_mfma.h).  Every band's split-f16
@@ -103,28 +158,18 @@ __device__ __forceinline__ void analysis_mfma_body(const AnalysisArgs& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ kf_h8 gpm_lds[];
   KF_PHASE_KERNEL_BEGIN
-  {
-    int off = 0;
-    for (int bi = 0; bi < a.n_bands; ++bi) {
-      const KF_CONST_AS BandDesc* bd = cptr(a.bands) + bi;
-      const int n = bd->gpm_nchunk * gpm_frags_per_chunk(D);
-      const kf_h8* src = (const kf_h8*)bd->gpm;
-      for (int i = threadIdx.x; i < n; i += BS) gpm_lds[off + i] = src[i];
-      off += n;
-    }
-    if (threadIdx.x == 0) gpm_lds[a.gpm_frags - 1] = kf_h8{};   // shared zero fragment
-  }
-  __syncthreads();
+  stage_tables<BS, D>(a, a.n_bands, gpm_lds);
   KF_PHASE(KF_PH_PROLOGUE)
   double acc = 0.0, acc1 = 0.0;
-  const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * BS;
-  const int64_t nv = visit_count(a);
   if constexpr (spec_base(SPEC) == SPEC_PROP_PF) {
     // small emulators (short GP loops): the next pixel group's index and its
     // single propagated parameter's x_a / P_a,jj are loaded before this group's
     // analysis, so the forecast starts from registers instead of a dependent
-    // order -> state load chain (pixel indices < 2^31: one VGPR carried)
+    // order -> state load chain (pixel indices < 2^31: one VGPR carried).
+    // wave_tiles' walk with that read-ahead carried across its iterations.
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    const int64_t nv = visit_count(a);
     const KF_CONST_AS PropArgs* pa = cptr(a.prop);
     const int pj = prop_single(pa->prop_mask);
     int64_t base = (int64_t)blockIdx.x * BS + (threadIdx.x - lane);
@@ -151,10 +196,7 @@ __device__ __forceinline__ void analysis_mfma_body(const AnalysisArgs& a) {
       float dn1;
       const float dn = pixel_analysis_mfma<NP, D, FOBS, false, false, LAYOUT, IL, SPEC, MIXLO>(
           a, p, act, gpm_lds, dn1 KF_PHASE_ARG, pj, px, pp);
-      {
-        float* dno = opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->dn_out;
-        if (act && dno) KF_PX(dno, 0, p) = dn;
-      }
+      store_dn_out(p, act, dn);
       acc += act ? (double)dn : 0.0;
       acc1 += act ? (double)dn1 : 0.0;
       p32 = pn;
@@ -162,23 +204,14 @@ __device__ __forceinline__ void analysis_mfma_body(const AnalysisArgs& a) {
       pp = ppn;
     }
   } else {
-    for (int64_t base = (int64_t)blockIdx.x * BS + (threadIdx.x - lane); base < nv; base += stride) {
-      const int64_t q = base + lane;
-      const bool act = q < nv;
-      const int64_t p = visit_px(a.order, act ? q : nv - 1);
-      float dn1;
+    wave_tiles<BS>(a, acc, acc1, [&](int64_t p, bool act, float& dn1) {
       const float dn = pixel_analysis_mfma<NP, D, FOBS, false, false, LAYOUT, IL, SPEC, MIXLO>(a, p, act, gpm_lds,
                                                                                               dn1 KF_PHASE_ARG);
-      {
-        // re-read through the opaque kernarg pointer: not pinned in SGPRs across the GP loop
-        float* dno = opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->dn_out;
-        if (act && dno) KF_PX(dno, 0, p) = dn;
-      }
-      acc += act ? (double)dn : 0.0;
-      acc1 += act ? (double)dn1 : 0.0;
-    }
+      store_dn_out(p, act, dn);
+      return dn;
+    });
   }
-  analysis_partials<BS>(a, acc, acc1);
+  launch_partials<BS>(a, acc, acc1);
   KF_PHASE_KERNEL_END
 #endif
 }
@@ -204,40 +237,17 @@ __global__ __launch_bounds__(BLOCK, 3) void analysis_tip_sl_kernel(AnalysisArgs 
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ kf_h8 gpm_lds[];
   KF_PHASE_KERNEL_BEGIN
-  {
-    int off = 0;
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi) {
-      const KF_CONST_AS BandDesc* bd = cptr(a.bands) + bi;
-      const int n = bd->gpm_nchunk * gpm_frags_per_chunk(4);
-      const kf_h8* src = (const kf_h8*)bd->gpm;
-      for (int i = threadIdx.x; i < n; i += BLOCK) gpm_lds[off + i] = src[i];
-      off += n;
-    }
-    if (threadIdx.x == 0) gpm_lds[a.gpm_frags - 1] = kf_h8{};   // shared zero fragment
-  }
-  __syncthreads();
+  stage_tables<BLOCK, 4>(a, 2, gpm_lds);
   KF_PHASE(KF_PH_PROLOGUE)
   double acc = 0.0, acc1 = 0.0;
-  const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  const int64_t nv = visit_count(a);
-  for (int64_t base = (int64_t)blockIdx.x * BLOCK + (threadIdx.x - lane); base < nv; base += stride) {
-    const int64_t q = base + lane;
-    const bool act = q < nv;
-    const int64_t p = visit_px(a.order, act ? q : nv - 1);
+  wave_tiles<BLOCK>(a, acc, acc1, [&](int64_t p, bool act, float& dn1) {
     const KF_CONST_AS AnalysisArgs* ka = opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr());
     const TipGroup g = tip_group_load<OUT>(&ka->tc, p);
-    float dn1;
     const float dn = pixel_analysis_tip_sl<IL, ROWS, OUT>(p, act, g, gpm_lds, dn1 KF_PHASE_ARG);
-    {
-      float* dno = opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->dn_out;
-      if (act && dno) KF_PX(dno, 0, p) = dn;
-    }
-    acc += act ? (double)dn : 0.0;
-    acc1 += act ? (double)dn1 : 0.0;
-  }
-  analysis_partials<BLOCK>(a, acc, acc1);
+    store_dn_out(p, act, dn);
+    return dn;
+  });
+  launch_partials<BLOCK>(a, acc, acc1);
   KF_PHASE_KERNEL_END
 #endif
 }
@@ -253,25 +263,13 @@ __device__ __forceinline__ void analysis_mfma_g_body(const AnalysisArgs& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   KF_PHASE_KERNEL_BEGIN
   double acc = 0.0, acc1 = 0.0;
-  const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  const int64_t nv = visit_count(a);
-  for (int64_t base = (int64_t)blockIdx.x * BLOCK + (threadIdx.x - lane); base < nv; base += stride) {
-    const int64_t q = base + lane;
-    const bool act = q < nv;
-    const int64_t p = visit_px(a.order, act ? q : nv - 1);
-    float dn1;
+  wave_tiles<BLOCK>(a, acc, acc1, [&](int64_t p, bool act, float& dn1) {
     const float dn = pixel_analysis_mfma<NP, D, FOBS, true, PF, BAND_LAYOUT_RUNTIME, IL, SPEC, MIXLO>(
         a, p, act, nullptr, dn1 KF_PHASE_ARG);
-    {
-      // re-read through the opaque kernarg pointer: not pinned in SGPRs across the GP loop
-      float* dno = opaque((const KF_CONST_AS AnalysisArgs*)__builtin_amdgcn_kernarg_segment_ptr())->dn_out;
-      if (act && dno) KF_PX(dno, 0, p) = dn;
-    }
-    acc += act ? (double)dn : 0.0;
-    acc1 += act ? (double)dn1 : 0.0;
-  }
-  analysis_partials(a, acc, acc1);
+    store_dn_out(p, act, dn);
+    return dn;
+  });
+  launch_partials(a, acc, acc1);
   KF_PHASE_KERNEL_END
 #endif
 }
@@ -295,33 +293,12 @@ template <int NP, int D, int FOBS, bool MIXLO>
 __device__ __forceinline__ void gain_mfma_body(const GainArgs& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ kf_h8 gpm_lds[];
-  {
-    int off = 0;
-    for (int bi = 0; bi < a.n_bands; ++bi) {
-      const KF_CONST_AS BandDesc* bd = cptr(a.bands) + bi;
-      const int n = bd->gpm_nchunk * gpm_frags_per_chunk(D);
-      const kf_h8* src = (const kf_h8*)bd->gpm;
-      for (int i = threadIdx.x; i < n; i += BLOCK) gpm_lds[off + i] = src[i];
-      off += n;
-    }
-    if (threadIdx.x == 0) gpm_lds[a.gpm_frags - 1] = kf_h8{};   // shared zero fragment
-  }
-  __syncthreads();
+  stage_tables<BLOCK, D>(a, a.n_bands, gpm_lds);
   double acc = 0.0, acc1 = 0.0;
-  const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  const int64_t nv = visit_count(a);
-  for (int64_t base = (int64_t)blockIdx.x * BLOCK + (threadIdx.x - lane); base < nv; base += stride) {
-    const int64_t q = base + lane;
-    const bool act = q < nv;
-    const int64_t p = visit_px(a.order, act ? q : nv - 1);
-    float dn1;
-    const float dn = pixel_gain_mfma<NP, D, FOBS, false, false, MIXLO>(a, p, act, gpm_lds, dn1);
-    acc += act ? (double)dn : 0.0;
-    acc1 += act ? (double)dn1 : 0.0;
-  }
-  if (a.partials_first) block_partials2<BLOCK>(acc, acc1, a.partials, a.partials_first);
-  else if (a.partials) block_partial(acc, a.partials);
+  wave_tiles<BLOCK>(a, acc, acc1, [&](int64_t p, bool act, float& dn1) {
+    return pixel_gain_mfma<NP, D, FOBS, false, false, MIXLO>(a, p, act, gpm_lds, dn1);
+  });
+  launch_partials(a, acc, acc1);
 #endif
 }
 
@@ -350,20 +327,10 @@ __device__ __forceinline__ void gain_mfma_g_body(const GainArgs& a) {
   static_assert(BLOCK / 64 == GPM_G_WAVES, "per-wave LDS transpose buffers of gp_mfma_sums_g_xb");
 #if defined(__HIP_DEVICE_COMPILE__)
   double acc = 0.0, acc1 = 0.0;
-  const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  const int64_t nv = visit_count(a);
-  for (int64_t base = (int64_t)blockIdx.x * BLOCK + (threadIdx.x - lane); base < nv; base += stride) {
-    const int64_t q = base + lane;
-    const bool act = q < nv;
-    const int64_t p = visit_px(a.order, act ? q : nv - 1);
-    float dn1;
-    const float dn = pixel_gain_mfma<NP, D, FOBS, true, true, MIXLO>(a, p, act, nullptr, dn1);
-    acc += act ? (double)dn : 0.0;
-    acc1 += act ? (double)dn1 : 0.0;
-  }
-  if (a.partials_first) block_partials2<BLOCK>(acc, acc1, a.partials, a.partials_first);
-  else if (a.partials) block_partial(acc, a.partials);
+  wave_tiles<BLOCK>(a, acc, acc1, [&](int64_t p, bool act, float& dn1) {
+    return pixel_gain_mfma<NP, D, FOBS, true, true, MIXLO>(a, p, act, nullptr, dn1);
+  });
+  launch_partials(a, acc, acc1);
 #endif
 }
 
@@ -387,8 +354,7 @@ __global__ __launch_bounds__(BLOCK) void gain_kernel(GainArgs a) {
     acc += (double)pixel_gain<NP, FD, FOBS>(a, visit_px(a.order, q), dn1);
     acc1 += (double)dn1;
   }
-  if (a.partials_first) block_partials2<BLOCK>(acc, acc1, a.partials, a.partials_first);
-  else if (a.partials) block_partial(acc, a.partials);
+  launch_partials(a, acc, acc1);
 }
 
 // MODE < 0: runtime a.mode (prepare / classic: Cholesky-sized registers);

@@ -470,6 +470,22 @@ __device__ __forceinline__ void gpm_patch_c(kf_h8 (&xb)[2][gpm_k_steps(D)], floa
   xb[1][KK] = __builtin_bit_cast(kf_h8, b1);
 }
 
+// One band's sums from the iteration's shared operand sxb: a copy of it with
+// the band's constant patched in.  (The table pointer is read after the
+// operand is ready, as the written-out sequence did: same scalar code.)
+template <int D, bool PF, bool IL, bool MIXLO>
+__device__ __forceinline__ void gp_mfma_sums_g_sx(const KF_CONST_AS BandDesc* bdp, int nchunk,
+                                                  const kf_h8 (&sxb)[2][gpm_k_steps(D)], float c, float (&S)[D + 1]) {
+  kf_h8 xb[2][gpm_k_steps(D)];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int kk = 0; kk < gpm_k_steps(D); ++kk) xb[i][kk] = sxb[i][kk];
+  float cl;
+  gpm_patch_c<D>(xb, c, cl);
+  gp_mfma_sums_g_xb<D, PF, IL, MIXLO>(bdp->gpm, nchunk, xb, cl, S);
+}
+
 // Line tables (AnalysisArgs.line_* / GainArgs.line_*): the first Gauss-Newton
 // iteration at a partial-reset forecast sees every parameter but the
 // propagated one at the reset mean, so each band's GP value and gradient are
@@ -600,6 +616,22 @@ __device__ __forceinline__ void gpm_epilogue(const KF_CONST_AS BandDesc* q, cons
     for (int d = 0; d < D && d < NP; ++d) h[d] = fmaf(-q->coef[d] * xi[d], S0, LN2 * S[d]);
   } else {
     gp_epilogue<NP, D>(q->offset, q->coef, q->map, xi, S0, S, H0, h);
+  }
+}
+
+// Scatter of a band's input gradient g to the state through the descriptor's
+// map, into h zeroed by the caller (identity map: h[d] = g_d).
+template <int NP, int D>
+__device__ __forceinline__ void gpm_scatter(const KF_CONST_AS BandDesc* q, const float (&g)[D], float (&h)[NP]) {
+  if (q->map_identity) {
+#pragma unroll
+    for (int d = 0; d < D && d < NP; ++d) h[d] = g[d];
+  } else {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+#pragma unroll
+      for (int j = 0; j < NP; ++j) h[j] += (q->map[d] == j) ? g[d] : 0.f;
+    }
   }
 }
 
@@ -765,14 +797,7 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
       KF_PHASE(KF_PH_BAND_IN)
       if constexpr (SXC) {
         if (sx) {
-          kf_h8 xb[2][gpm_k_steps(D)];
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int kk = 0; kk < gpm_k_steps(D); ++kk) xb[i][kk] = sxb[i][kk];
-          float cl;
-          gpm_patch_c<D>(xb, c, cl);
-          gp_mfma_sums_g_xb<D, PF, IL, MIXLO>(bdp->gpm, nch, xb, cl, S);
+          gp_mfma_sums_g_sx<D, PF, IL, MIXLO>(bdp, nch, sxb, c, S);
         } else {
           gp_mfma_sums_g<D, PF, IL, MIXLO>(bdp->gpm, nch, xi, c, S);
         }
@@ -807,19 +832,9 @@ __device__ __forceinline__ float pixel_analysis_mfma(const AnalysisArgs& a, int6
       } else {
         // scatter to the state (identity map: h[d] = g_d)
         float h[NP];
-        const KF_CONST_AS BandDesc* q = opaque(bdp);
 #pragma unroll
         for (int j = 0; j < NP; ++j) h[j] = 0.f;
-        if (q->map_identity) {
-#pragma unroll
-          for (int d = 0; d < D && d < NP; ++d) h[d] = g[d];
-        } else {
-#pragma unroll
-          for (int d = 0; d < D; ++d) {
-#pragma unroll
-            for (int j = 0; j < NP; ++j) h[j] += (q->map[d] == j) ? g[d] : 0.f;
-          }
-        }
+        gpm_scatter<NP, D>(opaque(bdp), g, h);
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
           const float wh = w * h[i];
@@ -1259,17 +1274,7 @@ __device__ __forceinline__ float pixel_gain_mfma(const GainArgs& a, int64_t p, b
       if (__all(lp.in || !use)) {
         float g[D];
         line_eval<D>(lp.row + bi * (D + 1) * 4, lp.s, H0, g);
-        const KF_CONST_AS BandDesc* q = opaque(bdp);
-        if (q->map_identity) {
-#pragma unroll
-          for (int d = 0; d < D && d < NP; ++d) h[d] = g[d];
-        } else {
-#pragma unroll
-          for (int d = 0; d < D; ++d) {
-#pragma unroll
-            for (int j = 0; j < NP; ++j) h[j] += (q->map[d] == j) ? g[d] : 0.f;
-          }
-        }
+        gpm_scatter<NP, D>(opaque(bdp), g, h);
         tabled = true;
         ok = finitef(H0);
 #pragma unroll
@@ -1292,14 +1297,7 @@ __device__ __forceinline__ float pixel_gain_mfma(const GainArgs& a, int64_t p, b
               gpm_operands<D>(xi, 0.f, sxb, c0);
               sx_it = it;
             }
-            kf_h8 xb[2][gpm_k_steps(D)];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-              for (int kk = 0; kk < gpm_k_steps(D); ++kk) xb[i][kk] = sxb[i][kk];
-            float cl;
-            gpm_patch_c<D>(xb, c, cl);
-            gp_mfma_sums_g_xb<D, false, IL, MIXLO>(bdp->gpm, nch, xb, cl, S);
+            gp_mfma_sums_g_sx<D, false, IL, MIXLO>(bdp, nch, sxb, c, S);
           }
         }
         if (!sx) gp_mfma_sums_g<D, false, IL, MIXLO>(bdp->gpm, nch, xi, c, S);

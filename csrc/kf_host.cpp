@@ -40,51 +40,47 @@ static void grid_stride(int64_t N, int grid, double* partials, F&& f) {
   }
 }
 
-template <int NP>
-static int h_analysis(const AnalysisArgs& a, int grid) {
+// The same mapping over the visiting slots q of a K1 / K1g launch (pixel
+// order[q], visit_count slots), with both norm accumulators of a fused
+// two-iteration launch: f(p, dn1) -> dn.
+template <typename A, typename F>
+static void grid_stride_visit(const A& a, int grid, F&& f) {
   const int64_t stride = (int64_t)grid * HBLOCK;
   const int64_t nv = visit_count(a);
-  // JRC-TIP structure of the fused forecast's precision (AnalysisArgs.a_struct,
-  // checked by the caller): the structure-aware solve, as the SPEC_*_TIP kernels
-  const bool tip = NP == 7 && (a.a_struct & A_STRUCT_TIP) && a.prop && a.variant != AV_DENSE_SOLVE;
 #pragma omp parallel for schedule(dynamic, 4)
   for (int b = 0; b < grid; ++b) {
     double acc = 0.0, acc1 = 0.0;
     for (int t = 0; t < HBLOCK; ++t)
       for (int64_t q = (int64_t)b * HBLOCK + t; q < nv; q += stride) {
         float dn1;
-        const int64_t p = visit_px(a.order, q);
-        float dn;
-        if constexpr (NP == 7) {
-          dn = tip ? pixel_analysis<NP, 0, 0, 4, false, StructTip>(a, p, dn1) : pixel_analysis<NP>(a, p, dn1);
-        } else {
-          dn = pixel_analysis<NP>(a, p, dn1);
-        }
-        if (a.dn_out) a.dn_out[p] = dn;
-        acc += (double)dn;
+        acc += (double)f(visit_px(a.order, q), dn1);
         acc1 += (double)dn1;
       }
     if (a.partials) a.partials[b] = acc;
     if (a.partials_first) a.partials_first[b] = acc1;
   }
+}
+
+template <int NP>
+static int h_analysis(const AnalysisArgs& a, int grid) {
+  // JRC-TIP structure of the fused forecast's precision (AnalysisArgs.a_struct,
+  // checked by the caller): the structure-aware solve, as the SPEC_*_TIP kernels
+  const bool tip = NP == 7 && (a.a_struct & A_STRUCT_TIP) && a.prop && a.variant != AV_DENSE_SOLVE;
+  grid_stride_visit(a, grid, [&](int64_t p, float& dn1) {
+    float dn;
+    if constexpr (NP == 7) {
+      dn = tip ? pixel_analysis<NP, 0, 0, 4, false, StructTip>(a, p, dn1) : pixel_analysis<NP>(a, p, dn1);
+    } else {
+      dn = pixel_analysis<NP>(a, p, dn1);
+    }
+    if (a.dn_out) a.dn_out[p] = dn;
+    return dn;
+  });
   return 0;
 }
 template <int NP>
 static int h_gain(const GainArgs& a, int grid) {
-  const int64_t stride = (int64_t)grid * HBLOCK;
-  const int64_t nv = visit_count(a);
-#pragma omp parallel for schedule(dynamic, 4)
-  for (int b = 0; b < grid; ++b) {
-    double acc = 0.0, acc1 = 0.0;
-    for (int t = 0; t < HBLOCK; ++t)
-      for (int64_t q = (int64_t)b * HBLOCK + t; q < nv; q += stride) {
-        float dn1;
-        acc += (double)pixel_gain<NP>(a, visit_px(a.order, q), dn1);
-        acc1 += (double)dn1;
-      }
-    if (a.partials) a.partials[b] = acc;
-    if (a.partials_first) a.partials_first[b] = acc1;
-  }
+  grid_stride_visit(a, grid, [&](int64_t p, float& dn1) { return pixel_gain<NP>(a, p, dn1); });
   return 0;
 }
 template <int NP>

@@ -434,6 +434,85 @@ def gp_operator_supported(n_params, d) -> bool:
     return bool(ext().gp_operator_supported(int(n_params), int(d)))
 
 
+# ------------------------------------------------ launch options shared by K1 / K1g / K9
+# One copy of the validation and field setting that analysis(), gain() and
+# reg_finish() have in common; each raises ValueError where any of them did.
+def _check_rows(rows, N, dev, ld):
+    """SoA operands ``(tensor or None, rows, name)``: [rows, ld] each, one ld."""
+    for t, r, nm in rows:
+        _check_soa(t, r, N, nm, device=dev)
+    for t, _, _ in rows:
+        if t is not None and t.shape[1] != ld:
+            raise ValueError("all SoA operands must share the leading dimension")
+
+
+def _check_prop(prop, N, ld, dev):
+    """The fused-forecast handle (:func:`prop_args` with ``fused=True``) against the launch."""
+    if prop is None:
+        return
+    if prop.args.ld != ld or prop.args.N < N or prop.device != dev:
+        raise ValueError("fused propagation arguments do not match the launch's layout/device")
+    if not prop.fused:
+        raise ValueError("prop=... needs prop_args(..., fused=True)")
+
+
+def _check_partials(N, gn_fused, partials_first):
+    if gn_fused not in (1, 2):
+        raise ValueError("gn_fused must be 1 or 2")
+    if partials_first is not None and (partials_first.dtype != torch.float64 or partials_first.numel() < grid_for(N)):
+        raise ValueError("partials_first must be float64 with >= grid_for(N) entries")
+
+
+def _set_rasters(a, out, n_params, N, dev, x_alias=None, mean_elsewhere=False):
+    """``out = (mean, unc, idx)``: the fused output rasters [n_params, plane] and
+    their map (int64 [N]; None: identity).  A None mean means the state's x is
+    the mean raster (DeviceOutput alias: ``x_alias`` in the raster's plane under
+    the identity map), unless another launch writes it (``mean_elsewhere``)."""
+    mean, unc, idx = out
+    if mean is None and unc is None:
+        raise ValueError("out = (mean, unc, idx) needs a raster")
+    plane = (mean if unc is None else unc).shape[1]
+    if mean is None and not mean_elsewhere and (idx is not None or x_alias is None or x_alias.shape[1] != plane):
+        raise ValueError("out mean None needs the identity map and x_out of the raster's plane")
+    for t, nm in ((mean, "out mean"), (unc, "out unc")):
+        if t is None:
+            continue
+        _check_soa(t, n_params, 0, nm, device=dev)
+        if t.shape[1] != plane:
+            raise ValueError("out mean / unc planes differ")
+    if idx is not None:
+        _check_vec(idx, N, "out idx", torch.int64, dev)
+    elif plane < N:
+        raise ValueError("identity output needs plane >= N")
+    a.out_mean, a.out_unc, a.out_idx, a.out_plane = _ptr(mean), _ptr(unc), _ptr(idx), plane
+
+
+def _set_visit(a, N, dev, order, n_visit, n_visit_dev, dn_out, subset_ok):
+    """``order`` / ``n_visit`` / ``n_visit_dev`` / ``dn_out`` (:func:`analysis`);
+    returns the slot count that sizes the grid.  ``subset_ok``: the launch is one
+    that may visit a subset (a single iteration, no regulariser)."""
+    if order is not None:
+        _check_vec(order, N, "order", torch.int32, dev)
+        a.order = _ptr(order)
+    nv = N
+    if n_visit is not None:
+        nv = int(n_visit)
+        if order is None or not 0 < nv <= N:
+            raise ValueError(f"n_visit={n_visit} needs an order and 0 < n_visit <= N={N}")
+        if not subset_ok:
+            raise ValueError("n_visit: single-iteration launches without the regulariser")
+        a.n_visit = nv
+    if n_visit_dev is not None:
+        if n_visit is None:
+            raise ValueError("n_visit_dev needs n_visit (the bound that sizes the grid)")
+        _check_vec(n_visit_dev, 1, "n_visit_dev", torch.int32, dev)
+        a.n_visit_dev = _ptr(n_visit_dev)
+    if dn_out is not None:
+        _check_vec(dn_out, N, "dn_out", torch.float32, dev)
+        a.dn_out = _ptr(dn_out)
+    return nv
+
+
 def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=None, b_out=None, status=None,
              partials=None, N=None, solve=True, fast=True, variant=None, a_in=None, b_in=None, prop=None,
              out=None, reg=None, x0_out=None, gn_fused=1, partials_first=None, order=None, n_visit=None,
@@ -510,30 +589,20 @@ def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=
         raise ValueError("x_prev, x_f and pf_inv are required unless the propagation is fused")
     if prop is not None and (x_f is not None or pf_inv is not None or a_in is not None):
         raise ValueError("fused propagation replaces x_f/pf_inv and excludes a_in")
-    for t, r, nm in ((x_prev, n_params, "x_prev"), (x_f, n_params, "x_f"), (pf_inv, nt, "pf_inv"),
-                     (x_out, n_params, "x_out"), (a_out, nt, "a_out"), (b_out, n_params, "b_out")):
-        _check_soa(t, r, N, nm, device=dev)
     ld = ref.shape[1]
-    for t in (x_prev, x_f, pf_inv, x_out, a_out, b_out):
-        if t is not None and t.shape[1] != ld:
-            raise ValueError("all SoA operands must share the leading dimension")
-    if prop is not None and (prop.args.ld != ld or prop.args.N < N or prop.device != dev):
-        raise ValueError("fused propagation arguments do not match the analysis layout/device")
-    if prop is not None and not prop.fused:
-        raise ValueError("analysis(prop=...) needs prop_args(..., fused=True)")
+    _check_rows(((x_prev, n_params, "x_prev"), (x_f, n_params, "x_f"), (pf_inv, nt, "pf_inv"),
+                 (x_out, n_params, "x_out"), (a_out, nt, "a_out"), (b_out, n_params, "b_out")), N, dev, ld)
+    _check_prop(prop, N, ld, dev)
     if solve and x_out is None:
         raise ValueError("solve=True needs x_out")
     _check_vec(status, N, "status", torch.uint8, dev)
     if partials is not None and (partials.dtype != torch.float64 or partials.numel() < grid_for(N)):
         raise ValueError("partials must be float64 with >= grid_for(N) entries")
-    if gn_fused not in (1, 2):
-        raise ValueError("gn_fused must be 1 or 2")
+    _check_partials(N, gn_fused, partials_first)
     if gn_fused == 2 and (a_in is not None or not solve):
         raise ValueError("gn_fused=2 runs the solve path only (no band chunks or solve=False)")
     if gn_fused == 2 and reg is not None and x0_out is None:
         raise ValueError("gn_fused=2 with reg needs x0_out (x_1, the second iteration's linearisation point)")
-    if partials_first is not None and (partials_first.dtype != torch.float64 or partials_first.numel() < grid_for(N)):
-        raise ValueError("partials_first must be float64 with >= grid_for(N) entries")
     a = ext().AnalysisArgs()
     a.N, a.ld, a.n_bands, a.solve = N, ld, bands.n, int(bool(solve))
     a.gn_fused = int(gn_fused)
@@ -564,21 +633,7 @@ def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=
             raise ValueError("fused output needs solve=True")
         if unc is None or (reg is not None and mean is not None):
             raise ValueError("out = (mean, unc, idx); with reg the mean is None (reg_finish writes it)")
-        plane = unc.shape[1]
-        if mean is None and reg is None and (idx is not None or x_out is None or x_out.shape[1] != plane):
-            # the state's x is the mean raster (DeviceOutput alias): identity map, x's layout
-            raise ValueError("out mean None needs the identity map and x_out of the raster's plane")
-        for t, nm in ((mean, "out mean"), (unc, "out unc")):
-            if t is None:
-                continue
-            _check_soa(t, n_params, 0, nm, device=dev)
-            if t.shape[1] != plane:
-                raise ValueError("out mean / unc planes differ")
-        if idx is not None:
-            _check_vec(idx, N, "out idx", torch.int64, dev)
-        elif plane < N:
-            raise ValueError("identity output needs plane >= N")
-        a.out_mean, a.out_unc, a.out_idx, a.out_plane = _ptr(mean), _ptr(unc), _ptr(idx), plane
+        _set_rasters(a, out, n_params, N, dev, x_alias=x_out, mean_elsewhere=reg is not None)
     if x0_out is not None:
         _check_soa(x0_out, n_params, N, "x0_out", device=dev)
         if x0_out.shape[1] != ld:
@@ -601,25 +656,7 @@ def analysis(n_params, bands: BandTable, x_prev, x_f, pf_inv, x_out=None, a_out=
                 raise ValueError(f"dense geometry {geo} does not cover N={N} pixels")
             a.geo_w, a.geo_h, a.geo_halo, a.geo_n_up = int(geo["w"]), int(geo["h"]), int(geo["halo"]), \
                 int(geo["n_up"])
-    if order is not None:
-        _check_vec(order, N, "order", torch.int32, dev)
-        a.order = _ptr(order)
-    nv = N
-    if n_visit is not None:
-        nv = int(n_visit)
-        if order is None or not 0 < nv <= N:
-            raise ValueError(f"n_visit={n_visit} needs an order and 0 < n_visit <= N={N}")
-        if gn_fused != 1 or reg is not None:
-            raise ValueError("n_visit: single-iteration launches without the regulariser")
-        a.n_visit = nv
-    if n_visit_dev is not None:
-        if n_visit is None:
-            raise ValueError("n_visit_dev needs n_visit (the bound that sizes the grid)")
-        _check_vec(n_visit_dev, 1, "n_visit_dev", torch.int32, dev)
-        a.n_visit_dev = _ptr(n_visit_dev)
-    if dn_out is not None:
-        _check_vec(dn_out, N, "dn_out", torch.float32, dev)
-        a.dn_out = _ptr(dn_out)
+    nv = _set_visit(a, N, dev, order, n_visit, n_visit_dev, dn_out, gn_fused == 1 and reg is None)
     if bands.dom is not None:
         a.dom_check, a.dom_lo, a.dom_hi = 1, list(bands.dom[0]), list(bands.dom[1])
     if a_rows:
@@ -786,20 +823,12 @@ def gain(n_params, bands: BandTable, x_prev, x_f, p_f, x_out, p_out=None, status
         raise ValueError("x_prev, x_f and p_f are required unless the propagation is fused")
     if prop is not None and (x_f is not None or p_f is not None):
         raise ValueError("fused propagation replaces x_f/p_f")
-    for t, r, nm in ((x_prev, n_params, "x_prev"), (x_f, n_params, "x_f"), (p_f, nt, "p_f"),
-                     (x_out, n_params, "x_out"), (p_out, nt, "p_out")):
-        _check_soa(t, r, N, nm, device=dev)
     ld = ref.shape[1]
-    for t in (x_prev, x_f, p_f, x_out, p_out):
-        if t is not None and t.shape[1] != ld:
-            raise ValueError("all SoA operands must share the leading dimension")
-    if prop is not None and (prop.args.ld != ld or prop.args.N < N or prop.device != dev or not prop.fused):
-        raise ValueError("fused propagation arguments do not match the gain layout/device")
+    _check_rows(((x_prev, n_params, "x_prev"), (x_f, n_params, "x_f"), (p_f, nt, "p_f"),
+                 (x_out, n_params, "x_out"), (p_out, nt, "p_out")), N, dev, ld)
+    _check_prop(prop, N, ld, dev)
     _check_vec(status, N, "status", torch.uint8, dev)
-    if gn_fused not in (1, 2):
-        raise ValueError("gn_fused must be 1 or 2")
-    if partials_first is not None and (partials_first.dtype != torch.float64 or partials_first.numel() < grid_for(N)):
-        raise ValueError("partials_first must be float64 with >= grid_for(N) entries")
+    _check_partials(N, gn_fused, partials_first)
     a = ext().GainArgs()
     a.N, a.ld, a.n_bands, a.joseph = N, ld, bands.n, int(bool(joseph))
     a.fast_d, a.fast_obs = (bands.fast_d, bands.fast_obs) if fast else (0, 0)
@@ -825,39 +854,8 @@ def gain(n_params, bands: BandTable, x_prev, x_f, p_f, x_out, p_out=None, status
         mean, unc, idx = out
         if unc is None:
             raise ValueError("out = (mean, unc, idx) needs the uncertainty planes")
-        plane = unc.shape[1]
-        if mean is None and (idx is not None or x_out is None or x_out.shape[1] != plane):
-            raise ValueError("out mean None needs the identity map and x_out of the raster's plane")
-        for t, nm in ((mean, "out mean"), (unc, "out unc")):
-            if t is None:
-                continue
-            _check_soa(t, n_params, 0, nm, device=dev)
-            if t.shape[1] != plane:
-                raise ValueError("out mean / unc planes differ")
-        if idx is not None:
-            _check_vec(idx, N, "out idx", torch.int64, dev)
-        elif plane < N:
-            raise ValueError("identity output needs plane >= N")
-        a.out_mean, a.out_unc, a.out_idx, a.out_plane = _ptr(mean), _ptr(unc), _ptr(idx), plane
-    if order is not None:
-        _check_vec(order, N, "order", torch.int32, dev)
-        a.order = _ptr(order)
-    nv = N
-    if n_visit is not None:
-        nv = int(n_visit)
-        if order is None or not 0 < nv <= N:
-            raise ValueError(f"n_visit={n_visit} needs an order and 0 < n_visit <= N={N}")
-        if gn_fused != 1:
-            raise ValueError("n_visit: single-iteration launches")
-        a.n_visit = nv
-    if n_visit_dev is not None:
-        if n_visit is None:
-            raise ValueError("n_visit_dev needs n_visit (the bound that sizes the grid)")
-        _check_vec(n_visit_dev, 1, "n_visit_dev", torch.int32, dev)
-        a.n_visit_dev = _ptr(n_visit_dev)
-    if dn_out is not None:
-        _check_vec(dn_out, N, "dn_out", torch.float32, dev)
-        a.dn_out = _ptr(dn_out)
+        _set_rasters(a, out, n_params, N, dev, x_alias=x_out)
+    nv = _set_visit(a, N, dev, order, n_visit, n_visit_dev, dn_out, gn_fused == 1)
     if pdiag_rows:
         if int(pdiag_rows) >> n_params:
             raise ValueError(f"pdiag_rows has bits past the {n_params} parameters")
@@ -1135,15 +1133,12 @@ def reg_finish(n_params, u, v, z_ext, nbr, x_ref, x_out, gamma, reg_mask, N, par
     check_np(n_params)
     dev = u.device
     k = bin(int(reg_mask)).count("1")
-    _check_soa(u, n_params, N, "u", device=dev)
-    _check_soa(v, k * n_params, N, "v", device=dev)
-    _check_soa(z_ext, k, N, "z_ext", device=dev)
-    _check_soa(x_ref, n_params, N, "x_ref", device=dev)
-    _check_soa(x_out, n_params, N, "x_out", device=dev)
+    _check_soa(z_ext, k, N, "z_ext", device=dev)   # its own leading dimension (ld_ext)
     ld = u.shape[1]
-    for t in (v, x_ref, x_out):
-        if t.shape[1] != ld:
-            raise ValueError("all SoA operands must share the leading dimension")
+    if v is None or x_ref is None or x_out is None:
+        raise ValueError("u, v, x_ref and x_out are required")
+    _check_rows(((u, n_params, "u"), (v, k * n_params, "v"), (x_ref, n_params, "x_ref"), (x_out, n_params, "x_out")),
+                N, dev, ld)
     a = _reg_args(n_params, JACOBI_FINISH, N, ld, gamma, reg_mask, nbr, geo)
     a.ld_ext = z_ext.shape[1]
     a.u, a.v, a.x_ext, a.x_ref, a.x_out, a.partials = map(_ptr, (u, v, z_ext, x_ref, x_out, partials))
@@ -1156,19 +1151,8 @@ def reg_finish(n_params, u, v, z_ext, nbr, x_ref, x_out, gamma, reg_mask, N, par
             _check_soa(a_prec, ntri(n_params), N, "a_prec", device=dev)
             if a_prec.shape[1] != ld:
                 raise ValueError("a_prec must share the leading dimension")
-        plane = mean.shape[1]
-        for t, nm in ((mean, "out mean"), (unc, "out unc")):
-            if t is None:
-                continue
-            _check_soa(t, n_params, 0, nm, device=dev)
-            if t.shape[1] != plane:
-                raise ValueError("out mean / unc planes differ")
-        if idx is not None:
-            _check_vec(idx, N, "out idx", torch.int64, dev)
-        elif plane < N:
-            raise ValueError("identity output needs plane >= N")
+        _set_rasters(a, out, n_params, N, dev)   # no x_alias: this launch writes the mean
         a.a_in = _ptr(a_prec)
-        a.out_mean, a.out_unc, a.out_idx, a.out_plane = _ptr(mean), _ptr(unc), _ptr(idx), plane
     ext().jacobi(n_params, a, grid_for(N), _dev(u), _stream(u))
     _set_valid(partials, grid_for(N))
     return partials
