@@ -14,9 +14,12 @@ it to a strategy:
   (EngineConfig.convergence_chunk, engine/chunks.py), the reference drivers'
   one-LinearKalman-per-chunk semantics (kafka_test_Py36.py:147-187).
 
-Each iteration's device work goes through :meth:`_launch_iteration` (gain
-form, spatial prior, band-parallel, split GP path or the plain fused
-analysis) or :meth:`_launch_fused2` (GN 1 + 2 in one launch).
+The loops only say which iteration they queue and, per chunk, which pixels
+it visits (:class:`_Visit`); every iteration's device work in either strategy
+goes through :meth:`GaussNewtonMixin._launch`, which decides the rest from
+the run: the mode (gain form, spatial prior, band-parallel, split GP path or
+the plain fused analysis), GN 1 + 2 in one launch, the stored precision and
+output rasters, the norm sinks and the forecast operands.
 """
 from __future__ import annotations
 
@@ -35,10 +38,10 @@ LOG = logging.getLogger(__name__.rsplit(".", 1)[0] + ".linear_kf.linear_kf")
 @dataclass
 class _GNRun:
     """One date's Gauss-Newton problem as set up by do_all_bands_state: the
-    operators, the forecast (fused ``prop`` or materialised ``fc``), the
-    state / precision / status buffers and the launch options the iteration
-    strategies (_gn_global, _gn_chunked) and the per-mode launches share."""
-    timestep: object
+    operators, the forecast operands (``x_f``, ``P_f``, or None, None and the
+    fused ``prop``), the state / precision / status buffers and the launch
+    options the iteration strategies (_gn_global, _gn_chunked) and the
+    per-mode launches share."""
     specs: list
     dbs: list
     table: object
@@ -47,7 +50,8 @@ class _GNRun:
     bp: bool
     split: object
     prop: object
-    fc: object
+    x_f: object
+    P_f: object
     x_prev: object
     x_new: object
     P_out: object
@@ -63,6 +67,25 @@ class _GNRun:
     fuse_sp: bool
     first_plain: bool
     static_conv: bool
+
+
+@dataclass
+class _Visit:
+    """What the per-chunk loop varies per launch: the pixels visited
+    (``order[:n_visit]``; n_visit None: all; ``n_visit_dev``: the count read on
+    the device, n_visit then only a bound) and the per-pixel norm sink
+    (``dn_out``; None on a statically converged date)."""
+    order: object
+    n_visit: object
+    n_visit_dev: object
+    dn_out: object
+
+
+def _swap(x_prev, x_new):
+    """The iterate ping-pong: the next iteration linearises at x_new and
+    writes over x_prev (allocated here after a first iteration at the fused
+    forecast, which has no x_prev)."""
+    return x_new, (x_prev if x_prev is not None else torch.empty_like(x_new))
 
 
 class GaussNewtonMixin:
@@ -116,19 +139,14 @@ class GaussNewtonMixin:
         norms, deferred = [], []
         x_prev, x_new = run.x_prev, run.x_new
         while True:
-            # the analysis precision is only needed from the iteration that can
-            # end the loop on: skip its 4*ntri B/px store before min_iterations
-            A_keep = run.P_out if n_iter >= cfg.min_iterations else None
-            out_now = run.out_t if n_iter >= cfg.min_iterations else None
-            if run.precomp:
-                pre = self._precompute_host(run.specs, run.dbs, x_prev)
-                run.table = build_table(run.specs, run.dbs, self.n_params, self._cache, self.device, run.h0_outs, pre)
-            if run.fuse2 or run.fuse_sp:
+            self._rebuild_table(run, x_prev)
+            fused = run.fuse2 or run.fuse_sp
+            if fused:
                 # iterations 1 + 2 in one launch: outputs of iteration 2 (which can end the loop)
                 red2 = self._red_hist[1:3]
                 with self.timer.phase("analysis"):
                     if N:
-                        self._launch_fused2(run, x_prev, x_new)
+                        self._launch(run, x_prev, x_new, n_iter, True)
                         K.reduce_partials(self._partials1, red2[0:1])
                         K.reduce_partials(self._partials, red2[1:2])
                     else:
@@ -139,21 +157,10 @@ class GaussNewtonMixin:
                 deferred.append((1, pend2.column(0)))
                 pend = pend2.column(1)
                 n_iter = 2
-                x_prev, x_new = x_new, (x_prev if x_prev is not None else torch.empty_like(x_new))
-                if run.static_conv and not self._norms_needed_now():
-                    # norm 2 is exactly 0: converged.  Norm 1 is read after the
-                    # next launch is queued (no host wait between the steps)
-                    if self._lookahead_fn is not None:
-                        self._lookahead_fn()
-                        self._lookahead_fn = None
-                    self._resolve_lazy_norms()
-                    norms = [None, 0.0]
-                    self._lazy_norms.append((norms, deferred[0][1], pend, run.len_x, run.n_bands))
-                    return x_prev, n_iter, norms
             else:
                 with self.timer.phase("analysis"):
                     if N:
-                        self._launch_iteration(run, n_iter, x_prev, x_new, A_keep, out_now)
+                        self._launch(run, x_prev, x_new, n_iter, False)
                 red = self._red_hist[min(n_iter, self._red_hist.numel() - 1):][:1]
                 with self.timer.phase("analysis"):
                     if N:
@@ -162,17 +169,22 @@ class GaussNewtonMixin:
                         red.zero_()
                 with self.timer.phase("converge"):
                     pend = self.comm.sum_f64_async(red)
-                x_prev, x_new = x_new, (x_prev if x_prev is not None else torch.empty_like(x_new))
+            x_prev, x_new = _swap(x_prev, x_new)
+            if fused and run.static_conv and not self._norms_needed_now():
+                # norm 2 is exactly 0: converged.  Norm 1 is read after the
+                # next launch is queued (no host wait between the steps)
+                self._run_lookahead()
+                self._resolve_lazy_norms()
+                norms = [None, 0.0]
+                self._lazy_norms.append((norms, deferred[0][1], pend, run.len_x, run.n_bands))
+                return x_prev, n_iter, norms
             if n_iter < cfg.min_iterations:
                 # this iteration cannot end the loop (n_iter <= max_iterations too):
                 # queue the next one without waiting for the norm
                 deferred.append((n_iter, pend))
                 n_iter += 1
                 continue
-            if self._lookahead_fn is not None:
-                # host preparation of the next date runs under this iteration's kernels
-                self._lookahead_fn()
-                self._lookahead_fn = None
+            self._run_lookahead()
             self._resolve_lazy_norms()
             for it, pd in deferred:
                 norms.append(self._log_norm(pd.result(), run.len_x, run.n_bands, it))
@@ -186,51 +198,60 @@ class GaussNewtonMixin:
                 return x_prev, n_iter, norms
             n_iter += 1
 
-    def _launch_fused2(self, run: "_GNRun", x_prev, x_new):
-        """GN iterations 1 and 2 in one launch (the plain analysis, or the plain
-        first iteration with the regularised prepare of the second)."""
-        n, N, prop, fc = self.n_params, self.N, run.prop, run.fc
-        if run.gain:
-            fx, fP = (None, None) if prop is not None else (fc.x, fc.P)
-            K.gain(n, run.table, x_prev, fx, fP, x_new, run.P_out, run.status, self._partials, N=N,
-                   joseph=self.config.joseph, prop=prop, out=run.out_t, gn_fused=2, partials_first=self._partials1,
-                   order=run.order, pdiag_rows=run.pdiag_rows, line=self._line_opt)
-        elif run.fuse_sp:
-            self._regularised_iteration(run.table, x_prev, fc, x_new, run.P_out, run.status, prop, run.out_t,
-                                        final=True, partials_first=self._partials1, a_rows=run.a_rows)
-        else:
-            K.analysis(n, run.table, x_prev, None if prop is not None else fc.x, None if prop is not None else fc.P,
-                       x_new, run.P_out, None, run.status, self._partials, N=N, prop=prop, out=run.out_t,
-                       gn_fused=2, partials_first=self._partials1, order=run.order, a_rows=run.a_rows,
-                       line=self._line_opt)
+    def _run_lookahead(self):
+        """The next date's host preparation (LinearKalman._prepare_date), once,
+        under the kernels just queued: called after the launch that can end
+        the loop and before the first blocking read of a norm or decision."""
+        if self._lookahead_fn is not None:
+            self._lookahead_fn()
+            self._lookahead_fn = None
 
-    def _launch_iteration(self, run: "_GNRun", n_iter, x_prev, x_new, A_keep, out_now):
-        """One Gauss-Newton iteration's device work, by mode: the gain form
-        (K1g), the spatial prior's plain first iteration or regularised solve
-        (K9 + C2), band-parallel (C5), the split GP path, or the plain fused
-        analysis (K1)."""
+    def _rebuild_table(self, run: "_GNRun", x_prev):
+        """OP_PRECOMP bands (reference-protocol factories): evaluate them on the
+        host at this iteration's linearisation point and rebuild the band
+        table into ``run.table``, where the launches and the Hessian pass
+        after the loop read it."""
+        if run.precomp:
+            pre = self._precompute_host(run.specs, run.dbs, x_prev)
+            run.table = build_table(run.specs, run.dbs, self.n_params, self._cache, self.device, run.h0_outs, pre)
+
+    def _launch(self, run: "_GNRun", x_prev, x_new, n_iter, fused, visit: "_Visit | None" = None):
+        """One Gauss-Newton iteration's device work (``fused``: iterations 1
+        and 2 in one launch), by mode: the gain form (K1g), the spatial prior's
+        plain first iteration or regularised solve (K9 + C2), band-parallel
+        (C5), the split GP path, or the plain fused analysis (K1).  ``visit``:
+        the per-chunk loop's visiting subset and per-pixel norms; without it
+        the launch visits every pixel and writes the tile-wide norm partials."""
         cfg = self.config
-        n, N, prop, fc, table = self.n_params, self.N, run.prop, run.fc, run.table
-        fx, fP = (None, None) if prop is not None else (fc.x, fc.P)
+        n = self.n_params
+        # the analysis precision and the output rasters are only needed from the
+        # iteration that can end the loop on: skip the 4*ntri B/px store before
+        # min_iterations.  The fused pair always stores (min_iterations > 2 too)
+        store = fused or n_iter >= cfg.min_iterations
+        P_out, out = (run.P_out, run.out_t) if store else (None, None)
+        if visit is None:
+            partials, first = self._partials, self._partials1 if fused else None
+            kw = dict(order=run.order)
+        else:
+            partials, first = None, None
+            kw = dict(order=visit.order, n_visit=visit.n_visit, n_visit_dev=visit.n_visit_dev, dn_out=visit.dn_out)
+        kw.update(N=self.N, prop=run.prop, gn_fused=2 if fused else 1, partials_first=first, line=self._line_opt)
         if run.gain:
-            K.gain(n, table, x_prev, fx, fP, x_new, A_keep, run.status, self._partials, N=N, joseph=cfg.joseph,
-                   prop=prop, out=out_now, order=run.order, pdiag_rows=run.pdiag_rows if A_keep is not None else 0,
-                   line=self._line_opt)
-        elif run.first_plain and n_iter == 1:
+            K.gain(n, run.table, x_prev, run.x_f, run.P_f, x_new, P_out, run.status, partials, joseph=cfg.joseph,
+                   out=out, pdiag_rows=run.pdiag_rows if store else 0, **kw)
+        elif run.first_plain and n_iter == 1 and not fused:
             # the unfused form of fuse_sp's first iteration (same kernel path)
-            K.analysis(n, table, x_prev, fx, fP, x_new, None, None, run.status, self._partials, N=N, prop=prop,
-                       order=run.order, line=self._line_opt)
+            K.analysis(n, run.table, x_prev, run.x_f, run.P_f, x_new, None, None, run.status, partials, **kw)
             self._reg_log.append({"solver": "plain", "rho": 0.0, "sweeps": 0, "r2": None, "count": 0})
         elif cfg.spatial_gamma > 0:
-            self._regularised_iteration(table, x_prev, fc, x_new, A_keep, run.status, prop, out_now,
-                                        final=n_iter >= cfg.min_iterations, a_rows=run.a_rows)
+            self._regularised_iteration(run, x_prev, x_new, P_out, out, final=store, partials_first=first)
         elif run.bp:
-            self._band_parallel_iteration(table, x_prev, fc, x_new, A_keep, run.status)
+            self._band_parallel_iteration(run, x_prev, x_new, P_out, visit)
         elif run.split is not None:
-            self._split_iteration(run.split, x_prev, fc, x_new, A_keep, run.status)
+            self._split_iteration(run, x_prev, x_new, P_out)
         else:
-            K.analysis(n, table, x_prev, fx, fP, x_new, A_keep, None, run.status, self._partials, N=N, prop=prop,
-                       out=out_now, order=run.order, a_rows=run.a_rows, line=self._line_opt)
+            K.analysis(n, run.table, x_prev, run.x_f, run.P_f, x_new, P_out, None, run.status, partials, out=out,
+                       a_rows=run.a_rows, **kw)
 
     def _chunk_state(self):
         from .chunks import ChunkConvergence
@@ -254,62 +275,37 @@ class GaussNewtonMixin:
         largest chunk's iteration count, the largest tested norm per
         iteration)."""
         cfg = self.config
-        n, N = self.n_params, self.N
-        table, specs, dbs, precomp, prop, fc = run.table, run.specs, run.dbs, run.precomp, run.prop, run.fc
-        x_prev, x_new, P_out, status, order, out_t = run.x_prev, run.x_new, run.P_out, run.status, run.order, run.out_t
-        h0_outs, a_rows, gain = run.h0_outs, run.a_rows, run.gain
+        N = self.N
         cc = self._chunk_state()
-        fx, fP = (None, None) if prop is not None else (fc.x, fc.P)
-        fuse = (cfg.fuse_gn and not precomp and not run.bp and cfg.min_iterations >= 2 and cfg.max_iterations >= 1
-                and not (prop is None and fc is None))
         # linear operators: iteration 2 repeats iteration 1 exactly, so every
         # chunk's norm is 0 and every chunk stops at iteration 2 -- the decision
-        # is known without the per-chunk norms' read-back
-        static = fuse and run.static_conv and not self._norms_needed_now()
+        # is known without the per-chunk norms' read-back (static_conv implies
+        # the fused first launch, run.fuse2)
+        static = run.static_conv and not self._norms_needed_now()
         if not static and not cc.ready:
             cc.begin()          # (normally queued at the end of the previous date, off this date's host path)
-        n_iter, n_visit, vis, full = 1, N, order, True
+        x_prev, x_new = run.x_prev, run.x_new
+        n_iter, n_visit, vis, full = 1, N, run.order, True
         norms = []
         # the tail past the first decision that keeps chunks iterating: up to
         # ``gn_lookahead`` iterations queued ahead of the read-backs, each
         # launch / compaction reading its pixel count on the device (n_dev);
         # n_visit stays a host bound (the last count read: counts only shrink)
-        depth = cfg.gn_lookahead if not (run.bp or precomp) else 0
+        depth = cfg.gn_lookahead if not (run.bp or run.precomp) else 0
         pending = []            # (iteration, its decision) not read yet
         tail, n_dev, n_end = False, None, None
         while True:
-            A_keep = P_out if n_iter >= cfg.min_iterations else None
-            out_now = out_t if n_iter >= cfg.min_iterations else None
-            if precomp:
-                pre = self._precompute_host(specs, dbs, x_prev)
-                table = build_table(specs, dbs, n, self._cache, self.device, h0_outs, pre)
-            kw = dict(prop=prop, order=vis, dn_out=None if static else cc.dn)
-            if not full:
-                kw["n_visit"] = n_visit
-                if n_dev is not None:
-                    kw["n_visit_dev"] = n_dev
+            self._rebuild_table(run, x_prev)
+            fused = run.fuse2 and n_iter == 1
             with self.timer.phase("analysis"):
                 if N and n_visit:
-                    first2 = fuse and n_iter == 1
-                    if run.bp:      # C5 band groups: the all-reduced normal equations, same subset and norms
-                        self._band_parallel_iteration(table, x_prev, fc, x_new, A_keep, status, order=vis,
-                                                      n_visit=kw.get("n_visit"), dn_out=cc.dn)
-                    elif gain:      # K1g: the same visiting, subset and per-pixel norms
-                        K.gain(n, table, x_prev, fx, fP, x_new, P_out if first2 else A_keep, status, None, N=N,
-                               joseph=cfg.joseph, out=out_t if first2 else out_now, gn_fused=2 if first2 else 1,
-                               pdiag_rows=run.pdiag_rows if (first2 or A_keep is not None) else 0, **kw,
-                               line=self._line_opt)
-                    elif first2:
-                        K.analysis(n, table, x_prev, fx, fP, x_new, P_out, None, status, None, N=N, out=out_t,
-                                   gn_fused=2, a_rows=a_rows, **kw, line=self._line_opt)
-                    else:
-                        K.analysis(n, table, x_prev, fx, fP, x_new, A_keep, None, status, None, N=N, out=out_now,
-                                   a_rows=a_rows, **kw, line=self._line_opt)
+                    self._launch(run, x_prev, x_new, n_iter, fused,
+                                 _Visit(vis, None if full else n_visit, n_dev, None if static else cc.dn))
             if n_iter == 1:
                 cc.resolve()    # the previous dates' histograms, under this launch (read-backs done long ago)
-            if fuse and n_iter == 1:
+            if fused:
                 n_iter = 2
-            x_prev, x_new = x_new, (x_prev if x_prev is not None else torch.empty_like(x_new))
+            x_prev, x_new = _swap(x_prev, x_new)
             if static:
                 self.last_chunk_iters = cc.set_static(n_iter)
                 return x_prev, n_iter, [0.0]
@@ -319,9 +315,7 @@ class GaussNewtonMixin:
             with self.timer.phase("converge"):
                 pending.append((n_iter, cc.decide(n_iter, cfg.convergence_tolerance, cfg.min_iterations,
                                                   cfg.max_iterations)))
-            if self._lookahead_fn is not None:
-                self._lookahead_fn()
-                self._lookahead_fn = None
+            self._run_lookahead()
             read = None
             # read the oldest decision unless the tail may queue one more iteration first
             while pending and not (tail and len(pending) <= depth and n_iter <= cfg.max_iterations):

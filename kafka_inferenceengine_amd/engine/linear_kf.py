@@ -848,17 +848,18 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             # the previous analysis; the first iteration linearises at it
             prop = forecast.handle()
             src = forecast.src
-            fc = None
+            x_f = P_f = None
             x_prev = None
             x_new = torch.empty_like(src.x)
             P_out = torch.empty_like(src.P)
             ld = src.x.shape[1]
         else:
             fc = self._as_kind(forecast, COVARIANCE if gain else PRECISION)
-            ld = fc.x.shape[1]
-            x_prev = fc.x.clone()
-            x_new = torch.empty_like(fc.x)
-            P_out = torch.empty_like(fc.P)
+            x_f, P_f = fc.x, fc.P
+            ld = x_f.shape[1]
+            x_prev = x_f.clone()
+            x_new = torch.empty_like(x_f)
+            P_out = torch.empty_like(P_f)
         # every analysis / gain kernel writes the status of each of its N pixels
         status = torch.empty(max(N, 1), dtype=torch.uint8, device=self.device)
         len_x = float(n * self.n_total)
@@ -867,8 +868,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         plain = not (gain or precomp or split or bp or cfg.spatial_gamma > 0 or cfg.hessian_correction)
         spatial = cfg.spatial_gamma > 0 and not (gain or precomp or bp or cfg.hessian_correction)
         out_t = None
-        if ((plain or spatial or (gain and not precomp)) and N and cfg.fuse_output and not self._marginal_output()
-                and hasattr(self.output, "device_targets")):
+        if (plain or spatial or (gain and not precomp)) and N and self._fused_output():
             # plain and spatial paths: the final state's x doubles as the mean raster (dense strips)
             out_t = self.output.device_targets(self, self.device, alias=plain or spatial or gain)
         # analysis precision rows stored (EngineConfig.store_precision): a mask of
@@ -887,10 +887,16 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             a_rows = 0 if gain else p_valid
             if p_valid == 0:
                 P_out = None
-        # GN iterations 1 and 2 in one launch (the first never ends the loop): rank-
-        # independent test, so every rank queues the same collectives
-        fuse2 = ((plain or (gain and not precomp)) and cfg.fuse_gn and cfg.min_iterations >= 2
-                 and cfg.max_iterations >= 1 and not (prop is None and fc is None))
+        # GN iterations 1 and 2 in one launch (the first never ends the loop), for
+        # both strategies: rank-independent test, so every rank queues the same
+        # collectives.  The information form with hessian_correction fuses under
+        # convergence_chunk only: the tile-wide loop took the exclusion over
+        # from ``plain`` (which drops hessian_correction for the fused output: the
+        # K6 pass changes the precision after the loop), the per-chunk loop never
+        # had it.  The fused launch is bit-identical to the two, so both are
+        # right, and each strategy keeps the launches it has always queued
+        fuse2 = ((plain or (gain and not precomp) or (chunked and cfg.hessian_correction and not precomp))
+                 and cfg.fuse_gn and cfg.min_iterations >= 2 and cfg.max_iterations >= 1)
         # linear / identity operators: y' = y - offset does not depend on the
         # linearisation point (kf_core.h FD_LINEAR), so iteration 2 repeats
         # iteration 1 exactly and its norm is 0 -- converged without a read-back
@@ -905,8 +911,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         # cannot end the loop), fused with the regularised prepare of the second
         first_plain = spatial and cfg.spatial_first_plain and cfg.min_iterations >= 2 and cfg.max_iterations >= 1
         fuse_sp = first_plain and cfg.fuse_gn
-        run = _GNRun(timestep=timestep, specs=specs, dbs=dbs, table=table, precomp=precomp, gain=gain, bp=bp,
-                     split=split, prop=prop, fc=fc, x_prev=x_prev, x_new=x_new, P_out=P_out, status=status,
+        run = _GNRun(specs=specs, dbs=dbs, table=table, precomp=precomp, gain=gain, bp=bp,
+                     split=split, prop=prop, x_f=x_f, P_f=P_f, x_prev=x_prev, x_new=x_new, P_out=P_out, status=status,
                      order=order, out_t=out_t, h0_outs=h0_outs, a_rows=a_rows, pdiag_rows=pdiag_rows, len_x=len_x,
                      n_bands=len(bands),
                      fuse2=fuse2, fuse_sp=fuse_sp, first_plain=first_plain, static_conv=static_conv)
@@ -957,8 +963,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         if (cfg.store_precision == "always" or self._full_precision_step or not last_of_step or not more_dates
                 or cfg.band_sequential or cfg.hessian_correction or cfg.return_innovations):
             return None
-        if not (cfg.fuse_output and not self._marginal_output()
-                and hasattr(self.output, "device_targets")) and self.output is not None:
+        if not self._fused_output() and self.output is not None:
             # the dump reads the precision diagonal (observations.py:392-393); a marginal dump every row
             return None
         if cfg.analysis_form == "gain":
@@ -1066,8 +1071,9 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                     torch.empty((n, ldh), dtype=torch.float32, device=self.device)) for _ in range(2)]
         return {"d": d, "chunks": chunks, "h0": h0_buf, "h": h_buf, "acc": acc}
 
-    def _split_iteration(self, plan, x_prev, fc: KFState, x_out, A_out, status):
+    def _split_iteration(self, run: _GNRun, x_prev, x_out, A_out):
         n, N = self.n_params, self.N
+        plan, x_f, P_f, status = run.split, run.x_f, run.P_f, run.status
         chunks = plan["chunks"]
         prev = None
         for ci, (op_tab, an_tab, nb) in enumerate(chunks):
@@ -1075,28 +1081,29 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             last = ci == len(chunks) - 1
             a_in, b_in = prev if prev is not None else (None, None)
             if last:
-                K.analysis(n, an_tab, x_prev, fc.x, fc.P, x_out, A_out, None, status, self._partials, N=N,
+                K.analysis(n, an_tab, x_prev, x_f, P_f, x_out, A_out, None, status, self._partials, N=N,
                            a_in=a_in, b_in=b_in)
             else:
                 A_c, b_c = plan["acc"][ci % 2]
-                K.analysis(n, an_tab, x_prev, fc.x, fc.P, None, A_c, b_c, status, None, N=N, solve=False,
+                K.analysis(n, an_tab, x_prev, x_f, P_f, None, A_c, b_c, status, None, N=N, solve=False,
                            a_in=a_in, b_in=b_in)
                 prev = (A_c, b_c)
 
     # ------------------------------------------------ band-parallel (TP-like)
-    def _band_parallel_iteration(self, table, x_prev, fc: KFState, x_out, A_out, status, order=None, n_visit=None,
-                                 dn_out=None):
+    def _band_parallel_iteration(self, run: _GNRun, x_prev, x_out, A_out, visit=None):
         """C5: this rank accumulates sum_b w h h^T and sum_b w h y' over its own
         bands (band slot 0 also adds the forecast precision), one RCCL
         all-reduce of the packed [A | b] per pixel within the band group, then
-        every member solves redundantly (identical x on the group).  ``order`` /
-        ``n_visit`` / ``dn_out``: the per-chunk loop's visiting subset and
-        per-pixel norms (both launches visit the same pixels; the all-reduced
-        entries of the others are never read)."""
-        vis = dict(order=order, n_visit=n_visit)
+        every member solves redundantly (identical x on the group).  ``visit``
+        (engine/gn.py:_Visit): the per-chunk loop's visiting subset and
+        per-pixel norms, which replace the solve's norm partials (both launches
+        visit the same pixels; the all-reduced entries of the others are never
+        read)."""
+        table, x_f, P_f, status = run.table, run.x_f, run.P_f, run.status
+        vis, dn_out = ({}, None) if visit is None else (dict(order=visit.order, n_visit=visit.n_visit), visit.dn_out)
         n, N = self.n_params, self.N
         nt = ntri(n)
-        ld = fc.x.shape[1]
+        ld = x_f.shape[1]
         if self._bp_buf is None or self._bp_buf.shape[1] != ld:
             self._bp_buf = torch.zeros((nt + n, ld), dtype=torch.float32, device=self.device)
             self._bp_solve_tab = build_table([], [], n, self._cache, self.device)
@@ -1104,15 +1111,15 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         A_part, b_part = self._bp_buf[:nt], self._bp_buf[nt:]
         if N:
             if self.band_comm.rank == 0:
-                K.analysis(n, table, x_prev, fc.x, fc.P, None, A_part, b_part, status, None, N=N, solve=False, **vis)
+                K.analysis(n, table, x_prev, x_f, P_f, None, A_part, b_part, status, None, N=N, solve=False, **vis)
             else:
                 self._bp_buf.zero_()
-                K.analysis(n, table, x_prev, fc.x, fc.P, None, A_part, b_part, status, None, N=N, solve=False,
+                K.analysis(n, table, x_prev, x_f, P_f, None, A_part, b_part, status, None, N=N, solve=False,
                            a_in=A_part, b_in=b_part, **vis)
         with self.timer.phase("band_allreduce"):
             self.band_comm.all_reduce_(self._bp_buf)
         if N:
-            K.analysis(n, self._bp_solve_tab, x_prev, fc.x, fc.P, x_out, A_out, None, self._bp_status,
+            K.analysis(n, self._bp_solve_tab, x_prev, x_f, P_f, x_out, A_out, None, self._bp_status,
                        None if dn_out is not None else self._partials, N=N, a_in=A_part, b_in=b_part,
                        dn_out=dn_out, **vis)
 
@@ -1232,6 +1239,13 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                 prec = self._as_kind(state, PRECISION)
                 self.output.dump_data(timestep, x, P, prec.to_reference()[1], self.partition.local_mask,
                                       self.n_params)
+
+    def _fused_output(self) -> bool:
+        """The output rasters are written by the analysis kernel itself
+        (EngineConfig.fuse_output, an output with device rasters), not dumped
+        from the state afterwards."""
+        return (self.config.fuse_output and not self._marginal_output()
+                and hasattr(self.output, "device_targets"))
 
     def _marginal_output(self) -> bool:
         """The output writes marginal std rasters (``uncertainty="marginal"``): no

@@ -37,8 +37,7 @@ class SpatialPriorMixin:
         self._reg_log = []
         return out
 
-    def _regularised_iteration(self, table, x_prev, fc: KFState | None, x_out, A_out, status, prop=None, out=None,
-                               final=True, partials_first=None, a_rows=0):
+    def _regularised_iteration(self, run, x_prev, x_out, A_out, out=None, final=True, partials_first=None):
         """GMRF spatial prior (K9 + C2), affine block-Jacobi form (kf_core.h):
         the analysis kernel assembles (A, b) and, instead of solving, factors
         A_reg = A + g deg E_R once and writes u = A_reg^-1 b and V = A_reg^-1 E_R;
@@ -46,10 +45,12 @@ class SpatialPriorMixin:
         s(z) (s: neighbour sums, halo rows exchanged by C2), and the last one forms
         x = u + g V s(z) with the convergence partials.  Identical to ``sweeps``
         block-Jacobi sweeps of (A_reg) x = b + g E_R sum_q x_q.  The analysis
-        precision includes the smoother's diagonal.  With ``prop`` the forecast
-        is fused as in the plain path (first iteration: x0 = forecast, written
-        for the norm and the first sweep).  ``a_rows``: the precision rows
-        stored (0: all; EngineConfig.store_precision).  ``partials_first``: the launch runs
+        precision includes the smoother's diagonal.  ``run`` (engine/gn.py:_GNRun)
+        holds the band table, the forecast operands, the status buffer, the
+        visiting order and the precision rows stored (``a_rows``, 0: all;
+        EngineConfig.store_precision).  With ``run.prop`` the forecast is fused
+        as in the plain path (first iteration: x0 = forecast, written for the
+        norm and the first sweep).  ``partials_first``: the launch runs
         the plain first Gauss-Newton iteration in registers (its norm there)
         and prepares the regularised second, linearised at x_1 (written to the
         x0 buffer, the finish's reference for the norm)."""
@@ -64,12 +65,12 @@ class SpatialPriorMixin:
         gamma = self.config.spatial_gamma
         sweeps = max(1, int(self.config.jacobi_sweeps))
         rows = reg.reg_rows()
-        fx, fP = (fc.x, fc.P) if fc is not None else (None, None)
         fused = partials_first is not None
+        kw = dict(N=N, prop=run.prop, gn_fused=2 if fused else 1, partials_first=partials_first, order=run.order,
+                  a_rows=run.a_rows, line=self._line_opt)
         if not rows:   # nothing regularised: plain analysis
-            K.analysis(n, table, x_prev, fx, fP, x_out, A_out, None, status, self._partials, N=N, prop=prop, out=out,
-                       gn_fused=2 if fused else 1, partials_first=partials_first, order=self._visit, a_rows=a_rows,
-                       line=self._line_opt)
+            K.analysis(n, run.table, x_prev, run.x_f, run.P_f, x_out, A_out, None, run.status, self._partials, out=out,
+                       **kw)
             return
         k = len(rows)
         ld = x_out.shape[1]
@@ -80,12 +81,10 @@ class SpatialPriorMixin:
         x_ref = x_prev if (x_prev is not None and not fused) else x0_buf
         # the final iteration's uncertainty raster comes from the prepare (diag of
         # the regularised precision in registers), the mean from reg_finish
-        K.analysis(n, table, x_prev, fx, fP, u, A_out, None, status, None, N=N, prop=prop,
+        K.analysis(n, run.table, x_prev, run.x_f, run.P_f, u, A_out, None, run.status, None,
                    reg=dict(gamma=gamma, mask=reg.reg_mask, v_out=v, nbr=None if geo else reg.nbr, geo=geo),
                    x0_out=None if x_ref is x_prev else x0_buf,
-                   out=None if out is None else (None, out[1], out[2]),
-                   gn_fused=2 if fused else 1, partials_first=partials_first, order=self._visit, a_rows=a_rows,
-                   line=self._line_opt)
+                   out=None if out is None else (None, out[1], out[2]), **kw)
         if fused:
             self._reg_log.append({"solver": "plain", "rho": 0.0, "sweeps": 0, "r2": None, "count": 0})
         nbr = None if geo else reg.nbr

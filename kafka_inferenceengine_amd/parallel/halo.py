@@ -11,7 +11,7 @@ Overlap (C2): ``start_fill`` posts the exchange and returns at once;
 ``finish_fill`` makes the compute stream wait for it and unpacks the halo
 columns.  The engine computes a sweep's boundary rows first, starts their
 exchange, computes the interior rows while the rows are on the wire, and only
-then finishes the exchange (``LinearKalman._regularised_iteration``).
+then finishes the exchange (``SpatialPriorMixin._reg_sweep_solve`` / ``_reg_tiled_solve``).
 """
 from __future__ import annotations
 

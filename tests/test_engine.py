@@ -91,6 +91,30 @@ def test_engine_host_propagator_and_precomputed_operator_paths():
     assert ((st.P - ref.P).abs() / rowmax).max() < 2e-3
 
 
+def test_precomputed_operator_hessian_correction_per_chunk():
+    """Precomputed-operator bands (a factory without device_spec on a source
+    without band specs) with hessian_correction under convergence_chunk: the
+    Hessian pass after the loop reads the band table the last iteration
+    rebuilt.  It skips bands that are not GP bands, so the run equals the one
+    without the correction bit for bit."""
+    mask, obs, prior, x0, Pinv, Q = _setup(seed=2)
+    obs.band_spec = lambda date, band: None
+    grid = _grid(4)
+
+    def user_factory(*a):
+        return k.create_nonlinear_observation_operator(*a)
+
+    res = []
+    for hc in (False, True):
+        kf = k.LinearKalman(obs, None, mask, user_factory, k.TIP_PARAMETERS, device="cpu",
+                            state_propagation=k.propagate_information_filter_LAI,
+                            config=k.EngineConfig(hessian_correction=hc, convergence_chunk=[8, 8]))
+        kf.set_trajectory_model()
+        kf.set_trajectory_uncertainty(Q)
+        res.append(kf.run(grid, x0, None, Pinv))
+    assert torch.equal(res[0].x, res[1].x) and torch.equal(res[0].P, res[1].P)
+
+
 def test_gain_form_fused_forecast_and_output():
     """Gain form with the forecast evaluated inside the K1g kernel and the
     output rasters written by it, against the materialised forecast (invert +
