@@ -436,6 +436,36 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     if (device) check_hip(dev_smooth(np, a, (hipStream_t)stream), "smooth");
     else check_host(host_smooth(np, a), "smooth");
   });
+  // innovation statistics and the chi-square gate (kf_core.h pixel_innovation): z [nb][ldz], chi2 / nobs /
+  // nrej / status [N]; screened: nb plane pointers (device memory on the device) or null
+  m.attr("INNOV_SCOPE_BAND") = INNOV_SCOPE_BAND;
+  m.attr("INNOV_SCOPE_GROUP") = INNOV_SCOPE_GROUP;
+  m.attr("INNOV_MAX_BANDS") = INNOV_MAX_BANDS;
+  m.def("innovation", [](int np, uintptr_t x, uintptr_t p, int kind, uintptr_t bands, int nb, uintptr_t grp,
+                         double gate, int scope, uintptr_t z, int64_t ldz, uintptr_t chi2, uintptr_t nobs,
+                         uintptr_t nrej, uintptr_t status, uintptr_t screened, int64_t N, int64_t ld, bool device,
+                         uintptr_t stream) {
+    InnovationArgs a{};
+    a.N = N;
+    a.ld = ld;
+    a.ldz = ldz;
+    a.kind = kind;
+    a.nb = nb;
+    a.scope = scope;
+    a.gate = (float)gate;
+    a.x = P<const float>(x);
+    a.p = P<const float>(p);
+    a.bands = P<const BandDesc>(bands);
+    a.grp = P<const int32_t>(grp);
+    a.z = P<float>(z);
+    a.chi2 = P<float>(chi2);
+    a.nobs = P<uint8_t>(nobs);
+    a.nrej = P<uint8_t>(nrej);
+    a.status = P<uint8_t>(status);
+    a.screened = P<void* const>(screened);
+    if (device) check_hip(dev_innovation(np, a, (hipStream_t)stream), "innovation");
+    else check_host(host_innovation(np, a), "innovation");
+  });
   // GeoTIFF tile encoder (predictor 3 + one zlib stream per 256^2 tile; mode:
   // fixed Huffman, or a dynamic table per tile where that is smaller)
   m.attr("DFL_TILE") = DFL_TILE;

@@ -1356,6 +1356,172 @@ KF_HD bool eval_operator(const BandDesc& bd, int64_t p, int64_t ld, const float 
 }
 
 // ---------------------------------------------------------------------------
+// Innovation statistics and the background check of pixel p.  For a state
+// (x, rows p of kind MARG_PRECISION / MARG_COVARIANCE: the forecast the analysis
+// starts from, or any materialised state) and the date's bands,
+//   z_b = (y_b - H_b(x)) / sqrt(h_b^T P h_b + 1 / w_b)
+// is the normalised innovation of band b (h_b the operator's Jacobian row at x,
+// w_b the decoded inverse variance), NaN where the band has no observation or
+// its operator fails.  chi2 = sum_b z_b^2 over the counted bands (nobs of them):
+// the sum of the per-band statistics, NOT the joint Mahalanobis distance
+// r^T S^-1 r (the bands' innovations are correlated through P).
+//   MARG_PRECISION: the block is factorised once (chol_packed), per band
+//     U^T v = h is solved and h^T P h = v . v.
+//   MARG_COVARIANCE: h^T P h by symv; a factorisation of a copy tells whether
+//     the block is SPD.
+// gate k > 0 rejects: INNOV_SCOPE_BAND every band with |z_b| > k,
+// INNOV_SCOPE_GROUP every counted band of a group (grp[b], null: one group) in
+// which any band has |z_b| > k (a cloud spoils all bands of a sensor).  The
+// decision is a 64-bit mask (nb <= INNOV_MAX_BANDS), so the second pass over the
+// bands, which writes the screened planes, needs no stored z.
+// screened[b] (optional, per band): a copy of the one plane that carries the
+// band's nodata code, rejected pixels set to that code -- OBS_DN16 dn -> 0,
+// OBS_F32 w -> 0, OBS_BF16 w (bf16 bits) -> 0, OBS_BF16Y y (bf16 bits) -> NaN
+// (0x7FC0), the codes decode_obs reads as "no observation".  The source planes
+// are never written.
+// Fails open (status 1, else 0): a block that is not SPD or an input that is
+// not finite makes the pixel unscreenable -- chi2 and every z NaN, nobs = nrej
+// = 0, the screened planes plain copies; the analysis has its own fallbacks.
+constexpr int INNOV_SCOPE_BAND = 0, INNOV_SCOPE_GROUP = 1;
+constexpr int INNOV_MAX_BANDS = 64;
+struct InnovationArgs {
+  int64_t N, ld, ldz;
+  int32_t kind;            // MARG_PRECISION / MARG_COVARIANCE: what p holds
+  int32_t nb;              // bands, <= INNOV_MAX_BANDS
+  int32_t scope;           // INNOV_SCOPE_*
+  float gate;              // k >= 0; 0: statistics only
+  const float* x;          // [NP][ld]
+  const float* p;          // [NT][ld]
+  const BandDesc* bands;   // [nb]
+  const int32_t* grp;      // optional [nb], group ids in 0..63
+  float* z;                // optional [nb][ldz]
+  float* chi2;             // optional [N]
+  uint8_t* nobs;           // optional [N]
+  uint8_t* nrej;           // optional [N]
+  uint8_t* status;         // [N]
+  void* const* screened;   // optional [nb] plane pointers (an entry may be null)
+};
+inline bool innovation_args_ok(int np, const InnovationArgs& a) {
+  if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return false;
+  if (a.scope != INNOV_SCOPE_BAND && a.scope != INNOV_SCOPE_GROUP) return false;
+  if (a.N < 0 || a.N > a.ld || np < 1 || np > MAX_D || a.nb < 0 || a.nb > INNOV_MAX_BANDS) return false;
+  if (!(a.gate >= 0.f) || !finitef(a.gate) || (a.z && a.ldz < a.N) || (a.nb > 0 && !a.bands)) return false;
+  return a.x && a.p && a.status;
+}
+
+// |v|^2 with U^T v = h, U from chol_packed: h^T (U^T U)^-1 h (the forward
+// substitution of chol_inv_diag for a general right-hand side)
+template <int NP>
+KF_HD float chol_fwd_norm2(const float (&U)[ntri(NP)], const float (&h)[NP]) {
+  float v[NP], s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    float t = h[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) t = fmaf(-U[tri(NP, k, i)], v[k], t);
+    v[i] = t * U[tri(NP, i, i)];
+    s = fmaf(v[i], v[i], s);
+  }
+  return s;
+}
+
+template <int NP>
+KF_HD void pixel_innovation(const InnovationArgs& a, int64_t p) {
+  constexpr int NT = ntri(NP);
+  KF_DCHECK(p >= 0 && p < a.N && a.N <= a.ld);
+  const int64_t ld = a.ld;
+  const float nan = __builtin_nanf("");
+  float x[NP], A[NT];
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    x[j] = a.x[j * ld + p];
+    ok = ok && finitef(x[j]);
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    A[t] = a.p[t * ld + p];
+    ok = ok && finitef(A[t]);
+  }
+  const bool cov = a.kind == MARG_COVARIANCE;
+  if (cov) {
+    float U[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) U[t] = A[t];
+    ok = chol_packed<NP>(U) && ok;
+  } else {
+    ok = chol_packed<NP>(A) && ok;
+  }
+  const float k = a.gate;
+  uint64_t counted = 0, over = 0, gbad = 0;
+  float chi2 = 0.f;
+  for (int b = 0; b < a.nb; ++b) {
+    const BandDesc bd = cptr(a.bands)[b];
+    float y, w, zb = nan;
+    decode_obs<0>(bd, p, y, w);
+    // lanes without an observation skip the operator: a wave under cloud branches over it
+    if (ok && w > 0.f) {
+      float H0, h[NP];
+      if (eval_operator<NP>(bd, p, ld, x, H0, h)) {
+        float s;
+        if (cov) {
+          float ph[NP];
+          symv<NP>(A, h, ph);
+          s = 0.f;
+#pragma unroll
+          for (int j = 0; j < NP; ++j) s = fmaf(h[j], ph[j], s);
+        } else {
+          s = chol_fwd_norm2<NP>(A, h);
+        }
+        const float zz = (y - H0) * kf_rsqrt(s + kf_rcp(w));
+        if (finitef(zz)) {
+          zb = zz;
+          counted |= 1ull << b;
+          chi2 = fmaf(zz, zz, chi2);
+          if (k > 0.f && fabsf(zz) > k) {
+            over |= 1ull << b;
+            gbad |= 1ull << (a.grp ? (cptr(a.grp)[b] & 63) : 0);
+          }
+        }
+      }
+    }
+    if (a.z) a.z[b * a.ldz + p] = zb;
+  }
+  uint64_t rej = over;
+  if (a.scope == INNOV_SCOPE_GROUP && gbad) {
+    rej = 0;
+    for (int b = 0; b < a.nb; ++b) {
+      const int g = a.grp ? (cptr(a.grp)[b] & 63) : 0;
+      if ((gbad >> g) & 1u) rej |= 1ull << b;
+    }
+    rej &= counted;
+  }
+  if (a.screened) {
+    for (int b = 0; b < a.nb; ++b) {
+      void* out = cptr(a.screened)[b];
+      if (!out) continue;
+      const KF_CONST_AS BandDesc* bd = cptr(a.bands) + b;
+      const bool r = (rej >> b) & 1u;
+      const int obs = bd->obs;
+      if (obs == OBS_F32) {
+        const uint32_t v = reinterpret_cast<const uint32_t*>(bd->w)[p];
+        reinterpret_cast<uint32_t*>(out)[p] = r ? 0u : v;
+      } else if (obs == OBS_DN16) {
+        reinterpret_cast<uint16_t*>(out)[p] = r ? (uint16_t)0 : bd->dn[p];
+      } else if (obs == OBS_BF16) {
+        reinterpret_cast<uint16_t*>(out)[p] = r ? (uint16_t)0 : reinterpret_cast<const uint16_t*>(bd->w)[p];
+      } else if (obs == OBS_BF16Y) {
+        reinterpret_cast<uint16_t*>(out)[p] = r ? (uint16_t)0x7FC0 : reinterpret_cast<const uint16_t*>(bd->y)[p];
+      }
+    }
+  }
+  if (a.chi2) a.chi2[p] = ok ? chi2 : nan;
+  if (a.nobs) a.nobs[p] = (uint8_t)__builtin_popcountll(counted);
+  if (a.nrej) a.nrej[p] = (uint8_t)__builtin_popcountll(rej);
+  a.status[p] = ok ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------
 // K4/K5: propagation and prior blending for one pixel.
 // Forecast fused into the analysis kernel: the partial prior reset, one
 // compile-time formula (a runtime mode switch in the analysis prologue costs

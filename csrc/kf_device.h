@@ -534,6 +534,14 @@ __global__ __launch_bounds__(BLOCK) void smooth_kernel(const SmoothArgs a) {
   for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < a.N; p += stride) pixel_smooth<NP>(a, p);
 }
 
+// Innovation statistics and the chi-square gate (pixel_innovation): one pixel
+// per thread, every SoA row and observation plane read and written coalesced.
+template <int NP>
+__global__ __launch_bounds__(BLOCK) void innovation_kernel(const InnovationArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * BLOCK;
+  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < a.N; p += stride) pixel_innovation<NP>(a, p);
+}
+
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void gather_kernel(const T* src, const int64_t* idx, T* dst, int64_t n,
                                                       int rows, int64_t src_ld, int64_t dst_ld) {

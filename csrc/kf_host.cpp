@@ -188,6 +188,12 @@ static int h_smooth(const SmoothArgs& a) {
   for (int64_t p = 0; p < a.N; ++p) pixel_smooth<NP>(a, p);
   return 0;
 }
+template <int NP>
+static int h_innovation(const InnovationArgs& a) {
+#pragma omp parallel for schedule(static)
+  for (int64_t p = 0; p < a.N; ++p) pixel_innovation<NP>(a, p);
+  return 0;
+}
 
 // GeoTIFF tiles on the host: the same row encoder as dfl_tile_kernel, rows in
 // order into one byte stream per tile (bit-identical streams).  Dynamic mode:
@@ -481,6 +487,10 @@ int host_marginal(int np, const float* x, const float* p, int kind, int64_t N, i
 int host_smooth(int np, const SmoothArgs& a) {
   if (!smooth_args_ok(np, a)) return -1;
   KF_HOST_NP_SWITCH(np, h_smooth, a);
+}
+int host_innovation(int np, const InnovationArgs& a) {
+  if (!innovation_args_ok(np, a)) return -1;
+  KF_HOST_NP_SWITCH(np, h_innovation, a);
 }
 int host_obs_order(const BandDesc* bands, const int32_t* grp, int nb, int G, int64_t N, int32_t* order, bool local) {
   if (G < 1 || G > 3) return -1;

@@ -132,6 +132,10 @@ template <int NP>
 static void l_smooth(const SmoothArgs& a, int grid, hipStream_t s) {
   hipLaunchKernelGGL(smooth_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
 }
+template <int NP>
+static void l_innovation(const InnovationArgs& a, int grid, hipStream_t s) {
+  hipLaunchKernelGGL(innovation_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
+}
 
 // Grid cap for the per-pixel kernels (one f64 partial per workgroup).  The
 // default keeps grid-stride loops; raising it to >= N/256 gives one pixel per
@@ -704,6 +708,13 @@ hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s) {
   if (!smooth_args_ok(np, a)) return hipErrorInvalidValue;
   if (a.N == 0) return hipSuccess;
   KF_NP_SWITCH(np, l_smooth, a, grid_for(a.N, g_max_blocks), s);
+  return hipGetLastError();
+}
+// grid capped by set_max_blocks, as dev_marginal
+hipError_t dev_innovation(int np, const InnovationArgs& a, hipStream_t s) {
+  if (!innovation_args_ok(np, a)) return hipErrorInvalidValue;
+  if (a.N == 0) return hipSuccess;
+  KF_NP_SWITCH(np, l_innovation, a, grid_for(a.N, g_max_blocks), s);
   return hipGetLastError();
 }
 // Fixed-order f64 sum of a launch's norm partials: one workgroup (at most

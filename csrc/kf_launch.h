@@ -57,6 +57,8 @@ hipError_t dev_marginal(int np, const float* x, const float* p, int kind, int64_
                         float* mean, float* unc, int64_t plane, hipStream_t s);
 // one backward step of the RTS smoother (kf_core.h pixel_smooth)
 hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s);
+// innovation statistics and the chi-square gate (kf_core.h pixel_innovation)
+hipError_t dev_innovation(int np, const InnovationArgs& a, hipStream_t s);
 hipError_t dev_reduce(const double* partials, int n, double* out, hipStream_t s);
 hipError_t dev_gather(int elem_bytes, const void* src, const int64_t* idx, void* dst, int64_t n, int rows,
                       int64_t src_ld, int64_t dst_ld, hipStream_t s);
@@ -99,6 +101,7 @@ int host_unpack(int np, const float* x, const float* a, int64_t N, int64_t ld, c
 int host_marginal(int np, const float* x, const float* p, int kind, int64_t N, int64_t ld, const int64_t* idx,
                   float* mean, float* unc, int64_t plane);
 int host_smooth(int np, const SmoothArgs& a);
+int host_innovation(int np, const InnovationArgs& a);
 // obs_order chunk: pixels per scatter workgroup; local = 1 partitions each
 // chunk on its own (no count / scan passes, chunk-aligned, see kf_kernels.hip)
 constexpr int KF_ORD_CHUNK = 4096;

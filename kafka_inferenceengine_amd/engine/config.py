@@ -111,6 +111,15 @@ class EngineConfig:
                                               # float64 cubic line tables instead of the GP sums (the
                                               # forecast varies in one parameter only; models/gp.py)
     return_innovations: bool = False
+    # background check before every date's analysis (ops.kernels.innovation): the
+    # normalised forecast innovation z_b = (y_b - H_b(x_f)) / sqrt(h_b^T P_f h_b + sigma_b^2)
+    # of every band; gate k > 0 rejects observations with |z_b| > k ("band"), or every
+    # observed band of a sensor group in which one band exceeds k ("group": a cloud
+    # spoils all bands of a sensor).  innovation_stats: the statistics alone
+    # (LinearKalman.last_innovation), nothing rejected.  Both off: nothing runs
+    innovation_gate: float = 0.0
+    innovation_scope: str = "group"           # 'group' | 'band'
+    innovation_stats: bool = False
     metrics_path: str | None = None           # JSONL metrics (per date / timestep)
     checkpoint_dir: str | None = None
     checkpoint_every: int = 0                 # timesteps between checkpoints (0: off)
@@ -139,6 +148,10 @@ class EngineConfig:
         if int(self.gn_lookahead) < 0:
             raise ValueError("gn_lookahead must be >= 0")
         self.gn_lookahead = int(self.gn_lookahead)
+        if not self.innovation_gate >= 0 or self.innovation_gate == float("inf"):
+            raise ValueError("innovation_gate must be a finite number >= 0 (0: no gate)")
+        if self.innovation_scope not in ("group", "band"):
+            raise ValueError("innovation_scope must be 'group' or 'band'")
         if self.store_precision not in ("auto", "always"):
             raise ValueError("store_precision must be 'auto' or 'always'")
         if isinstance(self.convergence_chunk, str) and self.convergence_chunk.strip().lower() in ("", "0", "tile",

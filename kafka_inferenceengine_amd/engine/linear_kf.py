@@ -17,6 +17,7 @@ the engine converts at the boundary and runs that piece on the host.
 from __future__ import annotations
 
 import bisect
+import dataclasses
 import logging
 import time
 from collections import namedtuple
@@ -160,6 +161,9 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         self._chunks = None               # per-chunk convergence state (config.convergence_chunk)
         self.last_chunk_iters = None      # {GN iterations: chunks} of the last date (chunked test)
         self.ood_history = None           # config.domain_history: ST_OUT_OF_DOMAIN on any date so far
+        self.last_innovation = None       # config.innovation_*: the last date's {"chi2", "nobs", "nrej"}
+        self.gate_history = None          # config.innovation_gate: dates with a rejection, per pixel (int32)
+        self._innov = None                # its buffers: statistics and the screened observation planes
         self._full_precision_step = False
         band = getattr(self.comm, "band", None)
         self.band_comm = band if (band is not None and band.world > 1) else None
@@ -266,6 +270,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         from ..input_output.checkpoint import CheckpointManager
 
         self._check_marginal_output()
+        self._check_innovation()
         ckpt = CheckpointManager(self.config.checkpoint_dir, self) if self.config.checkpoint_dir else None
         self.checkpointer = ckpt
         if self.config.gc_freeze:
@@ -324,6 +329,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         dump.  Returns the analysis state."""
         self.current_timestep = timestep
         self._check_marginal_output()
+        self._check_innovation()
         t0 = time.perf_counter()
         forecast = state
         if advance:
@@ -563,6 +569,12 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                 rows = self._precision_rows(last_of_step=i == len(locate_times) - 1, more_dates=bool(nxt))
                 try:
                     ready = prep is not None and prep[1] is bands
+                    if self._screening():
+                        # background check of the date's observations against the materialised
+                        # forecast; under a gate the analysis runs on the screened bands
+                        forecast, run_bands = self._screen_date(step, bands, forecast)
+                        ready = ready and run_bands is bands
+                        bands = run_bands
                     res = self.do_all_bands_state(step, bands, forecast, table=prep[2] if ready else None,
                                                   store_rows=rows,
                                                   order=prep[3] if ready and prep[3] is not None else False)
@@ -586,6 +598,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                 rec["spatial"] = self._spatial_record()
             if self.metrics.enabled:
                 rec.update(self._health_metrics(rec["wall_s"]))
+                if self._screening() and not self.config.band_sequential and self.last_innovation is not None:
+                    rec["innovation"] = self._innovation_record()
             self.metrics.log(rec)
         return forecast, info
 
@@ -599,7 +613,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         specs = [sp for sp, _ in bands]
         cfg = self.config
         order = None
-        if not (cfg.return_innovations or cfg.spatial_gamma > 0 or
+        # (a gated date runs on screened copies of its bands: its table and order follow the check)
+        if not (cfg.return_innovations or cfg.spatial_gamma > 0 or cfg.innovation_gate > 0 or
                 self.band_comm is not None or any(sp.kind == OP_PRECOMP for sp in specs)) and \
                 self._split_plan_kind(specs) is None:
             table = self._band_table(bands, specs, [d for _, d in bands])
@@ -629,6 +644,113 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                                      local=cfg.observed_first_local)
         self._order_bufs[slot] = (order if buf is None or buf.numel() < N else buf, scratch)
         return order
+
+    # ------------------------------------------- innovation statistics / gate
+    def _screening(self) -> bool:
+        return self.config.innovation_gate > 0 or self.config.innovation_stats
+
+    def _check_innovation(self):
+        cfg = self.config
+        if not self._screening():
+            return
+        if cfg.band_parallel > 1 or self.band_comm is not None:
+            raise ValueError("innovation_gate / innovation_stats with band_parallel > 1: a rank does not see all "
+                             "bands of a sensor group")
+        if cfg.band_sequential:
+            raise ValueError("innovation_gate / innovation_stats do not run with band_sequential")
+
+    def _band_groups(self, timestep, nb):
+        groups = self.observations.band_groups(timestep) if hasattr(self.observations, "band_groups") else None
+        if groups is not None and (len(groups) != nb or min(groups) < 0 or max(groups) > 63):
+            groups = None
+        return groups
+
+    @staticmethod
+    def _nodata_plane(db: DeviceBand) -> str:
+        """The field of a band that carries its nodata code (kf_core.h pixel_innovation)."""
+        return {K.OBS_DN16: "dn", K.OBS_F32: "w", K.OBS_BF16: "w", K.OBS_BF16Y: "y"}[db.kind]
+
+    def _innovation_table(self, specs, bands):
+        if any(s.kind == OP_PRECOMP for s in specs):
+            raise ValueError("the innovation check needs every band's operator on the device: a host-evaluated "
+                             "(reference-protocol) observation operator has none before the analysis")
+        return self._band_table(bands, specs, [d for _, d in bands])
+
+    def _screen_date(self, timestep, bands, forecast):
+        """Innovation statistics of one date against the forecast its analysis
+        starts from (config.innovation_gate / innovation_stats).  Returns the
+        materialised forecast and the bands to assimilate: under a gate, copies
+        whose nodata plane is an engine-owned buffer with the rejected
+        observations set to nodata (the source's planes are never written)."""
+        cfg = self.config
+        n, N = self.n_params, self.N
+        specs = [s for s, _ in bands]
+        dbs = [d for _, d in bands]
+        table = self._innovation_table(specs, bands)
+        fc = self._as_kind(forecast, self._analysis_kind())
+        fc.require_full("the innovation check")
+        gated = cfg.innovation_gate > 0
+        buf = self._innov
+        if buf is None:
+            dev = self.device
+            buf = self._innov = {"chi2": torch.zeros(max(N, 1), dtype=torch.float32, device=dev), "planes": {},
+                                 **{key: torch.zeros(max(N, 1), dtype=torch.uint8, device=dev)
+                                    for key in ("nobs", "nrej", "status")}}
+        screened = None
+        if gated:
+            screened = []
+            for b, db in enumerate(dbs):
+                src = getattr(db, self._nodata_plane(db))
+                t = buf["planes"].get((b, src.dtype))
+                if t is None or t.numel() < src.numel():
+                    t = buf["planes"][(b, src.dtype)] = torch.zeros(src.numel(), dtype=src.dtype, device=self.device)
+                screened.append(t[:src.numel()])
+        if N:
+            with self.timer.phase("innovation"):
+                K.innovation(n, table, fc.x, fc.P, kind=fc.kind, N=N, chi2=buf["chi2"], nobs=buf["nobs"],
+                             nrej=buf["nrej"], status=buf["status"], gate=cfg.innovation_gate,
+                             scope=cfg.innovation_scope, groups=self._band_groups(timestep, len(specs)),
+                             screened=screened)
+        self.last_innovation = {"chi2": buf["chi2"][:N], "nobs": buf["nobs"][:N], "nrej": buf["nrej"][:N],
+                                "status": buf["status"][:N]}
+        if not gated:
+            return fc, bands
+        hit = (buf["nrej"][:N] > 0).to(torch.int32)
+        self.gate_history = hit if self.gate_history is None else self.gate_history.add_(hit)
+        return fc, [(s, dataclasses.replace(db, **{self._nodata_plane(db): t}))
+                    for s, db, t in zip(specs, dbs, screened)]
+
+    def _innovation_record(self) -> dict:
+        """The date's innovation metrics (one device reduction and sync)."""
+        li = self.last_innovation
+        good = li["status"] == 0
+        sums = torch.stack([li["nobs"].sum(dtype=torch.float64), li["nrej"].sum(dtype=torch.float64),
+                            (~good).sum().to(torch.float64),
+                            torch.where(good, li["chi2"], torch.zeros_like(li["chi2"])).sum(dtype=torch.float64)])
+        obs, rej, bad, chi2 = sums.cpu().tolist()
+        return {"observed": int(obs), "rejected": int(rej), "unscreenable": int(bad),
+                "chi2_per_obs": chi2 / obs if obs else None}
+
+    def innovation(self, state, timestep, gate: float = 0.0, scope: str = "group") -> dict:
+        """Innovation statistics of ``timestep``'s observations against any
+        state: ``{"z" [n_bands, N], "chi2", "nobs", "nrej", "status" [N]}`` (see
+        ``ops.kernels.innovation``; chi2 is the sum of the per-band z^2, not the
+        joint Mahalanobis distance).  With the forecast a date's analysis started
+        from these are the background-check statistics; with the analysis state,
+        the observation-minus-analysis residuals.  Nothing is modified."""
+        bands = self._device_bands(timestep)
+        specs = [s for s, _ in bands]
+        table = self._innovation_table(specs, bands)
+        st = self._materialize(state)
+        st.require_full("innovation")
+        N, dev = self.N, self.device
+        out = {"z": torch.full((len(bands), max(N, 1)), float("nan"), dtype=torch.float32, device=dev),
+               "chi2": torch.zeros(max(N, 1), dtype=torch.float32, device=dev),
+               **{key: torch.zeros(max(N, 1), dtype=torch.uint8, device=dev) for key in ("nobs", "nrej", "status")}}
+        if N:
+            K.innovation(self.n_params, table, st.x, st.P, kind=st.kind, N=N, gate=gate, scope=scope,
+                         groups=self._band_groups(timestep, len(specs)), **out)
+        return {key: v[..., :N] for key, v in out.items()}
 
     def _health_metrics(self, wall_s: float) -> dict:
         """Per-date structured metrics: rank-local pixel updates/s,
@@ -962,6 +1084,10 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         cfg = self.config
         if (cfg.store_precision == "always" or self._full_precision_step or not last_of_step or not more_dates
                 or cfg.band_sequential or cfg.hessian_correction or cfg.return_innovations):
+            return None
+        if self._screening() and cfg.analysis_form == "gain":
+            # the next date's check materialises its forecast: the gain form's goes through the
+            # inverse of this analysis' full covariance (_lazy_cov)
             return None
         if not self._fused_output() and self.output is not None:
             # the dump reads the precision diagonal (observations.py:392-393); a marginal dump every row

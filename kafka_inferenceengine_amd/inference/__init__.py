@@ -4,6 +4,7 @@ from ..utils.blocks import (LazyBlockDiag, blocks_to_sparse, interleaved_to_soa,
                      unpack_matrix)
 from .kf_tools import (NoHessianMethod, PropagatorSpec, blend_prior, hessian_correction,  # noqa: F401
                        hessian_correction_multiband, hessian_correction_pixel, identity_propagation,
+                       innovation_blocks,
                        make_no_propagation, make_partial_prior_propagator, no_propagation,
                        propagate_and_blend_prior, propagate_information_filter, propagate_information_filter_approx_SLOW,
                        propagate_information_filter_LAI, propagate_information_filter_SLOW, propagate_standard_kalman,

@@ -325,3 +325,61 @@ def hessian_correction_multiband(gp, x0, R_mats, innovations, masks, state_mask,
     gps = gp if isinstance(gp, (list, tuple)) else [gp] * n_bands
     return sum(hessian_correction(g, x0, R, inn, mk, state_mask, b, nparams)
                for g, R, inn, mk, b in zip(gps, R_mats, innovations, masks, range(n_bands)))
+
+
+def innovation_blocks(P, y, w, H0, h, kind="precision", gate=0.0, scope="group", groups=None, ok=None):
+    """Float64 oracle of the innovation statistics and the chi-square gate
+    (``ops.kernels.innovation``, csrc/kf_core.h ``pixel_innovation``) on host blocks.
+
+    ``P`` [N, n, n]: the pixels' precision (``kind="precision"``) or covariance
+    (``"covariance"``) blocks; ``y`` / ``w`` [nb, N]: the decoded observations
+    and inverse variances (w <= 0: no observation); ``H0`` [nb, N] and ``h``
+    [nb, N, n]: each band's operator value and Jacobian row at the state, in
+    float64, so a caller can feed exact operator values; ``ok`` [nb, N] bool
+    (optional): False where the operator is invalid.
+
+    Returns ``(z, chi2, nobs, reject)``: z [nb, N] = (y - H0) / sqrt(h^T C h +
+    1/w) with C the covariance, NaN where the band is not counted; chi2 [N] the
+    sum of z^2 over the counted bands (not the joint Mahalanobis distance);
+    nobs [N] the counted bands; reject [nb, N] bool -- with ``gate`` k > 0 band
+    b where |z_b| > k (``scope="band"``), or every counted band of a group
+    (``groups``: one id per band, None: one group) in which a band exceeds k
+    (``scope="group"``).  A pixel whose block is not SPD or not finite is
+    unscreenable: z and chi2 NaN, nobs 0, nothing rejected."""
+    if kind not in ("precision", "covariance"):
+        raise ValueError("kind must be 'precision' or 'covariance'")
+    if scope not in ("band", "group"):
+        raise ValueError("scope must be 'band' or 'group'")
+    if not gate >= 0.0:
+        raise ValueError("gate must be >= 0")
+    P = np.asarray(P, dtype=np.float64)
+    y, w, H0 = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (y, w, H0))
+    h = np.asarray(h, dtype=np.float64).reshape(y.shape + (P.shape[-1],))
+    nb, N = y.shape
+    good = np.isfinite(P).all(axis=(1, 2))
+    safe = np.where(good[:, None, None], P, np.eye(P.shape[-1]))
+    good &= np.all(np.linalg.eigvalsh(safe) > 0.0, axis=1)
+    safe = np.where(good[:, None, None], P, np.eye(P.shape[-1]))
+    C = np.linalg.inv(safe) if kind == "precision" else safe
+    s = np.einsum("bpi,pij,bpj->bp", h, C, h)
+    with np.errstate(all="ignore"):
+        z = (y - H0) / np.sqrt(s + 1.0 / np.where(w > 0, w, 1.0))
+    counted = (w > 0) & good[None, :] & np.isfinite(z) & np.isfinite(h).all(axis=2) & np.isfinite(H0)
+    if ok is not None:
+        counted &= np.asarray(ok, dtype=bool).reshape(nb, N)
+    z = np.where(counted, z, np.nan)
+    chi2 = np.where(good, np.sum(np.where(counted, z, 0.0) ** 2, axis=0), np.nan)
+    nobs = counted.sum(axis=0).astype(np.int64)
+    over = counted & (np.abs(np.where(counted, z, 0.0)) > gate) if gate > 0 else np.zeros_like(counted)
+    if scope == "group" and over.any():
+        g = np.zeros(nb, dtype=np.int64) if groups is None else np.asarray(groups, dtype=np.int64)
+        if g.shape != (nb,):
+            raise ValueError("groups: one id per band")
+        reject = np.zeros_like(counted)
+        for gid in np.unique(g):
+            sel = g == gid
+            reject[sel] = over[sel].any(axis=0)[None, :]
+        reject &= counted
+    else:
+        reject = over
+    return z, chi2, nobs, reject

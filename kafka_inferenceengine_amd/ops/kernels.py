@@ -1624,6 +1624,101 @@ def smooth(n_params, x_a, p_a, x_next, p_next, x_out, p_out, status, *, kind, pr
              _ptr(q_pix), _dev(x_a), _stream(x_a))
 
 
+INNOVATION_SCOPES = ("band", "group")
+INNOVATION_MAX_BANDS = 64   # kf_core.h INNOV_MAX_BANDS: the reject decision is a 64-bit mask per pixel
+_SCREENED_PTRS = {}         # (device, plane addresses) -> int64 device tensor of the plane pointers
+
+
+def _screened_dtype(obs):
+    return torch.float32 if obs == OBS_F32 else torch.int16
+
+
+def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=None, nobs=None, nrej=None, status,
+               gate=0.0, scope="group", groups=None, screened=None):
+    """Innovation statistics and the chi-square gate, per pixel (csrc/kf_core.h
+    ``pixel_innovation``).  ``x`` [n_p, ld] and ``p`` [ntri, ld] (packed rows of
+    P^-1 for ``kind="precision"``, of P for ``"covariance"``) are the state the
+    observations of ``bands`` are checked against.  Outputs, each optional
+    except ``status``:
+
+    * ``z`` float32 [nb, ldz]: z_b = (y_b - H_b(x)) / sqrt(h_b^T P h_b + 1/w_b),
+      NaN where band b has no observation or its operator fails;
+    * ``chi2`` float32 [>= N]: the sum of z_b^2 over the ``nobs`` counted bands
+      (the sum of the per-band statistics, not the joint Mahalanobis distance);
+    * ``nobs`` / ``nrej`` uint8 [>= N]: counted and rejected bands;
+    * ``status`` uint8 [>= N]: 1 where the pixel is unscreenable (block not SPD,
+      input not finite): chi2 and z NaN, nothing rejected (fails open);
+    * ``screened``: one tensor (or None) per band, a copy of the plane that
+      carries the band's nodata code with the rejected pixels set to that code
+      (float32 ``w`` for OBS_F32, int16 ``dn`` / bf16 ``w`` / bf16 ``y`` for
+      OBS_DN16 / OBS_BF16 / OBS_BF16Y).  The source planes are never written.
+
+    ``gate`` k > 0 rejects band b where |z_b| > k (``scope="band"``) or every
+    counted band of a group in which any band exceeds k (``scope="group"``,
+    ``groups``: one id in 0..63 per band, None: one group).  gate = 0:
+    statistics only."""
+    check_np(n_params)
+    if kind not in MARGINAL_KINDS:
+        raise ValueError("kind must be 'precision' or 'covariance'")
+    if scope not in INNOVATION_SCOPES:
+        raise ValueError("scope must be 'band' or 'group'")
+    gate = float(gate)
+    if not (gate >= 0.0) or not np.isfinite(gate):
+        raise ValueError("gate must be a finite number >= 0")
+    nb = int(bands.n)
+    if nb > INNOVATION_MAX_BANDS:
+        raise ValueError(f"innovation: {nb} bands, at most {INNOVATION_MAX_BANDS} (the reject mask has 64 bits)")
+    N = int(x.shape[1] if N is None else N)
+    dev = x.device
+    ld = x.shape[1]
+    _check_soa(x, n_params, N, "x")
+    if p is None:
+        raise ValueError("p is required")
+    _check_soa(p, ntri(n_params), N, "p", device=dev)
+    if p.shape[1] != ld:
+        raise ValueError("x and p must share their row stride")
+    if bands.buf.device != dev:
+        raise ValueError(f"band table on {bands.buf.device}, expected {dev}")
+    if status is None:
+        raise ValueError("status is required")
+    _check_vec(status, N, "status", torch.uint8, dev)
+    _check_vec(chi2, N, "chi2", torch.float32, dev)
+    _check_vec(nobs, N, "nobs", torch.uint8, dev)
+    _check_vec(nrej, N, "nrej", torch.uint8, dev)
+    _check_soa(z, nb, N, "z", device=dev)
+    grp = None
+    if groups is not None:
+        groups = [int(g) for g in groups]
+        if len(groups) != nb or (nb and (min(groups) < 0 or max(groups) > 63)):
+            raise ValueError("innovation: one group id in 0..63 per band")
+        key = (str(dev), tuple(groups))
+        grp = _GROUP_IDS.get(key)
+        if grp is None:   # once per layout: a pageable H2D copy waits for the stream
+            grp = _GROUP_IDS[key] = torch.tensor(groups, dtype=torch.int32, device=dev)
+    ptrs = None
+    if screened is not None:
+        screened = list(screened)
+        if len(screened) != nb or len(bands.descs) != nb:
+            raise ValueError(f"screened: one plane (or None) per band, got {len(screened)} for {nb} bands")
+        for b, (t, d) in enumerate(zip(screened, bands.descs)):
+            if t is None:
+                continue
+            if d.obs not in (OBS_F32, OBS_DN16, OBS_BF16, OBS_BF16Y):
+                raise ValueError(f"screened[{b}]: band {b} carries no observation")
+            _check_vec(t, N, f"screened[{b}]", _screened_dtype(d.obs), dev)
+        key = (str(dev),) + tuple(_ptr(t) for t in screened)
+        ptrs = _SCREENED_PTRS.get(key)
+        if ptrs is None:
+            if len(_SCREENED_PTRS) >= 64:
+                _SCREENED_PTRS.clear()
+            ptrs = _SCREENED_PTRS[key] = small_h2d(torch.tensor(key[1:] or (0,), dtype=torch.int64), dev)
+    e = ext()
+    e.innovation(n_params, _ptr(x), _ptr(p), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION,
+                 bands.ptr, nb, _ptr(grp), gate, e.INNOV_SCOPE_BAND if scope == "band" else e.INNOV_SCOPE_GROUP,
+                 _ptr(z), 0 if z is None else z.shape[1], _ptr(chi2), _ptr(nobs), _ptr(nrej), _ptr(status),
+                 _ptr(ptrs), N, ld, _dev(x), _stream(x))
+
+
 def reduce_partials(partials: torch.Tensor, out: torch.Tensor | None = None):
     """Fixed-order f64 sum of the partials the last producer wrote (device:
     one workgroup)."""
