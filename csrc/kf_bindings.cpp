@@ -444,8 +444,10 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
   m.def("innovation", [](int np, uintptr_t x, uintptr_t p, int kind, uintptr_t bands, int nb, uintptr_t grp,
                          double gate, int scope, uintptr_t z, int64_t ldz, uintptr_t chi2, uintptr_t nobs,
                          uintptr_t nrej, uintptr_t status, uintptr_t screened, int64_t N, int64_t ld, bool device,
-                         uintptr_t stream) {
+                         uintptr_t stream, uintptr_t d2, uintptr_t logdet) {
     InnovationArgs a{};
+    a.d2 = P<float>(d2);           // joint statistic [N] (either one selects the joint instantiation)
+    a.logdet = P<float>(logdet);
     a.N = N;
     a.ld = ld;
     a.ldz = ldz;

@@ -1382,6 +1382,22 @@ KF_HD bool eval_operator(const BandDesc& bd, int64_t p, int64_t ld, const float 
 // Fails open (status 1, else 0): a block that is not SPD or an input that is
 // not finite makes the pixel unscreenable -- chi2 and every z NaN, nobs = nrej
 // = 0, the screened planes plain copies; the analysis has its own fallbacks.
+//
+// JOINT (a second instantiation, launched only when d2 or logdet is asked for):
+// the joint statistic of the counted bands, S = H P H^T + R over them,
+//   d2 = r^T S^-1 r (chi-square with nobs degrees of freedom under the
+//   linearised model), logdet = log det S (natural logarithm),
+// so that -(d2 + logdet + nobs log 2 pi) / 2 is the Gaussian log evidence of the
+// date's observations at the forecast.  Formed by the sequential scalar-band
+// recursion in ascending band order (the arithmetic of gain_band_update with two
+// sums added), on C = P, v_b = h_b (MARG_COVARIANCE) or in the whitened form
+// C = I, v_b = U^-T h_b (MARG_PRECISION), delta = 0 at the start:
+//   c = C v_b, s~ = v_b . c + 1 / w_b, e = r_b - v_b . delta,
+//   d2 += e^2 / s~, logdet += log s~, delta += c e / s~, C -= c c^T / s~.
+// d2 is a sum of non-negative terms (no cancellation, unlike sum w r^2 - g^T A^-1
+// g).  Both are 0 where no band is counted, NaN where the pixel is unscreenable
+// or a step variance s~ is not positive and finite.  The other outputs are the
+// same bits with and without JOINT.
 constexpr int INNOV_SCOPE_BAND = 0, INNOV_SCOPE_GROUP = 1;
 constexpr int INNOV_MAX_BANDS = 64;
 struct InnovationArgs {
@@ -1400,7 +1416,10 @@ struct InnovationArgs {
   uint8_t* nrej;           // optional [N]
   uint8_t* status;         // [N]
   void* const* screened;   // optional [nb] plane pointers (an entry may be null)
+  float* d2;               // optional [N]: joint r^T S^-1 r (pixel_innovation<NP, true> only)
+  float* logdet;           // optional [N]: log det S        (pixel_innovation<NP, true> only)
 };
+inline bool innovation_joint(const InnovationArgs& a) { return a.d2 || a.logdet; }
 inline bool innovation_args_ok(int np, const InnovationArgs& a) {
   if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return false;
   if (a.scope != INNOV_SCOPE_BAND && a.scope != INNOV_SCOPE_GROUP) return false;
@@ -1425,7 +1444,49 @@ KF_HD float chol_fwd_norm2(const float (&U)[ntri(NP)], const float (&h)[NP]) {
   return s;
 }
 
+// the same, keeping v: returns |v|^2 by the same operations in the same order
 template <int NP>
+KF_HD float chol_fwd_solve(const float (&U)[ntri(NP)], const float (&h)[NP], float (&v)[NP]) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    float t = h[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) t = fmaf(-U[tri(NP, k, i)], v[k], t);
+    v[i] = t * U[tri(NP, i, i)];
+    s = fmaf(v[i], v[i], s);
+  }
+  return s;
+}
+
+// One step of the joint recursion (see pixel_innovation): band vector v,
+// residual r, observation variance rv.  False where the step variance is not
+// positive and finite (C, delta and the sums are then left alone).
+template <int NP>
+KF_HD bool joint_band_step(float (&C)[ntri(NP)], float (&delta)[NP], const float (&v)[NP], float r, float rv,
+                           float& d2, float& logdet) {
+  float c[NP];
+  symv<NP>(C, v, c);
+  float vc = 0.f, e = r;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) { vc = fmaf(v[j], c[j], vc); e = fmaf(-v[j], delta[j], e); }
+  const float st = vc + rv;
+  if (!(st > 0.f) || !finitef(st)) return false;
+  const float is = kf_rcp(st), g = e * is;
+  d2 = fmaf(e, g, d2);
+  logdet += logf(st);
+#pragma unroll
+  for (int j = 0; j < NP; ++j) delta[j] = fmaf(c[j], g, delta[j]);
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    const float f = c[i] * is;
+#pragma unroll
+    for (int j = i; j < NP; ++j) C[tri(NP, i, j)] = fmaf(-f, c[j], C[tri(NP, i, j)]);
+  }
+  return true;
+}
+
+template <int NP, bool JOINT = false>
 KF_HD void pixel_innovation(const InnovationArgs& a, int64_t p) {
   constexpr int NT = ntri(NP);
   KF_DCHECK(p >= 0 && p < a.N && a.N <= a.ld);
@@ -1455,6 +1516,17 @@ KF_HD void pixel_innovation(const InnovationArgs& a, int64_t p) {
   const float k = a.gate;
   uint64_t counted = 0, over = 0, gbad = 0;
   float chi2 = 0.f;
+  // joint recursion state (JOINT only; dead code otherwise)
+  float C[JOINT ? NT : 1], delta[JOINT ? NP : 1], d2 = 0.f, logdet = 0.f;
+  bool jok = true;
+  if constexpr (JOINT) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      delta[i] = 0.f;
+#pragma unroll
+      for (int j = i; j < NP; ++j) C[tri(NP, i, j)] = cov ? A[tri(NP, i, j)] : (i == j ? 1.f : 0.f);
+    }
+  }
   for (int b = 0; b < a.nb; ++b) {
     const BandDesc bd = cptr(a.bands)[b];
     float y, w, zb = nan;
@@ -1464,20 +1536,29 @@ KF_HD void pixel_innovation(const InnovationArgs& a, int64_t p) {
       float H0, h[NP];
       if (eval_operator<NP>(bd, p, ld, x, H0, h)) {
         float s;
+        [[maybe_unused]] float v[JOINT ? NP : 1];
         if (cov) {
           float ph[NP];
           symv<NP>(A, h, ph);
           s = 0.f;
 #pragma unroll
           for (int j = 0; j < NP; ++j) s = fmaf(h[j], ph[j], s);
+          if constexpr (JOINT) {
+#pragma unroll
+            for (int j = 0; j < NP; ++j) v[j] = h[j];
+          }
         } else {
-          s = chol_fwd_norm2<NP>(A, h);
+          if constexpr (JOINT) s = chol_fwd_solve<NP>(A, h, v);
+          else s = chol_fwd_norm2<NP>(A, h);
         }
         const float zz = (y - H0) * kf_rsqrt(s + kf_rcp(w));
         if (finitef(zz)) {
           zb = zz;
           counted |= 1ull << b;
           chi2 = fmaf(zz, zz, chi2);
+          if constexpr (JOINT) {
+            if (jok) jok = joint_band_step<NP>(C, delta, v, y - H0, kf_rcp(w), d2, logdet);
+          }
           if (k > 0.f && fabsf(zz) > k) {
             over |= 1ull << b;
             gbad |= 1ull << (a.grp ? (cptr(a.grp)[b] & 63) : 0);
@@ -1514,6 +1595,11 @@ KF_HD void pixel_innovation(const InnovationArgs& a, int64_t p) {
         reinterpret_cast<uint16_t*>(out)[p] = r ? (uint16_t)0x7FC0 : reinterpret_cast<const uint16_t*>(bd->y)[p];
       }
     }
+  }
+  if constexpr (JOINT) {
+    jok = jok && ok;
+    if (a.d2) a.d2[p] = jok ? d2 : nan;
+    if (a.logdet) a.logdet[p] = jok ? logdet : nan;
   }
   if (a.chi2) a.chi2[p] = ok ? chi2 : nan;
   if (a.nobs) a.nobs[p] = (uint8_t)__builtin_popcountll(counted);

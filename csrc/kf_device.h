@@ -541,6 +541,14 @@ __global__ __launch_bounds__(BLOCK) void innovation_kernel(const InnovationArgs 
   const int64_t stride = (int64_t)gridDim.x * BLOCK;
   for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < a.N; p += stride) pixel_innovation<NP>(a, p);
 }
+// The same with the joint statistic d2 / logdet (pixel_innovation<NP, true>):
+// an instantiation of its own, so a launch without them runs the kernel above
+// at its own register count.
+template <int NP>
+__global__ __launch_bounds__(BLOCK) void innovation_joint_kernel(const InnovationArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * BLOCK;
+  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < a.N; p += stride) pixel_innovation<NP, true>(a, p);
+}
 
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void gather_kernel(const T* src, const int64_t* idx, T* dst, int64_t n,

@@ -190,6 +190,11 @@ static int h_smooth(const SmoothArgs& a) {
 }
 template <int NP>
 static int h_innovation(const InnovationArgs& a) {
+  if (innovation_joint(a)) {
+#pragma omp parallel for schedule(static)
+    for (int64_t p = 0; p < a.N; ++p) pixel_innovation<NP, true>(a, p);
+    return 0;
+  }
 #pragma omp parallel for schedule(static)
   for (int64_t p = 0; p < a.N; ++p) pixel_innovation<NP>(a, p);
   return 0;

@@ -134,7 +134,10 @@ static void l_smooth(const SmoothArgs& a, int grid, hipStream_t s) {
 }
 template <int NP>
 static void l_innovation(const InnovationArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL(innovation_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
+  if (innovation_joint(a))
+    hipLaunchKernelGGL(innovation_joint_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
+  else
+    hipLaunchKernelGGL(innovation_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
 }
 
 // Grid cap for the per-pixel kernels (one f64 partial per workgroup).  The

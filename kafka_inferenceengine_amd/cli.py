@@ -79,6 +79,8 @@ def _engine_config(args):
     from .engine.config import EngineConfig
 
     cfg = EngineConfig.from_args(args)
+    if getattr(args, "evidence_out", None) or getattr(args, "scan_q", None):
+        cfg.innovation_evidence = True
     if getattr(args, "smooth_out", None):
         # the backward pass reads every step's filtered state
         cfg.checkpoint_every, cfg.checkpoint_keep = 1, 0
@@ -96,7 +98,9 @@ def _engine_config(args):
     return cfg
 
 
-def _build(args, comm):
+def _build(args, comm, q_scale=None):
+    """The engine of a run.  ``q_scale`` (default ``--q-scale``) multiplies the
+    sensor's built-in model error Q."""
     import kafka_inferenceengine_amd as k
     from .parallel import StripPartition
 
@@ -193,12 +197,37 @@ def _build(args, comm):
     kf = k.LinearKalman(obs, out, mask, factory, params, state_propagation=prop,
                         prior=None if prop is not None else prior, config=cfg, comm=comm, partition=part)
     kf.set_trajectory_model()
+    q_scale = float(getattr(args, "q_scale", 1.0) if q_scale is None else q_scale)
+    if not (q_scale > 0.0 and np.isfinite(q_scale)):
+        raise SystemExit("--q-scale / --scan-q: a scale is a finite number > 0")
     if q is not None:
-        kf.set_trajectory_uncertainty(q)
+        kf.set_trajectory_uncertainty(q * q_scale)
+    elif q_scale != 1.0:
+        raise SystemExit(f"--q-scale / --scan-q: sensor {args.sensor} runs without a model error Q (its state is "
+                         "reset to the prior on every step)")
     dates = sorted(obs.dates)
     n = min(args.steps, len(dates)) if args.steps else len(dates)
     grid = [dates[0] - dt.timedelta(days=1)] + [dates[0] + dt.timedelta(days=step * (i + 1) - 1) for i in range(n)]
-    return kf, prior, grid, out, make_out
+    return kf, prior, grid, out, make_out, (geotransform, projection)
+
+
+def _scan_q(args, comm):
+    """``--scan-q``: the configured run once per scale of Q, no file output; one
+    record per scale and the scale with the largest total log evidence.  Every
+    scale is a full filter run: the analysis covariance that feeds the next
+    forecast depends on Q, so one trajectory cannot be re-scored under another."""
+    recs = []
+    for scale in args.scan_q:
+        kf, prior, grid, _, _, _ = _build(args, comm, q_scale=scale)
+        kf.run(grid, kf.state_from_prior(prior), None, None)
+        ev = kf.evidence_summary()
+        recs.append({"q_scale": scale, "loglik": ev["loglik"], "d2_per_dof": ev["d2_per_dof"], "dof": ev["dof"]})
+        if comm.rank == 0:
+            print(json.dumps(recs[-1]), flush=True)
+    best = max(recs, key=lambda r: r["loglik"])
+    if comm.rank == 0:
+        print(json.dumps({"best_q_scale": best["q_scale"], "loglik": best["loglik"]}))
+    return recs, best
 
 
 def cmd_run(args):
@@ -206,6 +235,11 @@ def cmd_run(args):
 
     import kafka_inferenceengine_amd as k
 
+    if args.scan_q:
+        for flag, v in (("--out", args.out), ("--smooth-out", args.smooth_out), ("--resume", args.resume),
+                        ("--evidence-out", args.evidence_out)):
+            if v:
+                raise SystemExit(f"--scan-q repeats the run with file output off: it does not go with {flag}")
     cfg = _engine_config(args)
     comm = Comm.from_env(device=args.device, band_parallel=getattr(args, "band_parallel", None) or 1,
                          timeout_s=cfg.comm_timeout_s)
@@ -213,7 +247,11 @@ def cmd_run(args):
         import torch
         dev = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
         comm = Comm.single(dev if dev != "cuda" else torch.device("cuda", torch.cuda.current_device()))
-    kf, prior, grid, out, make_out = _build(args, comm)
+    if args.scan_q:
+        _scan_q(args, comm)
+        comm.destroy()
+        return
+    kf, prior, grid, out, make_out, geo = _build(args, comm)
     import time
     t_run = time.perf_counter()
     start = None
@@ -236,6 +274,10 @@ def cmd_run(args):
             sm_out.flush()
         fb = [comm.sum_int(r["fallback_pixels"]) for r in smooth_recs]
         t_smooth = time.perf_counter()
+    evidence = kf.evidence_summary() if cfg.innovation_evidence else None      # every rank: a rank-ordered sum
+    if args.evidence_out:
+        from .input_output.evidence import write_evidence_rasters
+        ev_files = write_evidence_rasters(args.evidence_out, kf, *geo)
     if comm.rank == 0:
         rec = {"timesteps": len(kf.history), "pixels": kf.n_total,
                "gn_iterations": [h.get("gn_iterations") for h in kf.history],
@@ -266,6 +308,10 @@ def cmd_run(args):
                              **{k_: [round(1e3 * r.get(k_, 0.0), 1) for r in smooth_recs]
                                 for k_ in ("read_s", "h2d_s", "kernel_s", "output_s")},
                              "files": len(getattr(sm_out, "written", []))}
+        if evidence is not None:
+            rec["evidence"] = evidence
+            if args.evidence_out:
+                rec["evidence"] = {**evidence, "files": [os.path.basename(p) for p in ev_files]}
         print(json.dumps(rec))
     comm.destroy()
 
@@ -393,6 +439,16 @@ def main(argv=None):
                    help="after the forward run, smooth backward over the steps (RTS) and write the smoothed rasters, "
                         "under the same file names, into DIR; checkpoints every step (into DIR/checkpoints unless "
                         "--checkpoint-dir is given)")
+    r.add_argument("--evidence-out", default=None, metavar="DIR",
+                   help="implies --innovation-evidence; at the end of the run write evidence_loglik.tif, "
+                        "evidence_d2_per_dof.tif, evidence_dof.tif (and, with a gate, evidence_rejected_dates.tif) "
+                        "into DIR: the run's per-pixel Gaussian log evidence (linearised at each date's forecast), "
+                        "joint chi-square per degree of freedom and observation count")
+    r.add_argument("--q-scale", type=float, default=1.0, metavar="S",
+                   help="multiply the sensor's built-in model error Q by S")
+    r.add_argument("--scan-q", type=float, nargs="+", default=None, metavar="S",
+                   help="repeat the run once per scale S of Q with file output off; print one record per scale "
+                        "(q_scale, loglik, d2_per_dof, dof) and the scale with the largest total log evidence")
     r.add_argument("--log-level", default="WARNING")
     EngineConfig.add_arguments(r)
     r.set_defaults(fn=cmd_run)

@@ -120,6 +120,14 @@ class EngineConfig:
     innovation_gate: float = 0.0
     innovation_scope: str = "group"           # 'group' | 'band'
     innovation_stats: bool = False
+    # innovation_evidence: the check also forms the joint statistic d2 = r^T S^-1 r
+    # (S = H P_f H^T + R over the observations the analysis assimilates; chi-square
+    # with nobs degrees of freedom) and log det S per pixel and date, and sums the
+    # Gaussian log evidence -(d2 + log det S + nobs log 2 pi) / 2 over the run
+    # (LinearKalman.evidence / evidence_summary): the linearised (extended-filter)
+    # marginal likelihood, the quantity to maximise over Q.  With a gate it costs
+    # a second launch (a second operator evaluation) on the screened bands
+    innovation_evidence: bool = False
     metrics_path: str | None = None           # JSONL metrics (per date / timestep)
     checkpoint_dir: str | None = None
     checkpoint_every: int = 0                 # timesteps between checkpoints (0: off)

@@ -44,6 +44,7 @@ from .spatial import SpatialPriorMixin
 from .state import COVARIANCE, PRECISION, KFState, LazyForecast
 
 LOG = logging.getLogger(__name__ + ".linear_kf")
+LOG_2PI = float(np.log(2.0 * np.pi))
 
 Metadata = namedtuple("Metadata", "mask uncertainty")
 Previous_State = namedtuple("Previous_State", "timestamp x_vect cov_m icov_mv")
@@ -163,6 +164,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         self.ood_history = None           # config.domain_history: ST_OUT_OF_DOMAIN on any date so far
         self.last_innovation = None       # config.innovation_*: the last date's {"chi2", "nobs", "nrej"}
         self.gate_history = None          # config.innovation_gate: dates with a rejection, per pixel (int32)
+        self.evidence = None              # config.innovation_evidence: the run's per-pixel accumulators
         self._innov = None                # its buffers: statistics and the screened observation planes
         self._full_precision_step = False
         band = getattr(self.comm, "band", None)
@@ -266,11 +268,15 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             approx_diagonal=True, refine_diag=True, iter_obs_op=False, is_robust=False, dates=None,
             resume_from=None):
         """Full assimilation over ``time_grid`` (linear_kf.py:171-212).  Returns the
-        final analysis state (device).  ``resume_from`` restarts from a checkpoint."""
+        final analysis state (device).  ``resume_from`` restarts from a checkpoint.
+        The evidence accumulators (``config.innovation_evidence``) start at
+        zero here, also on a resumed run: they then hold the evidence of the
+        dates after the checkpoint only."""
         from ..input_output.checkpoint import CheckpointManager
 
         self._check_marginal_output()
         self._check_innovation()
+        self.evidence = None
         ckpt = CheckpointManager(self.config.checkpoint_dir, self) if self.config.checkpoint_dir else None
         self.checkpointer = ckpt
         if self.config.gc_freeze:
@@ -647,17 +653,19 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
 
     # ------------------------------------------- innovation statistics / gate
     def _screening(self) -> bool:
-        return self.config.innovation_gate > 0 or self.config.innovation_stats
+        cfg = self.config
+        return cfg.innovation_gate > 0 or cfg.innovation_stats or cfg.innovation_evidence
 
     def _check_innovation(self):
         cfg = self.config
         if not self._screening():
             return
         if cfg.band_parallel > 1 or self.band_comm is not None:
-            raise ValueError("innovation_gate / innovation_stats with band_parallel > 1: a rank does not see all "
-                             "bands of a sensor group")
+            raise ValueError("innovation_gate / innovation_stats / innovation_evidence with band_parallel > 1: a "
+                             "rank does not see all bands of a sensor group")
         if cfg.band_sequential:
-            raise ValueError("innovation_gate / innovation_stats do not run with band_sequential")
+            raise ValueError("innovation_gate / innovation_stats / innovation_evidence do not run with "
+                             "band_sequential")
 
     def _band_groups(self, timestep, nb):
         groups = self.observations.band_groups(timestep) if hasattr(self.observations, "band_groups") else None
@@ -678,10 +686,20 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
 
     def _screen_date(self, timestep, bands, forecast):
         """Innovation statistics of one date against the forecast its analysis
-        starts from (config.innovation_gate / innovation_stats).  Returns the
-        materialised forecast and the bands to assimilate: under a gate, copies
-        whose nodata plane is an engine-owned buffer with the rejected
-        observations set to nodata (the source's planes are never written)."""
+        starts from (config.innovation_gate / innovation_stats /
+        innovation_evidence).  Returns the materialised forecast and the bands to
+        assimilate: under a gate, copies whose nodata plane is an engine-owned
+        buffer with the rejected observations set to nodata (the source's planes
+        are never written).
+
+        With ``innovation_evidence`` the joint statistic d2 = r^T S^-1 r and
+        log det S of the observations the analysis assimilates are written too
+        (``last_innovation["d2"]`` / ``["logdet"]``) and added to
+        ``self.evidence``: the linearised (extended-filter) evidence at the
+        forecast.  Without a gate the one launch writes them.  With a gate the
+        first launch decides as always and a second one (gate 0, on the screened
+        band table the analysis needs anyway) computes them over the bands that
+        were kept: that costs a second evaluation of every band's operator."""
         cfg = self.config
         n, N = self.n_params, self.N
         specs = [s for s, _ in bands]
@@ -696,6 +714,13 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             buf = self._innov = {"chi2": torch.zeros(max(N, 1), dtype=torch.float32, device=dev), "planes": {},
                                  **{key: torch.zeros(max(N, 1), dtype=torch.uint8, device=dev)
                                     for key in ("nobs", "nrej", "status")}}
+        joint = cfg.innovation_evidence
+        if joint and "d2" not in buf:
+            buf.update({key: torch.zeros(max(N, 1), dtype=torch.float32, device=self.device)
+                        for key in ("d2", "logdet")})
+            buf.update({key: torch.zeros(max(N, 1), dtype=torch.uint8, device=self.device)
+                        for key in ("nobs_kept", "status_kept")})
+        first = dict(d2=buf["d2"], logdet=buf["logdet"]) if joint and not gated else {}
         screened = None
         if gated:
             screened = []
@@ -710,15 +735,65 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                 K.innovation(n, table, fc.x, fc.P, kind=fc.kind, N=N, chi2=buf["chi2"], nobs=buf["nobs"],
                              nrej=buf["nrej"], status=buf["status"], gate=cfg.innovation_gate,
                              scope=cfg.innovation_scope, groups=self._band_groups(timestep, len(specs)),
-                             screened=screened)
+                             screened=screened, **first)
         self.last_innovation = {"chi2": buf["chi2"][:N], "nobs": buf["nobs"][:N], "nrej": buf["nrej"][:N],
                                 "status": buf["status"][:N]}
         if not gated:
+            if joint:
+                self._add_evidence(buf["d2"], buf["logdet"], buf["nobs"])
             return fc, bands
         hit = (buf["nrej"][:N] > 0).to(torch.int32)
         self.gate_history = hit if self.gate_history is None else self.gate_history.add_(hit)
-        return fc, [(s, dataclasses.replace(db, **{self._nodata_plane(db): t}))
-                    for s, db, t in zip(specs, dbs, screened)]
+        run_bands = [(s, dataclasses.replace(db, **{self._nodata_plane(db): t}))
+                     for s, db, t in zip(specs, dbs, screened)]
+        if joint:
+            if N:
+                with self.timer.phase("innovation"):
+                    K.innovation(n, self._innovation_table(specs, run_bands), fc.x, fc.P, kind=fc.kind, N=N,
+                                 nobs=buf["nobs_kept"], status=buf["status_kept"], d2=buf["d2"], logdet=buf["logdet"])
+            self._add_evidence(buf["d2"], buf["logdet"], buf["nobs_kept"])
+        return fc, run_bands
+
+    def _add_evidence(self, d2, logdet, nobs):
+        """One date into the run's accumulators (device, torch ops, no sync).  A
+        pixel whose joint outputs are not finite on a date skips that date."""
+        N = self.N
+        d2, logdet, nobs = d2[:N], logdet[:N], nobs[:N]
+        self.last_innovation.update(d2=d2, logdet=logdet)
+        ev = self.evidence
+        if ev is None:
+            dev = self.device
+            ev = self.evidence = {"loglik": torch.zeros(N, dtype=torch.float64, device=dev),
+                                  "d2": torch.zeros(N, dtype=torch.float64, device=dev),
+                                  "dof": torch.zeros(N, dtype=torch.int32, device=dev),
+                                  "skipped": torch.zeros(N, dtype=torch.int32, device=dev)}
+        ok = torch.isfinite(d2) & torch.isfinite(logdet)
+        d64 = torch.where(ok, d2, torch.zeros_like(d2)).to(torch.float64)
+        l64 = torch.where(ok, logdet, torch.zeros_like(logdet)).to(torch.float64)
+        dof = torch.where(ok, nobs, torch.zeros_like(nobs)).to(torch.int32)
+        ev["loglik"].sub_(0.5 * (d64 + l64 + dof.to(torch.float64) * LOG_2PI))
+        ev["d2"].add_(d64)
+        ev["dof"].add_(dof)
+        ev["skipped"].add_((~ok).to(torch.int32))
+
+    def evidence_summary(self) -> dict:
+        """The run's evidence (config.innovation_evidence) summed over the active
+        pixels of every rank, in rank order: ``loglik`` the total Gaussian log
+        evidence (the filter's marginal likelihood by prediction-error
+        decomposition, linearised at each date's forecast), ``d2`` the total
+        joint chi-square, ``dof`` the observations behind it, ``d2_per_dof``
+        (about 1 for consistent Q and R; None without observations) and
+        ``skipped_pixel_dates``.  One device reduction and sync."""
+        ev = self.evidence
+        if ev is None:
+            local = torch.zeros(4, dtype=torch.float64, device=self.device)
+        else:
+            local = torch.stack([ev["loglik"].sum(), ev["d2"].sum(), ev["dof"].sum(dtype=torch.float64),
+                                 ev["skipped"].sum(dtype=torch.float64)])
+        tot = self.comm.sum_f64_async(local)
+        ll, d2, dof, skipped = (tot.result(j) for j in range(4))
+        return {"loglik": ll, "d2": d2, "dof": int(dof), "d2_per_dof": d2 / dof if dof else None,
+                "skipped_pixel_dates": int(skipped)}
 
     def _innovation_record(self) -> dict:
         """The date's innovation metrics (one device reduction and sync)."""
@@ -727,17 +802,30 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         sums = torch.stack([li["nobs"].sum(dtype=torch.float64), li["nrej"].sum(dtype=torch.float64),
                             (~good).sum().to(torch.float64),
                             torch.where(good, li["chi2"], torch.zeros_like(li["chi2"])).sum(dtype=torch.float64)])
-        obs, rej, bad, chi2 = sums.cpu().tolist()
+        if "d2" not in li:
+            obs, rej, bad, chi2 = sums.cpu().tolist()
+            return {"observed": int(obs), "rejected": int(rej), "unscreenable": int(bad),
+                    "chi2_per_obs": chi2 / obs if obs else None}
+        # the joint statistic of the assimilated observations (the kept ones under a gate)
+        fin = torch.isfinite(li["d2"]) & torch.isfinite(li["logdet"])
+        kept = torch.where(fin, (li["nobs"] - li["nrej"]), torch.zeros_like(li["nobs"])).sum(dtype=torch.float64)
+        d2 = torch.where(fin, li["d2"], torch.zeros_like(li["d2"])).sum(dtype=torch.float64)
+        ld = torch.where(fin, li["logdet"], torch.zeros_like(li["logdet"])).sum(dtype=torch.float64)
+        obs, rej, bad, chi2, kept, d2, ld = torch.cat([sums, torch.stack([kept, d2, ld])]).cpu().tolist()
         return {"observed": int(obs), "rejected": int(rej), "unscreenable": int(bad),
-                "chi2_per_obs": chi2 / obs if obs else None}
+                "chi2_per_obs": chi2 / obs if obs else None, "d2_per_obs": d2 / kept if kept else None,
+                "loglik": -0.5 * (d2 + ld + kept * LOG_2PI)}
 
-    def innovation(self, state, timestep, gate: float = 0.0, scope: str = "group") -> dict:
+    def innovation(self, state, timestep, gate: float = 0.0, scope: str = "group", joint: bool = False) -> dict:
         """Innovation statistics of ``timestep``'s observations against any
         state: ``{"z" [n_bands, N], "chi2", "nobs", "nrej", "status" [N]}`` (see
         ``ops.kernels.innovation``; chi2 is the sum of the per-band z^2, not the
         joint Mahalanobis distance).  With the forecast a date's analysis started
         from these are the background-check statistics; with the analysis state,
-        the observation-minus-analysis residuals.  Nothing is modified."""
+        the observation-minus-analysis residuals.  ``joint=True`` adds ``"d2"``
+        (the joint r^T S^-1 r of the counted bands) and ``"logdet"`` (log det S),
+        both [N], linearised at ``state`` for nonlinear bands; under a gate they
+        cover every counted band, rejected ones included.  Nothing is modified."""
         bands = self._device_bands(timestep)
         specs = [s for s, _ in bands]
         table = self._innovation_table(specs, bands)
@@ -747,6 +835,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         out = {"z": torch.full((len(bands), max(N, 1)), float("nan"), dtype=torch.float32, device=dev),
                "chi2": torch.zeros(max(N, 1), dtype=torch.float32, device=dev),
                **{key: torch.zeros(max(N, 1), dtype=torch.uint8, device=dev) for key in ("nobs", "nrej", "status")}}
+        if joint:
+            out.update({key: torch.zeros(max(N, 1), dtype=torch.float32, device=dev) for key in ("d2", "logdet")})
         if N:
             K.innovation(self.n_params, table, st.x, st.P, kind=st.kind, N=N, gate=gate, scope=scope,
                          groups=self._band_groups(timestep, len(specs)), **out)

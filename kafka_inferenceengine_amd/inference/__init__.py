@@ -2,7 +2,8 @@
 from ..utils.blocks import (LazyBlockDiag, blocks_to_sparse, interleaved_to_soa, ntri, pack_blocks,  # noqa: F401
                      pack_matrix, soa_to_interleaved, sparse_to_blocks, tri_indices, tri_pos, unpack_blocks,
                      unpack_matrix)
-from .kf_tools import (NoHessianMethod, PropagatorSpec, blend_prior, hessian_correction,  # noqa: F401
+from .kf_tools import (NoHessianMethod, PropagatorSpec, blend_prior, evidence_blocks,  # noqa: F401
+                       hessian_correction,
                        hessian_correction_multiband, hessian_correction_pixel, identity_propagation,
                        innovation_blocks,
                        make_no_propagation, make_partial_prior_propagator, no_propagation,

@@ -327,6 +327,28 @@ def hessian_correction_multiband(gp, x0, R_mats, innovations, masks, state_mask,
                for g, R, inn, mk, b in zip(gps, R_mats, innovations, masks, range(n_bands)))
 
 
+def _innovation_front(P, y, w, H0, h, kind, ok):
+    """What ``innovation_blocks`` and ``evidence_blocks`` share: the inputs in
+    float64, the covariance ``C`` (identity where the pixel is unscreenable),
+    ``good`` [N], the raw ``z`` [nb, N] and the counted bands [nb, N]."""
+    P = np.asarray(P, dtype=np.float64)
+    y, w, H0 = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (y, w, H0))
+    h = np.asarray(h, dtype=np.float64).reshape(y.shape + (P.shape[-1],))
+    nb, N = y.shape
+    good = np.isfinite(P).all(axis=(1, 2))
+    safe = np.where(good[:, None, None], P, np.eye(P.shape[-1]))
+    good &= np.all(np.linalg.eigvalsh(safe) > 0.0, axis=1)
+    safe = np.where(good[:, None, None], P, np.eye(P.shape[-1]))
+    C = np.linalg.inv(safe) if kind == "precision" else safe
+    s = np.einsum("bpi,pij,bpj->bp", h, C, h)
+    with np.errstate(all="ignore"):
+        z = (y - H0) / np.sqrt(s + 1.0 / np.where(w > 0, w, 1.0))
+    counted = (w > 0) & good[None, :] & np.isfinite(z) & np.isfinite(h).all(axis=2) & np.isfinite(H0)
+    if ok is not None:
+        counted &= np.asarray(ok, dtype=bool).reshape(nb, N)
+    return y, w, H0, h, C, good, z, counted
+
+
 def innovation_blocks(P, y, w, H0, h, kind="precision", gate=0.0, scope="group", groups=None, ok=None):
     """Float64 oracle of the innovation statistics and the chi-square gate
     (``ops.kernels.innovation``, csrc/kf_core.h ``pixel_innovation``) on host blocks.
@@ -352,21 +374,8 @@ def innovation_blocks(P, y, w, H0, h, kind="precision", gate=0.0, scope="group",
         raise ValueError("scope must be 'band' or 'group'")
     if not gate >= 0.0:
         raise ValueError("gate must be >= 0")
-    P = np.asarray(P, dtype=np.float64)
-    y, w, H0 = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (y, w, H0))
-    h = np.asarray(h, dtype=np.float64).reshape(y.shape + (P.shape[-1],))
+    y, w, H0, h, C, good, z, counted = _innovation_front(P, y, w, H0, h, kind, ok)
     nb, N = y.shape
-    good = np.isfinite(P).all(axis=(1, 2))
-    safe = np.where(good[:, None, None], P, np.eye(P.shape[-1]))
-    good &= np.all(np.linalg.eigvalsh(safe) > 0.0, axis=1)
-    safe = np.where(good[:, None, None], P, np.eye(P.shape[-1]))
-    C = np.linalg.inv(safe) if kind == "precision" else safe
-    s = np.einsum("bpi,pij,bpj->bp", h, C, h)
-    with np.errstate(all="ignore"):
-        z = (y - H0) / np.sqrt(s + 1.0 / np.where(w > 0, w, 1.0))
-    counted = (w > 0) & good[None, :] & np.isfinite(z) & np.isfinite(h).all(axis=2) & np.isfinite(H0)
-    if ok is not None:
-        counted &= np.asarray(ok, dtype=bool).reshape(nb, N)
     z = np.where(counted, z, np.nan)
     chi2 = np.where(good, np.sum(np.where(counted, z, 0.0) ** 2, axis=0), np.nan)
     nobs = counted.sum(axis=0).astype(np.int64)
@@ -383,3 +392,39 @@ def innovation_blocks(P, y, w, H0, h, kind="precision", gate=0.0, scope="group",
     else:
         reject = over
     return z, chi2, nobs, reject
+
+
+def evidence_blocks(P, y, w, H0, h, kind="precision", ok=None):
+    """Float64 oracle of the joint innovation statistic and the Gaussian log
+    evidence of one date (``ops.kernels.innovation`` ``d2`` / ``logdet``), on the
+    inputs of ``innovation_blocks`` and with its counting rule.
+
+    Per pixel, over the counted bands, S = H C H^T + diag(1 / w) with C the
+    covariance and r = y - H0.  Returns ``(d2, logdet, nobs, loglik)``, each
+    [N]: d2 = r^T S^-1 r (``np.linalg.solve``), logdet = log det S
+    (``slogdet``), loglik = -(d2 + logdet + nobs log 2 pi) / 2: the textbook
+    formula, free of the band order, not the kernel's band-by-band recursion.
+    For nonlinear bands this is the linearised (extended-filter) evidence at the
+    state H0 and h were evaluated at.  An unscreenable pixel gives NaN (nobs 0),
+    a pixel with nothing counted zeros."""
+    if kind not in ("precision", "covariance"):
+        raise ValueError("kind must be 'precision' or 'covariance'")
+    y, w, H0, h, C, good, _, counted = _innovation_front(P, y, w, H0, h, kind, ok)
+    N = y.shape[1]
+    d2 = np.zeros(N)
+    logdet = np.zeros(N)
+    for p in range(N):
+        if not good[p]:
+            d2[p] = logdet[p] = np.nan
+            continue
+        sel = counted[:, p]
+        if not sel.any():
+            continue
+        Hp = h[sel, p]
+        S = Hp @ C[p] @ Hp.T + np.diag(1.0 / w[sel, p])
+        r = y[sel, p] - H0[sel, p]
+        d2[p] = r @ np.linalg.solve(S, r)
+        logdet[p] = np.linalg.slogdet(S)[1]
+    nobs = counted.sum(axis=0).astype(np.int64)
+    loglik = -0.5 * (d2 + logdet + nobs * np.log(2.0 * np.pi))
+    return d2, logdet, nobs, loglik

@@ -1634,7 +1634,7 @@ def _screened_dtype(obs):
 
 
 def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=None, nobs=None, nrej=None, status,
-               gate=0.0, scope="group", groups=None, screened=None):
+               gate=0.0, scope="group", groups=None, screened=None, d2=None, logdet=None):
     """Innovation statistics and the chi-square gate, per pixel (csrc/kf_core.h
     ``pixel_innovation``).  ``x`` [n_p, ld] and ``p`` [ntri, ld] (packed rows of
     P^-1 for ``kind="precision"``, of P for ``"covariance"``) are the state the
@@ -1652,6 +1652,16 @@ def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=N
       carries the band's nodata code with the rejected pixels set to that code
       (float32 ``w`` for OBS_F32, int16 ``dn`` / bf16 ``w`` / bf16 ``y`` for
       OBS_DN16 / OBS_BF16 / OBS_BF16Y).  The source planes are never written.
+    * ``d2`` float32 [>= N]: the joint Mahalanobis distance r^T S^-1 r of the
+      counted bands, S = H P H^T + R over them: chi-square with ``nobs`` degrees
+      of freedom under the linearised model;
+    * ``logdet`` float32 [>= N]: log det S (natural logarithm), so that
+      -(d2 + logdet + nobs log 2 pi) / 2 is the Gaussian log evidence of the
+      pixel's counted observations, linearised at ``x``.  Both are 0 where no
+      band is counted and NaN where the pixel is unscreenable or a step variance
+      of the band-by-band recursion is not positive and finite.  Asking for
+      either launches the joint instantiation of the kernel (more registers);
+      every other output keeps its bits.
 
     ``gate`` k > 0 rejects band b where |z_b| > k (``scope="band"``) or every
     counted band of a group in which any band exceeds k (``scope="group"``,
@@ -1685,6 +1695,8 @@ def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=N
     _check_vec(chi2, N, "chi2", torch.float32, dev)
     _check_vec(nobs, N, "nobs", torch.uint8, dev)
     _check_vec(nrej, N, "nrej", torch.uint8, dev)
+    _check_vec(d2, N, "d2", torch.float32, dev)
+    _check_vec(logdet, N, "logdet", torch.float32, dev)
     _check_soa(z, nb, N, "z", device=dev)
     grp = None
     if groups is not None:
@@ -1716,7 +1728,7 @@ def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=N
     e.innovation(n_params, _ptr(x), _ptr(p), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION,
                  bands.ptr, nb, _ptr(grp), gate, e.INNOV_SCOPE_BAND if scope == "band" else e.INNOV_SCOPE_GROUP,
                  _ptr(z), 0 if z is None else z.shape[1], _ptr(chi2), _ptr(nobs), _ptr(nrej), _ptr(status),
-                 _ptr(ptrs), N, ld, _dev(x), _stream(x))
+                 _ptr(ptrs), N, ld, _dev(x), _stream(x), _ptr(d2), _ptr(logdet))
 
 
 def reduce_partials(partials: torch.Tensor, out: torch.Tensor | None = None):

@@ -11,6 +11,10 @@ started on the device).  One JSON line per record, also appended to ``--record``
 prosail10 workloads (the sources, emulators and prior of the benchmark, the
 prior as the state): statistics only, and with a gate writing the screened
 planes.  The kernel evaluates the GP bands with the VALU record loop.
+``joint``: the joint instantiation (``innovation_joint_kernel``: the statistics
+plus d2 = r^T S^-1 r and log det S); ``joint_kept``: the second launch of a
+gated date under ``innovation_evidence`` (gate 0 on the screened bands, writing
+status, nobs, d2 and logdet only).
 
     python scripts/bench_innovation.py kernels --configs tip7 prosail10 --size 10980
 
@@ -108,12 +112,27 @@ def one_kernel_config(config, size, reps, gate, device=None):
             ms.append(e0.elapsed_time(e1))
         return statistics.median(ms), min(ms), max(ms)
 
+    import dataclasses
+    d2, logdet = (torch.empty(N, dtype=torch.float32, device=dev) for _ in range(2))
+    # the screened bands of the gated launch: what the second launch of a gated date reads
+    kept = [(s, dataclasses.replace(db, **{kf._nodata_plane(db): t})) for (s, db), t in zip(bands, screened)]
     out = []
-    for name, kw in (("stats", dict(gate=0.0)), ("gated", dict(gate=gate, screened=screened))):
-        med, lo, hi = timed(lambda: K.innovation(n, table, st.x, st.P, kind=st.kind, N=N, chi2=chi2, nobs=nobs,
-                                                 nrej=nrej, status=status, groups=groups, **kw))
+    for name, kw in (("stats", dict(gate=0.0)), ("gated", dict(gate=gate, screened=screened)),
+                     ("joint", dict(gate=0.0, d2=d2, logdet=logdet)), ("joint_kept", None)):
+        if kw is None:
+            table2 = kf._innovation_table(specs, kept)
+            kw = dict(gate=0.0)
+            med, lo, hi = timed(lambda: K.innovation(n, table2, st.x, st.P, kind=st.kind, N=N, nobs=nobs,
+                                                     status=status, d2=d2, logdet=logdet))
+        else:
+            med, lo, hi = timed(lambda: K.innovation(n, table, st.x, st.P, kind=st.kind, N=N, chi2=chi2, nobs=nobs,
+                                                     nrej=nrej, status=status, groups=groups, **kw))
         seen = int(nobs.sum(dtype=torch.int64).item())
-        out.append({"bench": "kernel", "kernel": f"innovation_kernel/{name}", "config": config, "size": size,
+        fin = torch.isfinite(d2)
+        joint = {} if name in ("stats", "gated") else {
+            "d2_per_obs": round(float(torch.where(fin, d2, torch.zeros_like(d2)).sum(dtype=torch.float64).item())
+                                / max(seen, 1), 4), "joint_nan": int((~fin).sum().item())}
+        out.append({"bench": "kernel", "kernel": f"innovation_kernel/{name}", **joint, "config": config, "size": size,
                     "device": dev.type, "n_params": n, "n_bands": len(bands), "kind": st.kind, "gate": kw["gate"],
                     "ms_median": round(med, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4), "reps": reps,
                     "observed_bands": seen, "rejected_bands": int(nrej.sum(dtype=torch.int64).item()),
