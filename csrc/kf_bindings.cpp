@@ -48,6 +48,22 @@ static void set_arr(A (&dst)[N], const std::vector<A>& v, const char* name) {
 template <typename A, size_t N>
 static std::vector<A> get_arr(const A (&src)[N]) { return std::vector<A>(src, src + N); }
 
+// the raster scatter of unpack and marginal
+static RasterArgs raster_args(uintptr_t x, uintptr_t p, int kind, int64_t N, int64_t ld, uintptr_t idx, uintptr_t mean,
+                              uintptr_t unc, int64_t plane) {
+  RasterArgs a{};
+  a.N = N;
+  a.ld = ld;
+  a.x = P<const float>(x);
+  a.p = P<const float>(p);
+  a.kind = kind;
+  a.idx = P<const int64_t>(idx);
+  a.mean = P<float>(mean);
+  a.unc = P<float>(unc);
+  a.plane = plane;
+  return a;
+}
+
 #define PTR_FIELD(cls, name, T)                                                                     \
   def_property(#name, [](const cls& s) { return (uintptr_t)s.name; },                              \
                [](cls& s, uintptr_t v) { s.name = reinterpret_cast<T>(v); })
@@ -360,16 +376,29 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
   });
   m.def("invert", [](int np, uintptr_t src, uintptr_t dst, int64_t N, int64_t ld, uintptr_t st, bool device,
                      uintptr_t stream) {
-    if (device) check_hip(dev_invert(np, P<const float>(src), P<float>(dst), N, ld, P<uint8_t>(st),
-                                     (hipStream_t)stream), "invert");
-    else check_host(host_invert(np, P<const float>(src), P<float>(dst), N, ld, P<uint8_t>(st)), "invert");
+    InvertArgs a{};
+    a.N = N;
+    a.ld = ld;
+    a.src = P<const float>(src);
+    a.dst = P<float>(dst);
+    a.status = P<uint8_t>(st);
+    if (device) check_hip(dev_invert(np, a, (hipStream_t)stream), "invert");
+    else check_host(host_invert(np, a), "invert");
   });
   m.def("operator_eval", [](int np, uintptr_t bands, int band, uintptr_t x, int64_t N, int64_t ld, uintptr_t h0,
                             uintptr_t h, int64_t h_ld, uintptr_t ok, bool device, uintptr_t stream) {
-    if (device) check_hip(dev_operator(np, P<const BandDesc>(bands), band, P<const float>(x), N, ld, P<float>(h0),
-                                       P<float>(h), h_ld, P<uint8_t>(ok), (hipStream_t)stream), "operator_eval");
-    else check_host(host_operator(np, P<const BandDesc>(bands), band, P<const float>(x), N, ld, P<float>(h0),
-                                  P<float>(h), h_ld, P<uint8_t>(ok)), "operator_eval");
+    OperatorArgs a{};
+    a.N = N;
+    a.ld = ld;
+    a.bands = P<const BandDesc>(bands);
+    a.band = band;
+    a.x = P<const float>(x);
+    a.h0 = P<float>(h0);
+    a.h = P<float>(h);
+    a.h_ld = h_ld;
+    a.ok_out = P<uint8_t>(ok);
+    if (device) check_hip(dev_operator(np, a, (hipStream_t)stream), "operator_eval");
+    else check_host(host_operator(np, a), "operator_eval");
   });
   m.def("exp_split_probe", [](uintptr_t e, uintptr_t mh, uintptr_t ml, uintptr_t mv, int64_t n8, bool mixlo,
                               uintptr_t stream) {
@@ -379,34 +408,45 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
   m.def("gp_operator_supported", [](int np, int d) { return gp_operator_supported(np, d); });
   m.def("gp_operator", [](int np, int d, uintptr_t bands, int nb, uintptr_t x, int64_t N, int64_t ld, uintptr_t h0,
                           uintptr_t h, int64_t ldh, bool device, uintptr_t stream) {
-    if (device) check_hip(dev_gp_operator(np, d, P<const BandDesc>(bands), nb, P<const float>(x), N, ld, P<float>(h0),
-                                          P<float>(h), ldh, (hipStream_t)stream), "gp_operator");
-    else check_host(host_gp_operator(np, P<const BandDesc>(bands), nb, P<const float>(x), N, ld, P<float>(h0),
-                                     P<float>(h), ldh), "gp_operator");
+    GpOperatorArgs a{};
+    a.N = N;
+    a.ld = ld;
+    a.bands = P<const BandDesc>(bands);
+    a.nb = nb;
+    a.x = P<const float>(x);
+    a.h0 = P<float>(h0);
+    a.h = P<float>(h);
+    a.ldh = ldh;
+    if (device) check_hip(dev_gp_operator(np, d, a, (hipStream_t)stream), "gp_operator");
+    else check_host(host_gp_operator(np, a), "gp_operator");
   });
-  m.def("hessian", [](int np, uintptr_t bands, int nb, uintptr_t x, uintptr_t a, int64_t N, int64_t ld,
+  m.def("hessian", [](int np, uintptr_t bands, int nb, uintptr_t x, uintptr_t a_rows, int64_t N, int64_t ld,
                       bool device, uintptr_t stream) {
-    if (device) check_hip(dev_hessian(np, P<const BandDesc>(bands), nb, P<const float>(x), P<float>(a), N, ld,
-                                      (hipStream_t)stream), "hessian");
-    else check_host(host_hessian(np, P<const BandDesc>(bands), nb, P<const float>(x), P<float>(a), N, ld),
-                    "hessian");
+    HessianArgs a{};
+    a.N = N;
+    a.ld = ld;
+    a.bands = P<const BandDesc>(bands);
+    a.n_bands = nb;
+    a.x = P<const float>(x);
+    a.a = P<float>(a_rows);
+    if (device) check_hip(dev_hessian(np, a, (hipStream_t)stream), "hessian");
+    else check_host(host_hessian(np, a), "hessian");
   });
-  m.def("unpack", [](int np, uintptr_t x, uintptr_t a, int64_t N, int64_t ld, uintptr_t idx, uintptr_t mean,
+  // unpack: mean and 1/sqrt(diag(P^-1)) onto the raster from the precision rows p
+  m.def("unpack", [](int np, uintptr_t x, uintptr_t p, int64_t N, int64_t ld, uintptr_t idx, uintptr_t mean,
                      uintptr_t unc, int64_t plane, bool device, uintptr_t stream) {
-    if (device) check_hip(dev_unpack(np, P<const float>(x), P<const float>(a), N, ld, P<const int64_t>(idx),
-                                     P<float>(mean), P<float>(unc), plane, (hipStream_t)stream), "unpack");
-    else check_host(host_unpack(np, P<const float>(x), P<const float>(a), N, ld, P<const int64_t>(idx),
-                                P<float>(mean), P<float>(unc), plane), "unpack");
+    const RasterArgs a = raster_args(x, p, 0, N, ld, idx, mean, unc, plane);
+    if (device) check_hip(dev_unpack(np, a, (hipStream_t)stream), "unpack");
+    else check_host(host_unpack(np, a), "unpack");
   });
   // marginal std rasters: sqrt(diag(P)) from the precision (MARG_PRECISION) or covariance rows
   m.attr("MARG_PRECISION") = MARG_PRECISION;
   m.attr("MARG_COVARIANCE") = MARG_COVARIANCE;
   m.def("marginal", [](int np, uintptr_t x, uintptr_t p, int kind, int64_t N, int64_t ld, uintptr_t idx,
                        uintptr_t mean, uintptr_t unc, int64_t plane, bool device, uintptr_t stream) {
-    if (device) check_hip(dev_marginal(np, P<const float>(x), P<const float>(p), kind, N, ld, P<const int64_t>(idx),
-                                       P<float>(mean), P<float>(unc), plane, (hipStream_t)stream), "marginal");
-    else check_host(host_marginal(np, P<const float>(x), P<const float>(p), kind, N, ld, P<const int64_t>(idx),
-                                  P<float>(mean), P<float>(unc), plane), "marginal");
+    const RasterArgs a = raster_args(x, p, kind, N, ld, idx, mean, unc, plane);
+    if (device) check_hip(dev_marginal(np, a, (hipStream_t)stream), "marginal");
+    else check_host(host_marginal(np, a), "marginal");
   });
   // RTS smoother, one backward step: filtered (x_a, p_a of `kind`) and the next step's smoothed
   // (x_next, covariance p_next) -> smoothed (x_out, covariance p_out), status 1 where a pixel fell back

@@ -775,25 +775,64 @@ KF_HD void chol_inv_diag(const float (&U)[ntri(NP)], float (&d)[NP]) {
   }
 }
 
+// One auxiliary per-pixel pass = an *Args struct (N pixels, the launch's
+// operands), a pixel_* body and this tag.  Both runners are written once over
+// the tag: pixel_kernel<NP, OP> (kf_device.h) and host_pixels<OP> (kf_host.cpp)
+// call OP::px<NP>(args, p) for every p < args.N.
+#define KF_PIXEL_OP(OP, ARGS, FN)                                                   \
+  struct OP {                                                                       \
+    using Args = ARGS;                                                              \
+    template <int NP>                                                               \
+    static KF_HD void px(const Args& a, int64_t p) { FN<NP>(a, p); }                \
+  }
+
+// Output rasters of the unpack and marginal passes: per-pixel mean and
+// uncertainty scattered onto planes of `plane` cells each; idx == nullptr means
+// the identity raster map, a null mean / unc plane set is not written.
+struct RasterArgs {
+  int64_t N, ld;
+  const float* x;        // [NP][ld]
+  const float* p;        // [NT][ld] packed rows (unpack: P^-1; marginal: see kind)
+  int32_t kind;          // marginal only: MARG_PRECISION / MARG_COVARIANCE
+  const int64_t* idx;    // [N] raster cell of each pixel, or null
+  float* mean;           // [NP][plane] or null
+  float* unc;            // [NP][plane] or null
+  int64_t plane;
+};
+
+// Output unpack (observations.py:374-376, 392-393): mean and 1/sqrt(diag(P^-1)).
+template <int NP>
+KF_HD void pixel_unpack(const RasterArgs& a, int64_t p) {
+  const int64_t r = a.idx ? a.idx[p] : p;
+  KF_DCHECK(r >= 0 && r < a.plane);
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    if (a.mean) a.mean[j * a.plane + r] = a.x[j * a.ld + p];
+    if (a.unc) a.unc[j * a.plane + r] = kf_rsqrt(a.p[tri(NP, j, j) * a.ld + p]);
+  }
+}
+KF_PIXEL_OP(OpUnpack, RasterArgs, pixel_unpack);
+
 // Marginal posterior standard deviation of pixel p, sqrt(diag(P)), scattered
 // onto the raster with the mean (the unpack pass writes the conditional one,
-// 1/sqrt(diag(P^-1))).  kind: what the packed rows p_in hold.
+// 1/sqrt(diag(P^-1))).  kind: what the packed rows a.p hold.
 //   MARG_PRECISION: P^-1, every row read (rows an analysis kernel leaves out
 //     are stored as exact zeros), factorised and diag(P) formed by
 //     chol_inv_diag.  A pixel whose block is not SPD, or yields a variance that
 //     is not finite and positive, gets NaN in all NP planes.
 //   MARG_COVARIANCE: P itself (the gain form's state); only the diagonal rows
 //     are read, NaN where an entry is not finite and positive.
-// idx == nullptr: the identity raster map.
 constexpr int MARG_PRECISION = 0;
 constexpr int MARG_COVARIANCE = 1;
 template <int NP>
-KF_HD void pixel_marginal(const float* x, const float* p_in, int kind, int64_t N, int64_t ld, const int64_t* idx,
-                          float* mean, float* unc, int64_t plane, int64_t p) {
+KF_HD void pixel_marginal(const RasterArgs& a, int64_t p) {
   constexpr int NT = ntri(NP);
-  KF_DCHECK(p >= 0 && p < N && N <= ld);
-  (void)N;
-  const int64_t r = idx ? idx[p] : p;
+  KF_DCHECK(p >= 0 && p < a.N && a.N <= a.ld);
+  const float *x = a.x, *p_in = a.p;
+  float *mean = a.mean, *unc = a.unc;
+  const int64_t ld = a.ld, plane = a.plane;
+  const int kind = a.kind;
+  const int64_t r = a.idx ? a.idx[p] : p;
   KF_DCHECK(r >= 0 && r < plane);
   if (mean) {
 #pragma unroll
@@ -818,6 +857,7 @@ KF_HD void pixel_marginal(const float* x, const float* p_in, int kind, int64_t N
   for (int j = 0; j < NP; ++j)
     unc[j * plane + r] = (ok && (d[j] > 0.f) && finitef(d[j])) ? sqrtf(d[j]) : __builtin_nanf("");
 }
+KF_PIXEL_OP(OpMarginal, RasterArgs, pixel_marginal);
 
 template <int NP, class M = StructDense>
 KF_HD void symv(const float (&A)[ntri(NP)], const float (&x)[NP], float (&y)[NP]) {
@@ -1063,6 +1103,7 @@ KF_HD void pixel_smooth(const SmoothArgs& a, int64_t p) {
   }
   a.status[p3] = ok ? 0 : 1;
 }
+KF_PIXEL_OP(OpSmooth, SmoothArgs, pixel_smooth);
 
 KF_HD float bf16_to_f32(uint16_t b) {
   const uint32_t u = (uint32_t)b << 16;
@@ -1355,6 +1396,70 @@ KF_HD bool eval_operator(const BandDesc& bd, int64_t p, int64_t ld, const float 
   return ok && fin;
 }
 
+// Standalone operator evaluation of one band: H0 and, optionally, the Jacobian
+// rows h and the operator's validity ok_out at every pixel.
+struct OperatorArgs {
+  int64_t N, ld;
+  const BandDesc* bands;
+  int32_t band;
+  const float* x;    // [NP][ld]
+  float* h0;         // [N]
+  float* h;          // [NP][h_ld] or null
+  int64_t h_ld;
+  uint8_t* ok_out;   // [N] or null
+};
+template <int NP>
+KF_HD void pixel_operator(const OperatorArgs& a, int64_t p) {
+  // loop-invariant: the pixel loop of either runner fetches the descriptor once
+  const BandDesc bd = cptr(a.bands)[a.band];
+  float xv[NP], hv[NP], H0;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) xv[j] = a.x[j * a.ld + p];
+  const bool ok = eval_operator<NP>(bd, p, a.ld, xv, H0, hv);
+  a.h0[p] = H0;
+  if (a.h) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) a.h[j * a.h_ld + p] = hv[j];
+  }
+  if (a.ok_out) a.ok_out[p] = ok ? 1 : 0;
+}
+KF_PIXEL_OP(OpOperator, OperatorArgs, pixel_operator);
+
+// K2 split path: GP emulator value + Jacobian of every band of a chunk into
+// HBM (h0[b][p], h[b*NP+j][p]).  Without the analysis' packed A/b in registers
+// it runs at high occupancy; used for large input counts (PROSAIL D=10) and
+// many bands (multi-sensor), followed by the OP_PRECOMP analysis kernel.  Pixels
+// whose observation is masked skip the GP (wave-level skip under clouds) and
+// get zero rows.  eval(bd, b, xv, H0, hv): the band evaluator, as gain_pixel's
+// EVAL -- the device's gp_eval at its compiled (D, UNR), the host's
+// eval_operator.
+struct GpOperatorArgs {
+  int64_t N, ld;
+  const BandDesc* bands;
+  int32_t nb;
+  const float* x;   // [NP][ld]
+  float* h0;        // [nb][ldh]
+  float* h;         // [nb * NP][ldh]
+  int64_t ldh;
+};
+template <int NP, class EVAL>
+KF_HD void pixel_gp_operator(const GpOperatorArgs& a, int64_t p, EVAL&& eval) {
+  float xv[NP];
+#pragma unroll
+  for (int j = 0; j < NP; ++j) xv[j] = a.x[j * a.ld + p];
+  for (int b = 0; b < a.nb; ++b) {
+    const BandDesc bd = cptr(a.bands)[b];
+    float y, w, H0 = 0.f, hv[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) hv[j] = 0.f;
+    decode_obs(bd, p, y, w);
+    if (w > 0.f) eval(bd, b, xv, H0, hv);
+    a.h0[b * a.ldh + p] = H0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) a.h[((int64_t)b * NP + j) * a.ldh + p] = hv[j];
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Innovation statistics and the background check of pixel p.  For a state
 // (x, rows p of kind MARG_PRECISION / MARG_COVARIANCE: the forecast the analysis
@@ -1606,6 +1711,14 @@ KF_HD void pixel_innovation(const InnovationArgs& a, int64_t p) {
   if (a.nrej) a.nrej[p] = (uint8_t)__builtin_popcountll(rej);
   a.status[p] = ok ? 0 : 1;
 }
+// JOINT (innovation_joint): an instantiation of its own, so a launch without the
+// joint statistic runs at the plain body's register count
+template <bool JOINT>
+struct OpInnovation {
+  using Args = InnovationArgs;
+  template <int NP>
+  static KF_HD void px(const Args& a, int64_t p) { pixel_innovation<NP, JOINT>(a, p); }
+};
 
 // ---------------------------------------------------------------------------
 // K4/K5: propagation and prior blending for one pixel.
@@ -1802,6 +1915,7 @@ KF_HD void pixel_propagate(const PropArgs& a, int64_t p) {
   for (int t = 0; t < NT; ++t) KF_PX(a.p_f, t * ld, p) = P[t];
   if (a.status) KF_PX(a.status, 0, p) |= st;
 }
+KF_PIXEL_OP(OpPropagate, PropArgs, pixel_propagate);
 
 // Full-form right-hand side b = r + A x0 from the correction form r (DELTA).
 template <int NP, class M = StructDense>
@@ -2186,19 +2300,28 @@ KF_HD float pixel_analysis(const AnalysisArgs& a, int64_t p, float& dn_first) {
   }
 }
 
-// Packed SPD inverse (covariance <-> precision conversion).
+// Packed SPD inverse (covariance <-> precision conversion); ST_NONSPD is set in
+// status (optional) where the block is not positive definite.
+struct InvertArgs {
+  int64_t N, ld;
+  const float* src;   // [NT][ld]
+  float* dst;         // [NT][ld]
+  uint8_t* status;    // [N] or null
+};
 template <int NP>
-KF_HD bool pixel_invert(const float* src, float* dst, int64_t ld, int64_t p) {
+KF_HD void pixel_invert(const InvertArgs& a, int64_t p) {
   constexpr int NT = ntri(NP);
+  const int64_t ld = a.ld;
   float U[NT], R[NT];
 #pragma unroll
-  for (int t = 0; t < NT; ++t) U[t] = KF_PX(src, t * ld, p);
+  for (int t = 0; t < NT; ++t) U[t] = KF_PX(a.src, t * ld, p);
   const bool ok = chol_packed<NP>(U);
   chol_inverse<NP>(U, R);
 #pragma unroll
-  for (int t = 0; t < NT; ++t) KF_PX(dst, t * ld, p) = R[t];
-  return ok;
+  for (int t = 0; t < NT; ++t) KF_PX(a.dst, t * ld, p) = R[t];
+  if (a.status && !ok) a.status[p] |= ST_NONSPD;
 }
+KF_PIXEL_OP(OpInvert, InvertArgs, pixel_invert);
 
 // ---------------------------------------------------------------------------
 // K1g: covariance / gain form, bands processed as sequential scalar updates
@@ -2608,7 +2731,7 @@ struct JacobiArgs {
   // the plain Jacobi sweep
   const float* z_prev;   // [k][ld_ext] the iterate before z (local part)
   float omega;
-  // FINISH only, optional: fused output dump (unpack_kernel's work) of x and
+  // FINISH only, optional: fused output dump (pixel_unpack's work) of x and
   // 1/sqrt(diag A) with A = a_in (the analysis precision of this iteration)
   float* out_mean;       // [NP][out_plane]
   float* out_unc;        // [NP][out_plane]
@@ -3319,6 +3442,38 @@ KF_HD bool gp_hessian_dispatch(const BandDesc& bd, const float (&x)[NP], float& 
     return false;
   }
 }
+
+struct HessianArgs {
+  int64_t N, ld;
+  const BandDesc* bands;
+  int32_t n_bands;
+  const float* x;   // [NP][ld]
+  float* a;         // [NT][ld] packed A, corrected in place
+};
+template <int NP>
+KF_HD void pixel_hessian(const HessianArgs& a, int64_t p) {
+  constexpr int NT = ntri(NP);
+  float xv[NP], acc[NT];
+#pragma unroll
+  for (int j = 0; j < NP; ++j) xv[j] = a.x[j * a.ld + p];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = 0.f;
+  for (int bi = 0; bi < a.n_bands; ++bi) {
+    const BandDesc bd = cptr(a.bands)[bi];
+    if (bd.op != OP_GP) continue;
+    float y, w;
+    decode_obs(bd, p, y, w);
+    if (!(w > 0.f)) continue;
+    float f, Hs[NT];
+    if (!gp_hessian_dispatch<NP>(bd, xv, f, Hs)) continue;
+    const float s = w * (y - f);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = fmaf(s, Hs[t], acc[t]);
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t) a.a[t * a.ld + p] -= acc[t];
+}
+KF_PIXEL_OP(OpHessian, HessianArgs, pixel_hessian);
 
 // Sizes of the matrix-core GP tables (kf_gp_mfma.h), shared with the host-side
 // kernel choice (kf_plan.h).

@@ -399,156 +399,30 @@ __global__ __launch_bounds__(BLOCK) void jacobi_kernel(JacobiArgs a) {
   if (a.partials) block_partial(acc, a.partials);
 }
 
-template <int NP>
-__global__ __launch_bounds__(BLOCK) void propagate_kernel(PropArgs a) {
+// Every auxiliary per-pixel pass (kf_core.h KF_PIXEL_OP: propagate, invert,
+// operator, gp_operator, hessian, unpack, marginal, smooth, innovation): one
+// pixel per thread, grid-stride, every SoA row read and written coalesced.  The
+// pass is the tag OP; its arguments' N is the pixel count.
+template <int NP, class OP>
+__global__ __launch_bounds__(BLOCK) void pixel_kernel(const typename OP::Args a) {
   const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < a.N; p += stride)
-    pixel_propagate<NP>(a, p);
+  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < a.N; p += stride) OP::template px<NP>(a, p);
 }
 
-template <int NP>
-__global__ __launch_bounds__(BLOCK) void invert_kernel(const float* src, float* dst, int64_t N, int64_t ld,
-                                                      uint8_t* status) {
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < N; p += stride) {
-    const bool ok = pixel_invert<NP>(src, dst, ld, p);
-    if (status && !ok) status[p] |= ST_NONSPD;
+// K2 split path (pixel_gp_operator) with the VALU GP of D inputs, UNR record
+// pairs per step.  RELOAD: the descriptor's epilogue fields are re-read after
+// the record stream (61 instead of 91 VGPRs, 26 instead of 233 SGPR spills at
+// D=10).
+template <int D, int UNR>
+struct OpGpOperator {
+  using Args = GpOperatorArgs;
+  template <int NP>
+  static __device__ __forceinline__ void px(const Args& a, int64_t p) {
+    pixel_gp_operator<NP>(a, p, [&](const BandDesc& bd, int b, const float (&xv)[NP], float& H0, float (&hv)[NP]) {
+      gp_eval<NP, D, UNR, false, true>(bd, xv, H0, hv, a.bands + b);
+    });
   }
-}
-
-// Standalone operator evaluation (H0 and Jacobian rows) for one band.
-template <int NP>
-__global__ __launch_bounds__(BLOCK) void operator_kernel(const BandDesc* bands, int band, const float* x,
-                                                        int64_t N, int64_t ld, float* h0, float* h,
-                                                        int64_t h_ld, uint8_t* ok_out) {
-  const BandDesc bd = cptr(bands)[band];
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < N; p += stride) {
-    float xv[NP], hv[NP], H0;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) xv[j] = x[j * ld + p];
-    const bool ok = eval_operator<NP>(bd, p, ld, xv, H0, hv);
-    h0[p] = H0;
-    if (h) {
-#pragma unroll
-      for (int j = 0; j < NP; ++j) h[j * h_ld + p] = hv[j];
-    }
-    if (ok_out) ok_out[p] = ok ? 1 : 0;
-  }
-}
-
-// K2 split path: GP emulator value + Jacobian for a chunk of bands into HBM
-// (h0[b][p], h[b*NP+j][p]).  Without the analysis' packed A/b in registers it
-// runs at high occupancy; used for large input counts (PROSAIL D=10) and many
-// bands (multi-sensor), followed by the OP_PRECOMP analysis kernel.  Pixels
-// whose observation is masked skip the GP (wave-level skip under clouds).
-template <int NP, int D, int UNR>
-__global__ __launch_bounds__(BLOCK) void gp_operator_kernel(const BandDesc* bands, int nb, const float* x,
-                                                           int64_t N, int64_t ld, float* h0, float* h,
-                                                           int64_t ldh) {
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < N; p += stride) {
-    float xv[NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) xv[j] = x[j * ld + p];
-    for (int b = 0; b < nb; ++b) {
-      const BandDesc bd = cptr(bands)[b];
-      float y, w, H0 = 0.f, hv[NP];
-#pragma unroll
-      for (int j = 0; j < NP; ++j) hv[j] = 0.f;
-      decode_obs(bd, p, y, w);
-      // RELOAD: the descriptor's epilogue fields are re-read after the record
-      // stream (61 instead of 91 VGPRs, 26 instead of 233 SGPR spills at D=10)
-      if (w > 0.f) gp_eval<NP, D, UNR, false, true>(bd, xv, H0, hv, bands + b);
-      h0[b * ldh + p] = H0;
-#pragma unroll
-      for (int j = 0; j < NP; ++j) h[((int64_t)b * NP + j) * ldh + p] = hv[j];
-    }
-  }
-}
-
-// K6 Hessian correction: A -= w (y - H0(x)) d2f/dx2 for every GP band.
-template <int NP>
-__global__ __launch_bounds__(BLOCK) void hessian_kernel(const BandDesc* bands, int n_bands, const float* x,
-                                                       float* a, int64_t N, int64_t ld) {
-  constexpr int NT = ntri(NP);
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < N; p += stride) {
-    float xv[NP], acc[NT];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) xv[j] = x[j * ld + p];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = 0.f;
-    for (int bi = 0; bi < n_bands; ++bi) {
-      const BandDesc bd = cptr(bands)[bi];
-      if (bd.op != OP_GP) continue;
-      float y, w;
-      decode_obs(bd, p, y, w);
-      if (!(w > 0.f)) continue;
-      float f, Hs[NT];
-      if (!gp_hessian_dispatch<NP>(bd, xv, f, Hs)) continue;
-      const float s = w * (y - f);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = fmaf(s, Hs[t], acc[t]);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) a[t * ld + p] -= acc[t];
-  }
-}
-
-// Output unpack (observations.py:374-376, 392-393): mean and 1/sqrt(diag(P^-1))
-// scattered onto the raster; idx==nullptr means the identity map.
-template <int NP>
-__global__ __launch_bounds__(BLOCK) void unpack_kernel(const float* x, const float* a, int64_t N, int64_t ld,
-                                                      const int64_t* idx, float* mean, float* unc,
-                                                      int64_t plane) {
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < N; p += stride) {
-    const int64_t r = idx ? idx[p] : p;
-    KF_DCHECK(r >= 0 && r < plane);
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      if (mean) mean[j * plane + r] = x[j * ld + p];
-      if (unc) unc[j * plane + r] = kf_rsqrt(a[tri(NP, j, j) * ld + p]);
-    }
-  }
-}
-
-// Marginal output: mean and sqrt(diag(P)) onto the raster, from the stored
-// precision (factorised per pixel) or covariance rows (pixel_marginal).  One
-// pixel per thread; every SoA row is read coalesced.
-template <int NP>
-__global__ __launch_bounds__(BLOCK) void marginal_kernel(const float* x, const float* p_in, int kind, int64_t N,
-                                                        int64_t ld, const int64_t* idx, float* mean, float* unc,
-                                                        int64_t plane) {
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < N; p += stride)
-    pixel_marginal<NP>(x, p_in, kind, N, ld, idx, mean, unc, plane, p);
-}
-
-// RTS smoother, one backward step (pixel_smooth): one pixel per thread, every
-// SoA row read and written coalesced.
-template <int NP>
-__global__ __launch_bounds__(BLOCK) void smooth_kernel(const SmoothArgs a) {
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < a.N; p += stride) pixel_smooth<NP>(a, p);
-}
-
-// Innovation statistics and the chi-square gate (pixel_innovation): one pixel
-// per thread, every SoA row and observation plane read and written coalesced.
-template <int NP>
-__global__ __launch_bounds__(BLOCK) void innovation_kernel(const InnovationArgs a) {
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < a.N; p += stride) pixel_innovation<NP>(a, p);
-}
-// The same with the joint statistic d2 / logdet (pixel_innovation<NP, true>):
-// an instantiation of its own, so a launch without them runs the kernel above
-// at its own register count.
-template <int NP>
-__global__ __launch_bounds__(BLOCK) void innovation_joint_kernel(const InnovationArgs a) {
-  const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < a.N; p += stride) pixel_innovation<NP, true>(a, p);
-}
+};
 
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void gather_kernel(const T* src, const int64_t* idx, T* dst, int64_t n,
@@ -569,17 +443,6 @@ inline int grid_for(int64_t N, int max_blocks) {
   if (g < 1) g = 1;
   return (int)g;
 }
-
-#define KF_NP_SWITCH(np, FN, ...)                 \
-  switch (np) {                                   \
-    case 1: FN<1>(__VA_ARGS__); break;            \
-    case 2: FN<2>(__VA_ARGS__); break;            \
-    case 3: FN<3>(__VA_ARGS__); break;            \
-    case 4: FN<4>(__VA_ARGS__); break;            \
-    case 7: FN<7>(__VA_ARGS__); break;            \
-    case 10: FN<10>(__VA_ARGS__); break;          \
-    default: return hipErrorInvalidValue;         \
-  }
 
 // K1 / K1g launch tables.  Which kernel a launch takes is decided by
 // analysis_plan / gain_plan (kf_plan.h); the lists below are the

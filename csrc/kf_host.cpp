@@ -14,19 +14,6 @@ namespace kf {
 
 static constexpr int HBLOCK = 256;
 
-#define KF_HOST_NP_SWITCH(np, FN, ...)   \
-  switch (np) {                          \
-    case 1: return FN<1>(__VA_ARGS__);   \
-    case 2: return FN<2>(__VA_ARGS__);   \
-    case 3: return FN<3>(__VA_ARGS__);   \
-    case 4: return FN<4>(__VA_ARGS__);   \
-    case 7: return FN<7>(__VA_ARGS__);   \
-    case 10: return FN<10>(__VA_ARGS__); \
-    default: return -1;                  \
-  }
-
-bool host_supported(int np) { return np == 1 || np == 2 || np == 3 || np == 4 || np == 7 || np == 10; }
-
 // Block b handles pixels p = b*256 + t + k*grid*256 (same as the device).
 template <typename F>
 static void grid_stride(int64_t N, int grid, double* partials, F&& f) {
@@ -62,7 +49,7 @@ static void grid_stride_visit(const A& a, int grid, F&& f) {
 }
 
 template <int NP>
-static int h_analysis(const AnalysisArgs& a, int grid) {
+static void h_analysis(const AnalysisArgs& a, int grid) {
   // JRC-TIP structure of the fused forecast's precision (AnalysisArgs.a_struct,
   // checked by the caller): the structure-aware solve, as the SPEC_*_TIP kernels
   const bool tip = NP == 7 && (a.a_struct & A_STRUCT_TIP) && a.prop && a.variant != AV_DENSE_SOLVE;
@@ -76,129 +63,30 @@ static int h_analysis(const AnalysisArgs& a, int grid) {
     if (a.dn_out) a.dn_out[p] = dn;
     return dn;
   });
-  return 0;
-}
-template <int NP>
-static int h_gain(const GainArgs& a, int grid) {
-  grid_stride_visit(a, grid, [&](int64_t p, float& dn1) { return pixel_gain<NP>(a, p, dn1); });
-  return 0;
-}
-template <int NP>
-static int h_jacobi(const JacobiArgs& a, int grid) {
-  grid_stride(a.pn > 0 ? a.pn : a.N, grid, a.partials, [&](int64_t i) { return pixel_jacobi<NP>(a, a.p0 + i); });
-  return 0;
-}
-template <int NP>
-static int h_propagate(const PropArgs& a) {
-#pragma omp parallel for schedule(static)
-  for (int64_t p = 0; p < a.N; ++p) pixel_propagate<NP>(a, p);
-  return 0;
-}
-template <int NP>
-static int h_invert(const float* src, float* dst, int64_t N, int64_t ld, uint8_t* st) {
-#pragma omp parallel for schedule(static)
-  for (int64_t p = 0; p < N; ++p) {
-    const bool ok = pixel_invert<NP>(src, dst, ld, p);
-    if (st && !ok) st[p] |= ST_NONSPD;
-  }
-  return 0;
-}
-template <int NP>
-static int h_operator(const BandDesc* b, int band, const float* x, int64_t N, int64_t ld, float* h0, float* h,
-                      int64_t h_ld, uint8_t* okp) {
-  const BandDesc& bd = b[band];
-#pragma omp parallel for schedule(static)
-  for (int64_t p = 0; p < N; ++p) {
-    float xv[NP], hv[NP], H0;
-    for (int j = 0; j < NP; ++j) xv[j] = x[j * ld + p];
-    const bool ok = eval_operator<NP>(bd, p, ld, xv, H0, hv);
-    h0[p] = H0;
-    if (h)
-      for (int j = 0; j < NP; ++j) h[j * h_ld + p] = hv[j];
-    if (okp) okp[p] = ok ? 1 : 0;
-  }
-  return 0;
-}
-template <int NP>
-static int h_gp_operator(const BandDesc* bands, int nb, const float* x, int64_t N, int64_t ld, float* h0, float* h,
-                         int64_t ldh) {
-#pragma omp parallel for schedule(static)
-  for (int64_t p = 0; p < N; ++p) {
-    float xv[NP];
-    for (int j = 0; j < NP; ++j) xv[j] = x[j * ld + p];
-    for (int b = 0; b < nb; ++b) {
-      const BandDesc& bd = bands[b];
-      float y, w, H0 = 0.f, hv[NP];
-      for (int j = 0; j < NP; ++j) hv[j] = 0.f;
-      decode_obs(bd, p, y, w);
-      if (w > 0.f) eval_operator<NP>(bd, p, ld, xv, H0, hv);
-      h0[b * ldh + p] = H0;
-      for (int j = 0; j < NP; ++j) h[((int64_t)b * NP + j) * ldh + p] = hv[j];
-    }
-  }
-  return 0;
 }
 
-template <int NP>
-static int h_hessian(const BandDesc* bands, int nb, const float* x, float* a, int64_t N, int64_t ld) {
-  constexpr int NT = ntri(NP);
+// Every auxiliary per-pixel pass (kf_core.h KF_PIXEL_OP), as pixel_kernel runs it
+// on the device: OP::px<NP>(a, p) for every p < a.N; -1 for a state size with
+// no compiled code.
+template <class OP>
+static int host_pixels(int np, const typename OP::Args& a) {
+  const bool known = np_dispatch(np, [&](auto n) {
 #pragma omp parallel for schedule(static)
-  for (int64_t p = 0; p < N; ++p) {
-    float xv[NP], acc[NT];
-    for (int j = 0; j < NP; ++j) xv[j] = x[j * ld + p];
-    for (int t = 0; t < NT; ++t) acc[t] = 0.f;
-    for (int bi = 0; bi < nb; ++bi) {
-      const BandDesc& bd = bands[bi];
-      if (bd.op != OP_GP) continue;
-      float y, w;
-      decode_obs(bd, p, y, w);
-      if (!(w > 0.f)) continue;
-      float f, Hs[NT];
-      if (!gp_hessian_dispatch<NP>(bd, xv, f, Hs)) continue;
-      const float s = w * (y - f);
-      for (int t = 0; t < NT; ++t) acc[t] = fmaf(s, Hs[t], acc[t]);
-    }
-    for (int t = 0; t < NT; ++t) a[t * ld + p] -= acc[t];
+    for (int64_t p = 0; p < a.N; ++p) OP::template px<decltype(n)::value>(a, p);
+  });
+  return known ? 0 : -1;
+}
+
+// K2 split path on the host: any band operator, any input count
+struct OpGpOperatorHost {
+  using Args = GpOperatorArgs;
+  template <int NP>
+  static void px(const Args& a, int64_t p) {
+    pixel_gp_operator<NP>(a, p, [&](const BandDesc& bd, int, const float (&xv)[NP], float& H0, float (&hv)[NP]) {
+      eval_operator<NP>(bd, p, a.ld, xv, H0, hv);
+    });
   }
-  return 0;
-}
-template <int NP>
-static int h_unpack(const float* x, const float* a, int64_t N, int64_t ld, const int64_t* idx, float* mean,
-                    float* unc, int64_t plane) {
-#pragma omp parallel for schedule(static)
-  for (int64_t p = 0; p < N; ++p) {
-    const int64_t r = idx ? idx[p] : p;
-    for (int j = 0; j < NP; ++j) {
-      if (mean) mean[j * plane + r] = x[j * ld + p];
-      if (unc) unc[j * plane + r] = kf_rsqrt(a[tri(NP, j, j) * ld + p]);
-    }
-  }
-  return 0;
-}
-template <int NP>
-static int h_marginal(const float* x, const float* p_in, int kind, int64_t N, int64_t ld, const int64_t* idx,
-                      float* mean, float* unc, int64_t plane) {
-#pragma omp parallel for schedule(static)
-  for (int64_t p = 0; p < N; ++p) pixel_marginal<NP>(x, p_in, kind, N, ld, idx, mean, unc, plane, p);
-  return 0;
-}
-template <int NP>
-static int h_smooth(const SmoothArgs& a) {
-#pragma omp parallel for schedule(static)
-  for (int64_t p = 0; p < a.N; ++p) pixel_smooth<NP>(a, p);
-  return 0;
-}
-template <int NP>
-static int h_innovation(const InnovationArgs& a) {
-  if (innovation_joint(a)) {
-#pragma omp parallel for schedule(static)
-    for (int64_t p = 0; p < a.N; ++p) pixel_innovation<NP, true>(a, p);
-    return 0;
-  }
-#pragma omp parallel for schedule(static)
-  for (int64_t p = 0; p < a.N; ++p) pixel_innovation<NP>(a, p);
-  return 0;
-}
+};
 
 // GeoTIFF tiles on the host: the same row encoder as dfl_tile_kernel, rows in
 // order into one byte stream per tile (bit-identical streams).  Dynamic mode:
@@ -462,40 +350,34 @@ int64_t host_inflate_count_tokens(const uint8_t* comp, int64_t comp_bytes, const
   return bad ? -1 : total;
 }
 
-int host_analysis(int np, const AnalysisArgs& a, int grid) { KF_HOST_NP_SWITCH(np, h_analysis, a, grid); }
-int host_gain(int np, const GainArgs& a, int grid) { KF_HOST_NP_SWITCH(np, h_gain, a, grid); }
-int host_jacobi(int np, const JacobiArgs& a, int grid) { KF_HOST_NP_SWITCH(np, h_jacobi, a, grid); }
-int host_propagate(int np, const PropArgs& a) { KF_HOST_NP_SWITCH(np, h_propagate, a); }
-int host_invert(int np, const float* src, float* dst, int64_t N, int64_t ld, uint8_t* st) {
-  KF_HOST_NP_SWITCH(np, h_invert, src, dst, N, ld, st);
+int host_analysis(int np, const AnalysisArgs& a, int grid) {
+  return np_dispatch(np, [&](auto n) { h_analysis<decltype(n)::value>(a, grid); }) ? 0 : -1;
 }
-int host_operator(int np, const BandDesc* b, int band, const float* x, int64_t N, int64_t ld, float* h0, float* h,
-                  int64_t h_ld, uint8_t* ok) {
-  KF_HOST_NP_SWITCH(np, h_operator, b, band, x, N, ld, h0, h, h_ld, ok);
+int host_gain(int np, const GainArgs& a, int grid) {
+  return np_dispatch(np, [&](auto n) {
+    grid_stride_visit(a, grid, [&](int64_t p, float& dn1) { return pixel_gain<decltype(n)::value>(a, p, dn1); });
+  }) ? 0 : -1;
 }
-int host_gp_operator(int np, const BandDesc* b, int nb, const float* x, int64_t N, int64_t ld, float* h0, float* h,
-                     int64_t ldh) {
-  KF_HOST_NP_SWITCH(np, h_gp_operator, b, nb, x, N, ld, h0, h, ldh);
+int host_jacobi(int np, const JacobiArgs& a, int grid) {
+  return np_dispatch(np, [&](auto n) {
+    grid_stride(a.pn > 0 ? a.pn : a.N, grid, a.partials,
+                [&](int64_t i) { return pixel_jacobi<decltype(n)::value>(a, a.p0 + i); });
+  }) ? 0 : -1;
 }
-int host_hessian(int np, const BandDesc* b, int nb, const float* x, float* a, int64_t N, int64_t ld) {
-  KF_HOST_NP_SWITCH(np, h_hessian, b, nb, x, a, N, ld);
+int host_propagate(int np, const PropArgs& a) { return host_pixels<OpPropagate>(np, a); }
+int host_invert(int np, const InvertArgs& a) { return host_pixels<OpInvert>(np, a); }
+int host_operator(int np, const OperatorArgs& a) { return host_pixels<OpOperator>(np, a); }
+int host_gp_operator(int np, const GpOperatorArgs& a) { return host_pixels<OpGpOperatorHost>(np, a); }
+int host_hessian(int np, const HessianArgs& a) { return host_pixels<OpHessian>(np, a); }
+int host_unpack(int np, const RasterArgs& a) { return host_pixels<OpUnpack>(np, a); }
+int host_marginal(int np, const RasterArgs& a) {
+  if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return -1;
+  return host_pixels<OpMarginal>(np, a);
 }
-int host_unpack(int np, const float* x, const float* a, int64_t N, int64_t ld, const int64_t* idx, float* mean,
-                float* unc, int64_t plane) {
-  KF_HOST_NP_SWITCH(np, h_unpack, x, a, N, ld, idx, mean, unc, plane);
-}
-int host_marginal(int np, const float* x, const float* p, int kind, int64_t N, int64_t ld, const int64_t* idx,
-                  float* mean, float* unc, int64_t plane) {
-  if (kind != MARG_PRECISION && kind != MARG_COVARIANCE) return -1;
-  KF_HOST_NP_SWITCH(np, h_marginal, x, p, kind, N, ld, idx, mean, unc, plane);
-}
-int host_smooth(int np, const SmoothArgs& a) {
-  if (!smooth_args_ok(np, a)) return -1;
-  KF_HOST_NP_SWITCH(np, h_smooth, a);
-}
+int host_smooth(int np, const SmoothArgs& a) { return smooth_args_ok(np, a) ? host_pixels<OpSmooth>(np, a) : -1; }
 int host_innovation(int np, const InnovationArgs& a) {
   if (!innovation_args_ok(np, a)) return -1;
-  KF_HOST_NP_SWITCH(np, h_innovation, a);
+  return innovation_joint(a) ? host_pixels<OpInnovation<true>>(np, a) : host_pixels<OpInnovation<false>>(np, a);
 }
 int host_obs_order(const BandDesc* bands, const int32_t* grp, int nb, int G, int64_t N, int32_t* order, bool local) {
   if (G < 1 || G > 3) return -1;

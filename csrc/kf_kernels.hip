@@ -100,56 +100,32 @@ static void l_jacobi(const JacobiArgs& a, int grid, hipStream_t s) {
   else
     hipLaunchKernelGGL(jacobi_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
 }
-template <int NP>
-static void l_propagate(const PropArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL(propagate_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
-}
-template <int NP>
-static void l_invert(const float* src, float* dst, int64_t N, int64_t ld, uint8_t* st, int grid, hipStream_t s) {
-  hipLaunchKernelGGL(invert_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, src, dst, N, ld, st);
-}
-template <int NP>
-static void l_operator(const BandDesc* b, int band, const float* x, int64_t N, int64_t ld, float* h0, float* h,
-                       int64_t h_ld, uint8_t* ok, int grid, hipStream_t s) {
-  hipLaunchKernelGGL(operator_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, b, band, x, N, ld, h0, h, h_ld, ok);
-}
-template <int NP>
-static void l_hessian(const BandDesc* b, int nb, const float* x, float* a, int64_t N, int64_t ld, int grid,
-                      hipStream_t s) {
-  hipLaunchKernelGGL(hessian_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, b, nb, x, a, N, ld);
-}
-template <int NP>
-static void l_unpack(const float* x, const float* a, int64_t N, int64_t ld, const int64_t* idx, float* mean,
-                     float* unc, int64_t plane, int grid, hipStream_t s) {
-  hipLaunchKernelGGL(unpack_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, x, a, N, ld, idx, mean, unc, plane);
-}
-template <int NP>
-static void l_marginal(const float* x, const float* p, int kind, int64_t N, int64_t ld, const int64_t* idx,
-                       float* mean, float* unc, int64_t plane, int grid, hipStream_t s) {
-  hipLaunchKernelGGL(marginal_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, x, p, kind, N, ld, idx, mean, unc, plane);
-}
-template <int NP>
-static void l_smooth(const SmoothArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL(smooth_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
-}
-template <int NP>
-static void l_innovation(const InnovationArgs& a, int grid, hipStream_t s) {
-  if (innovation_joint(a))
-    hipLaunchKernelGGL(innovation_joint_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
-  else
-    hipLaunchKernelGGL(innovation_kernel<NP>, dim3(grid), dim3(BLOCK), 0, s, a);
-}
 
 // Grid cap for the per-pixel kernels (one f64 partial per workgroup).  The
 // default keeps grid-stride loops; raising it to >= N/256 gives one pixel per
 // thread so workgroups start and finish at different times and their memory
-// phases overlap other workgroups' compute.
+// phases overlap other workgroups' compute.  Every pixel_kernel launch takes it
+// (launch_np) -- propagate, invert, operator, gp_operator, hessian and unpack
+// honour the knob as marginal, smooth and innovation do -- so a test can make
+// every thread of any auxiliary pass walk the grid-stride loop.  The default is
+// KF_MAX_BLOCKS: no production launch is capped differently.
 static int g_max_blocks = KF_MAX_BLOCKS;
 void set_max_blocks(int n) { g_max_blocks = n > 0 ? n : KF_MAX_BLOCKS; }
 static int g_gp_unroll = 4;
 void set_gp_unroll(int n) { g_gp_unroll = n; }
 int get_max_blocks() { return g_max_blocks; }
 int dev_grid(int64_t N) { return grid_for(N, g_max_blocks); }
+
+// One auxiliary pass OP over a.N pixels (kf_device.h pixel_kernel).
+template <int NP, class OP>
+static void launch_np(const typename OP::Args& a, hipStream_t s) {
+  if (a.N > 0) hipLaunchKernelGGL((pixel_kernel<NP, OP>), dim3(dev_grid(a.N)), dim3(BLOCK), 0, s, a);
+}
+template <class OP>
+static hipError_t launch_pixels(int np, const typename OP::Args& a, hipStream_t s) {
+  const bool known = np_dispatch(np, [&](auto n) { launch_np<decltype(n)::value, OP>(a, s); });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
+}
 
 // ---------------------------------------------------------------------------
 // obs_order: a stable partition of 0..N-1 by observation class (obs_class:
@@ -653,72 +629,37 @@ std::vector<KernelPlan> dev_launch_table() {
   return out;
 }
 hipError_t dev_jacobi(int np, const JacobiArgs& a, int grid, hipStream_t s) {
-  KF_NP_SWITCH(np, l_jacobi, a, grid, s);
-  return hipGetLastError();
+  const bool known = np_dispatch(np, [&](auto n) { l_jacobi<decltype(n)::value>(a, grid, s); });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
 }
-hipError_t dev_propagate(int np, const PropArgs& a, hipStream_t s) {
-  KF_NP_SWITCH(np, l_propagate, a, grid_for(a.N, KF_MAX_BLOCKS), s);
-  return hipGetLastError();
+hipError_t dev_propagate(int np, const PropArgs& a, hipStream_t s) { return launch_pixels<OpPropagate>(np, a, s); }
+hipError_t dev_invert(int np, const InvertArgs& a, hipStream_t s) { return launch_pixels<OpInvert>(np, a, s); }
+hipError_t dev_operator(int np, const OperatorArgs& a, hipStream_t s) { return launch_pixels<OpOperator>(np, a, s); }
+hipError_t dev_hessian(int np, const HessianArgs& a, hipStream_t s) { return launch_pixels<OpHessian>(np, a, s); }
+hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s) { return launch_pixels<OpUnpack>(np, a, s); }
+hipError_t dev_marginal(int np, const RasterArgs& a, hipStream_t s) {
+  if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return hipErrorInvalidValue;
+  return launch_pixels<OpMarginal>(np, a, s);
 }
-hipError_t dev_invert(int np, const float* src, float* dst, int64_t N, int64_t ld, uint8_t* st, hipStream_t s) {
-  KF_NP_SWITCH(np, l_invert, src, dst, N, ld, st, grid_for(N, KF_MAX_BLOCKS), s);
-  return hipGetLastError();
+hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s) {
+  return smooth_args_ok(np, a) ? launch_pixels<OpSmooth>(np, a, s) : hipErrorInvalidValue;
 }
-hipError_t dev_operator(int np, const BandDesc* b, int band, const float* x, int64_t N, int64_t ld, float* h0,
-                        float* h, int64_t h_ld, uint8_t* ok, hipStream_t s) {
-  KF_NP_SWITCH(np, l_operator, b, band, x, N, ld, h0, h, h_ld, ok, grid_for(N, KF_MAX_BLOCKS), s);
-  return hipGetLastError();
+hipError_t dev_innovation(int np, const InnovationArgs& a, hipStream_t s) {
+  if (!innovation_args_ok(np, a)) return hipErrorInvalidValue;
+  return innovation_joint(a) ? launch_pixels<OpInnovation<true>>(np, a, s) : launch_pixels<OpInnovation<false>>(np, a, s);
 }
-hipError_t dev_gp_operator(int np, int d, const BandDesc* b, int nb, const float* x, int64_t N, int64_t ld,
-                           float* h0, float* h, int64_t ldh, hipStream_t s) {
-  const int g = grid_for(N, KF_MAX_BLOCKS);
+// the (np, d) pairs with a kernel: gp_operator_supported's list
+hipError_t dev_gp_operator(int np, int d, const GpOperatorArgs& a, hipStream_t s) {
   // record-stream unroll: 4 pairs by default, 2 selectable (set_gp_unroll) for A/B
-#define KF_GPOP(NP_, D_)                                                                                     \
-  if (np == NP_ && d == D_) {                                                                               \
-    if (g_gp_unroll == 2)                                                                                   \
-      hipLaunchKernelGGL((gp_operator_kernel<NP_, D_, 2>), dim3(g), dim3(BLOCK), 0, s, b, nb, x, N, ld, h0, \
-                         h, ldh);                                                                           \
-    else                                                                                                    \
-      hipLaunchKernelGGL((gp_operator_kernel<NP_, D_, 4>), dim3(g), dim3(BLOCK), 0, s, b, nb, x, N, ld, h0, \
-                         h, ldh);                                                                           \
-    return hipGetLastError();                                                                               \
+#define KF_GPOP(NP_, D_)                                           \
+  if (np == NP_ && d == D_) {                                      \
+    if (g_gp_unroll == 2) launch_np<NP_, OpGpOperator<D_, 2>>(a, s); \
+    else launch_np<NP_, OpGpOperator<D_, 4>>(a, s);                \
+    return hipGetLastError();                                      \
   }
   KF_GPOP(10, 10) KF_GPOP(10, 4) KF_GPOP(7, 7) KF_GPOP(7, 4) KF_GPOP(4, 4) KF_GPOP(3, 3) KF_GPOP(2, 2)
 #undef KF_GPOP
   return hipErrorInvalidValue;
-}
-
-hipError_t dev_hessian(int np, const BandDesc* b, int nb, const float* x, float* a, int64_t N, int64_t ld,
-                       hipStream_t s) {
-  KF_NP_SWITCH(np, l_hessian, b, nb, x, a, N, ld, grid_for(N, KF_MAX_BLOCKS), s);
-  return hipGetLastError();
-}
-hipError_t dev_unpack(int np, const float* x, const float* a, int64_t N, int64_t ld, const int64_t* idx,
-                      float* mean, float* unc, int64_t plane, hipStream_t s) {
-  KF_NP_SWITCH(np, l_unpack, x, a, N, ld, idx, mean, unc, plane, grid_for(N, KF_MAX_BLOCKS), s);
-  return hipGetLastError();
-}
-// grid capped by set_max_blocks (default KF_MAX_BLOCKS), so a test can make every
-// thread walk the grid-stride loop
-hipError_t dev_marginal(int np, const float* x, const float* p, int kind, int64_t N, int64_t ld, const int64_t* idx,
-                        float* mean, float* unc, int64_t plane, hipStream_t s) {
-  if (kind != MARG_PRECISION && kind != MARG_COVARIANCE) return hipErrorInvalidValue;
-  KF_NP_SWITCH(np, l_marginal, x, p, kind, N, ld, idx, mean, unc, plane, grid_for(N, g_max_blocks), s);
-  return hipGetLastError();
-}
-// grid capped by set_max_blocks, as dev_marginal
-hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s) {
-  if (!smooth_args_ok(np, a)) return hipErrorInvalidValue;
-  if (a.N == 0) return hipSuccess;
-  KF_NP_SWITCH(np, l_smooth, a, grid_for(a.N, g_max_blocks), s);
-  return hipGetLastError();
-}
-// grid capped by set_max_blocks, as dev_marginal
-hipError_t dev_innovation(int np, const InnovationArgs& a, hipStream_t s) {
-  if (!innovation_args_ok(np, a)) return hipErrorInvalidValue;
-  if (a.N == 0) return hipSuccess;
-  KF_NP_SWITCH(np, l_innovation, a, grid_for(a.N, g_max_blocks), s);
-  return hipGetLastError();
 }
 // Fixed-order f64 sum of a launch's norm partials: one workgroup (at most
 // KF_MAX_BLOCKS = 65536 entries, 512 KiB: a few microseconds).  No scratch

@@ -41,24 +41,18 @@ void launch_table_np7(std::vector<KernelPlan>& out);
 void launch_table_np10(std::vector<KernelPlan>& out);
 void launch_table_gain_np10(std::vector<KernelPlan>& out);
 hipError_t dev_jacobi(int np, const JacobiArgs& a, int grid, hipStream_t s);
+// The auxiliary per-pixel passes (kf_core.h KF_PIXEL_OP): one pixel_kernel launch over a.N pixels each,
+// the grid capped by set_max_blocks
 hipError_t dev_propagate(int np, const PropArgs& a, hipStream_t s);
-hipError_t dev_invert(int np, const float* src, float* dst, int64_t N, int64_t ld, uint8_t* st, hipStream_t s);
-hipError_t dev_operator(int np, const BandDesc* b, int band, const float* x, int64_t N, int64_t ld, float* h0,
-                        float* h, int64_t h_ld, uint8_t* ok, hipStream_t s);
-hipError_t dev_hessian(int np, const BandDesc* b, int nb, const float* x, float* a, int64_t N, int64_t ld,
-                       hipStream_t s);
-hipError_t dev_gp_operator(int np, int d, const BandDesc* b, int nb, const float* x, int64_t N, int64_t ld,
-                           float* h0, float* h, int64_t ldh, hipStream_t s);
+hipError_t dev_invert(int np, const InvertArgs& a, hipStream_t s);
+hipError_t dev_operator(int np, const OperatorArgs& a, hipStream_t s);
+hipError_t dev_hessian(int np, const HessianArgs& a, hipStream_t s);
+hipError_t dev_gp_operator(int np, int d, const GpOperatorArgs& a, hipStream_t s);
 bool gp_operator_supported(int np, int d);
-hipError_t dev_unpack(int np, const float* x, const float* a, int64_t N, int64_t ld, const int64_t* idx,
-                      float* mean, float* unc, int64_t plane, hipStream_t s);
-// kind: MARG_PRECISION / MARG_COVARIANCE (kf_core.h pixel_marginal)
-hipError_t dev_marginal(int np, const float* x, const float* p, int kind, int64_t N, int64_t ld, const int64_t* idx,
-                        float* mean, float* unc, int64_t plane, hipStream_t s);
-// one backward step of the RTS smoother (kf_core.h pixel_smooth)
-hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s);
-// innovation statistics and the chi-square gate (kf_core.h pixel_innovation)
-hipError_t dev_innovation(int np, const InnovationArgs& a, hipStream_t s);
+hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s);
+hipError_t dev_marginal(int np, const RasterArgs& a, hipStream_t s);       // a.kind: MARG_*
+hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s);         // one backward step of the RTS smoother
+hipError_t dev_innovation(int np, const InnovationArgs& a, hipStream_t s); // statistics and the chi-square gate
 hipError_t dev_reduce(const double* partials, int n, double* out, hipStream_t s);
 hipError_t dev_gather(int elem_bytes, const void* src, const int64_t* idx, void* dst, int64_t n, int rows,
                       int64_t src_ld, int64_t dst_ld, hipStream_t s);
@@ -85,21 +79,17 @@ int64_t host_chunk_compact(const ChunkCompactArgs& a);
 
 // Host runner: the same per-pixel code over OpenMP; the block partition
 // mirrors the device grid-stride mapping so partials have the same meaning.
-bool host_supported(int np);
+inline bool host_supported(int np) { return plan_np(np); }
 int host_analysis(int np, const AnalysisArgs& a, int grid);
 int host_gain(int np, const GainArgs& a, int grid);
 int host_jacobi(int np, const JacobiArgs& a, int grid);
 int host_propagate(int np, const PropArgs& a);
-int host_invert(int np, const float* src, float* dst, int64_t N, int64_t ld, uint8_t* st);
-int host_operator(int np, const BandDesc* b, int band, const float* x, int64_t N, int64_t ld, float* h0, float* h,
-                  int64_t h_ld, uint8_t* ok);
-int host_hessian(int np, const BandDesc* b, int nb, const float* x, float* a, int64_t N, int64_t ld);
-int host_gp_operator(int np, const BandDesc* b, int nb, const float* x, int64_t N, int64_t ld, float* h0, float* h,
-                     int64_t ldh);
-int host_unpack(int np, const float* x, const float* a, int64_t N, int64_t ld, const int64_t* idx, float* mean,
-                float* unc, int64_t plane);
-int host_marginal(int np, const float* x, const float* p, int kind, int64_t N, int64_t ld, const int64_t* idx,
-                  float* mean, float* unc, int64_t plane);
+int host_invert(int np, const InvertArgs& a);
+int host_operator(int np, const OperatorArgs& a);
+int host_hessian(int np, const HessianArgs& a);
+int host_gp_operator(int np, const GpOperatorArgs& a);
+int host_unpack(int np, const RasterArgs& a);
+int host_marginal(int np, const RasterArgs& a);
 int host_smooth(int np, const SmoothArgs& a);
 int host_innovation(int np, const InnovationArgs& a);
 // obs_order chunk: pixels per scatter workgroup; local = 1 partitions each

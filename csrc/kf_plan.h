@@ -6,6 +6,7 @@
 // line here and one table line; tests/test_launch_plan.py pins every launch.
 #pragma once
 #include <string>
+#include <type_traits>
 #include "kf_core.h"
 
 namespace kf {
@@ -117,8 +118,21 @@ inline std::string plan_name(const KernelPlan& p) {
   }
 }
 
-// State sizes with compiled kernels (KF_NP_SWITCH, kf_device.h).
-constexpr bool plan_np(int np) { return (np >= 1 && np <= 4) || np == 7 || np == 10; }
+// The state sizes with compiled kernels, listed once for both runners:
+// f(std::integral_constant<int, NP>) for np's size -> true, false for any other.
+template <class F>
+constexpr bool np_dispatch(int np, F&& f) {
+  switch (np) {
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 3: f(std::integral_constant<int, 3>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 7: f(std::integral_constant<int, 7>{}); return true;
+    case 10: f(std::integral_constant<int, 10>{}); return true;
+    default: return false;
+  }
+}
+constexpr bool plan_np(int np) { return np_dispatch(np, [](auto) {}); }
 
 // Interleaved exponent MFMAs (gpm_chunk IL: both column blocks' exponent
 // MFMAs before the first block's exponentials) by default where the second

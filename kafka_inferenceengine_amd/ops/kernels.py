@@ -1534,21 +1534,33 @@ class TileDecoder:
         return out, status[:n]
 
 
-def unpack(n_params, x, a, mean=None, unc=None, idx=None, N=None):
-    """Scatter mean and 1/sqrt(diag(P^-1)) onto raster planes [n_p, H*W]."""
+def _check_rasters(n_params, x, p, mean, unc, idx, N, pname) -> tuple[int, int]:
+    """The raster scatter of unpack() and marginal(): x [n_p, ld], the packed
+    rows ``p`` [ntri, ld] (read only for ``unc``), planes mean / unc [n_p, plane]
+    and the optional index map -> (N, plane)."""
     check_np(n_params)
     N = int(x.shape[1] if N is None else N)
     _check_soa(x, n_params, N, "x")
     if unc is not None:
-        _check_soa(a, ntri(n_params), N, "a", device=x.device)
+        _check_soa(p, ntri(n_params), N, pname, device=x.device)
+        if p.shape[1] != x.shape[1]:
+            raise ValueError(f"x and {pname} must share their row stride")
     plane = (mean if mean is not None else unc).shape[1]
     for t in (mean, unc):
         if t is not None:
             _check_soa(t, n_params, 0, "out", device=x.device)
+            if t.shape[1] != plane:
+                raise ValueError("mean and unc planes differ in size")
     if idx is not None:
         _check_vec(idx, N, "idx", torch.int64, x.device)
     elif plane < N:
         raise ValueError("output plane smaller than N without an index map")
+    return N, plane
+
+
+def unpack(n_params, x, a, mean=None, unc=None, idx=None, N=None):
+    """Scatter mean and 1/sqrt(diag(P^-1)) onto raster planes [n_p, H*W]."""
+    N, plane = _check_rasters(n_params, x, a, mean, unc, idx, N, "a")
     ext().unpack(n_params, _ptr(x), _ptr(a), N, x.shape[1], _ptr(idx), _ptr(mean), _ptr(unc), plane, _dev(x),
                  _stream(x))
 
@@ -1561,25 +1573,9 @@ def marginal(n_params, x, p, mean=None, unc=None, idx=None, N=None, kind="precis
     [n_p, H*W].  ``p`` holds the packed rows of P^-1 (``kind="precision"``:
     factorised per pixel; a block that is not SPD gives NaN in all its planes)
     or of P itself (``kind="covariance"``: the diagonal rows are read)."""
-    check_np(n_params)
     if kind not in MARGINAL_KINDS:
         raise ValueError("kind must be 'precision' or 'covariance'")
-    N = int(x.shape[1] if N is None else N)
-    _check_soa(x, n_params, N, "x")
-    if unc is not None:
-        _check_soa(p, ntri(n_params), N, "p", device=x.device)
-        if p.shape[1] != x.shape[1]:
-            raise ValueError("x and p must share their row stride")
-    plane = (mean if mean is not None else unc).shape[1]
-    for t in (mean, unc):
-        if t is not None:
-            _check_soa(t, n_params, 0, "out", device=x.device)
-            if t.shape[1] != plane:
-                raise ValueError("mean and unc planes differ in size")
-    if idx is not None:
-        _check_vec(idx, N, "idx", torch.int64, x.device)
-    elif plane < N:
-        raise ValueError("output plane smaller than N without an index map")
+    N, plane = _check_rasters(n_params, x, p, mean, unc, idx, N, "p")
     e = ext()
     e.marginal(n_params, _ptr(x), _ptr(p), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION, N,
                x.shape[1], _ptr(idx), _ptr(mean), _ptr(unc), plane, _dev(x), _stream(x))

@@ -1,6 +1,6 @@
 // sanitize_evidence.cpp — AddressSanitizer / UBSan driver for the joint
 // innovation statistic on the host runner (kf_core.h pixel_innovation<NP, true>,
-// shared verbatim with innovation_joint_kernel).  Every buffer is exactly sized,
+// shared verbatim with the device kernel).  Every buffer is exactly sized,
 // so an out-of-bounds index of the n x n accumulator, delta or the band walk
 // faults under -fsanitize=address.  Built and run by tests/test_sanitize_evidence.py:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer

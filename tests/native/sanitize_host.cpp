@@ -154,7 +154,9 @@ int main() {
 
   // K1g gain form (covariance input = inverse of the precision above)
   std::vector<float> cov((size_t)NT * N), po((size_t)NT * N);
-  check(host_invert(NP, Pf.data(), cov.data(), N, N, status.data()) == 0, "host_invert rc");
+  InvertArgs inv{};
+  inv.N = N; inv.ld = N; inv.src = Pf.data(); inv.dst = cov.data(); inv.status = status.data();
+  check(host_invert(NP, inv) == 0, "host_invert rc");
   GainArgs g;
   std::memset(&g, 0, sizeof(g));
   g.N = N; g.ld = N; g.n_bands = 2; g.joseph = 1; g.bands = bands;
@@ -165,10 +167,14 @@ int main() {
 
   // K2 split operator (7 params, 4 inputs) and K6 Hessian correction
   std::vector<float> h0((size_t)2 * N), hh((size_t)2 * NP * N);
-  check(host_gp_operator(NP, bands, 2, x.data(), N, N, h0.data(), hh.data(), N) == 0, "host_gp_operator rc");
+  GpOperatorArgs go{};
+  go.N = N; go.ld = N; go.bands = bands; go.nb = 2; go.x = x.data(); go.h0 = h0.data(); go.h = hh.data(); go.ldh = N;
+  check(host_gp_operator(NP, go) == 0, "host_gp_operator rc");
   check(all_finite(h0) && all_finite(hh), "gp operator finite");
   std::vector<float> ah = ao;
-  check(host_hessian(NP, bands, 2, x.data(), ah.data(), N, N) == 0, "host_hessian rc");
+  HessianArgs he{};
+  he.N = N; he.ld = N; he.bands = bands; he.n_bands = 2; he.x = x.data(); he.a = ah.data();
+  check(host_hessian(NP, he) == 0, "host_hessian rc");
 
   // K9 Jacobi sweep on a 40 x 25 raster (4-neighbour table, no halo)
   const int H = 40, W = 25;
@@ -193,8 +199,10 @@ int main() {
   std::vector<int64_t> idx((size_t)N);
   for (int64_t p = 0; p < N; ++p) idx[p] = p + (p > 500 ? 17 : 0);
   std::vector<float> mean((size_t)NP * plane), unc((size_t)NP * plane);
-  check(host_unpack(NP, x.data(), Pf.data(), N, N, idx.data(), mean.data(), unc.data(), plane) == 0,
-        "host_unpack rc");
+  RasterArgs un{};
+  un.N = N; un.ld = N; un.x = x.data(); un.p = Pf.data(); un.idx = idx.data(); un.mean = mean.data();
+  un.unc = unc.data(); un.plane = plane;
+  check(host_unpack(NP, un) == 0, "host_unpack rc");
 
   // K7 LUT nearest
   const int M = 33;

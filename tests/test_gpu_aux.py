@@ -1,4 +1,5 @@
-"""The auxiliary kernels -- K7 (nearest LUT row), propagate, invert, the K6
+"""The auxiliary kernels -- K7 (nearest LUT row), propagate, invert, the
+standalone operator evaluation, the K2 split path (gp_operator), the K6
 Hessian correction, unpack and gather -- at every compiled state size, against
 float64 NumPy models of the same operation (never the kernels' own source),
 with a leading dimension larger than N, a sentinel in every padding column and
@@ -12,12 +13,18 @@ Tolerances are the project's existing ones: ``x_err`` / ``a_err`` of
 test_oracles.py with x 1e-5 (1e-4 with the blend) and P 1e-5 (1e-4 for the
 exact information filter); invert ``rtol=1e-4, atol=1e-6``; the Hessian 2e-3
 of the largest entry of the correction; unpack's mean exact and its
-uncertainty ``rtol=1e-6``; gather and the K7 index exact.
+uncertainty ``rtol=1e-6``; gather and the K7 index exact; the operators those of
+tests/test_kernels.py:191-225 (precomputed rows exact, linear ``atol=1e-5``, SAR
+``rtol=2e-5`` and for the gradient ``rtol=2e-4, atol=1e-7``, GP ``atol=5e-6``
+and for the gradient ``5e-5``).
 
 Worst measured errors over all modes, blends and N (the tests print them).
 propagate: x without / with the blend, P of every mode but the exact filter /
 of the exact filter.  invert: the largest |err| / (atol + rtol |ref|), 1 being
 the bound.  hessian: of the largest entry.  unpack: relative, uncertainty.
+operator_eval and gp_operator: the largest |err| / (atol + rtol |ref|) of the
+value / of the gradient, 1 being the bound; the same figures, digit for digit,
+with the kernels as they were before pixel_kernel replaced them.
 
     kernel           n   host runner                       MI355X
     ---------------  --  --------------------------------  --------------------------------
@@ -44,6 +51,29 @@ the bound.  hessian: of the largest entry.  unpack: relative, uncertainty.
     unpack           4   8.4e-8                            9.3e-8
     unpack           7   8.5e-8                            8.2e-8
     unpack           10  8.9e-8                            8.9e-8
+    operator linear  1   1.5e-3 / 0                        1.5e-3 / 0
+    operator linear  2   2.5e-3 / 0                        2.5e-3 / 0
+    operator linear  3   3.0e-3 / 0                        3.0e-3 / 0
+    operator linear  4   3.7e-3 / 0                        3.7e-3 / 0
+    operator linear  7   7.2e-3 / 0                        7.2e-3 / 0
+    operator linear  10  5.6e-3 / 0                        5.6e-3 / 0
+    operator sar     2   1.8e-2 / 7.6e-3                   1.8e-2 / 1.0e-2
+    operator sar     3   2.1e-2 / 1.1e-2                   1.8e-2 / 1.1e-2
+    operator sar     4   1.8e-2 / 1.5e-2                   1.8e-2 / 1.5e-2
+    operator sar     7   1.8e-2 / 8.5e-3                   1.9e-2 / 8.5e-3
+    operator sar     10  2.0e-2 / 2.2e-2                   1.8e-2 / 2.2e-2
+    operator gp      1   1.3e-1 / 4.0e-2                   1.3e-1 / 3.9e-2
+    operator gp      2   1.9e-1 / 4.2e-2                   2.0e-1 / 3.9e-2
+    operator gp      3   1.3e-1 / 3.0e-2                   1.3e-1 / 2.9e-2
+    operator gp      4   5.4e-2 / 9.2e-3                   5.4e-2 / 9.9e-3
+    operator gp      7   2.0e-2 / 3.5e-3                   2.0e-2 / 3.5e-3
+    operator gp      10  1.4e-2 / 2.0e-3                   1.4e-2 / 2.1e-3
+    gp_operator 2,2  2   2.6e-1 / 4.1e-2                   2.7e-1 / 4.1e-2
+    gp_operator 3,3  3   1.3e-1 / 4.2e-2                   1.3e-1 / 4.2e-2
+    gp_operator 4,4  4   4.6e-2 / 1.1e-2                   4.6e-2 / 1.1e-2
+    gp_operator 7,7  7   1.9e-2 / 3.1e-3                   1.9e-2 / 3.1e-3
+    gp_operator 10,10 10 1.4e-2 / 2.4e-3                   1.4e-2 / 2.4e-3
+    gp_operator 7,4  7   1.5e-1 / 3.2e-2                   1.5e-1 / 3.2e-2
 
 The device's hardware reciprocal and reciprocal square root (kf_core.h kf_rcp,
 kf_rsqrt) leave it inside every project tolerance at every state size; no
@@ -212,6 +242,117 @@ def test_invert_every_state_size_vs_float64(dev, n):
         assert bool((st[N:] == 0xA5).all()) and pad_untouched(dst2, N)
         good = torch.from_numpy(~c["bad"])
         assert torch.equal(dst2[:, :N][:, good], dst[:, :N][:, good])
+
+
+# ------------------------------------------------------------------ operator_eval
+OPERATOR_BANDS = (("precomp", K.OBS_F32), ("precomp", K.OBS_DN16), ("linear", K.OBS_F32), ("sar", K.OBS_F32),
+                  ("gp", K.OBS_F32))
+# (value, gradient) bounds as allclose keywords, tests/test_kernels.py:191-225; precomputed rows are copied
+OPERATOR_TOL = {"linear": (dict(rtol=0, atol=1e-5), dict(rtol=0, atol=1e-5)),
+                "sar": (dict(rtol=2e-5, atol=1e-8), dict(rtol=2e-4, atol=1e-7)),
+                "gp": (dict(rtol=0, atol=5e-6), dict(rtol=0, atol=5e-5))}
+# lanes of the first block whose precomputed rows carry a planted NaN / Inf (kernel_cases.nongp_case)
+PLANTED = ((45, 47, 48), (46, 47))
+
+
+def bound_use(got, ref, rtol, atol):
+    """The largest |got - ref| / (atol + rtol |ref|): 1 is allclose's bound."""
+    return float(np.max(np.abs(got - ref) / (atol + rtol * np.abs(ref)))) if got.size else 0.0
+
+
+@pytest.mark.parametrize("n", C.AUX_NP)
+def test_operator_eval_every_state_size(dev, n):
+    """One band at a time over precomputed (two bands, NaN / Inf planted in
+    their rows), linear, SAR (n >= 2) and GP (small_gp(n)) operators: H0, the
+    Jacobian rows and ``ok`` against the case's float64 ``evals``; ``ok`` is 0 on
+    exactly the planted pixels; a launch without ``h`` and ``ok`` gives the same
+    H0 bit for bit; every padding column keeps its sentinel."""
+    bands = tuple(b for b in OPERATOR_BANDS if n >= 2 or b[0] != "sar")
+    worst = {}
+    for i in range(len(C.AUX_N)):
+        N, pad = C.aux_shape(C.AUX_NP.index(n) + i)
+        ld = N + pad
+        c = C.nongp_case(n, N, bands)
+        tab, _ = C.nongp_table(c, dev, pad)
+        x = C.padded(c["x0"].T, ld, dev, fill=-777.0)
+        for b, (op, _) in enumerate(bands):
+            H, hr = c["evals"][b][:2]
+            h0, h = C.sentinel(1, ld, dev)[0], C.sentinel(n, ld + 7, dev)
+            ok = torch.full((ld,), 0xA5, dtype=torch.uint8, device=dev)
+            K.operator_eval(n, tab, b, x, h0, h, ok, N=N)
+            h0b = C.sentinel(1, ld, dev)[0]
+            K.operator_eval(n, tab, b, x, h0b, N=N)
+            assert torch.equal(h0b.view(torch.int32), h0.view(torch.int32)), (op, N)
+            h0, h, ok = h0.cpu(), h.cpu(), ok.cpu()
+            assert pad_untouched(h0, N) and pad_untouched(h, N) and bool((ok[N:] == 0xA5).all()), (op, N, pad)
+            bad = ~(np.isfinite(H) & np.isfinite(hr).all(1))
+            assert np.array_equal(ok[:N].numpy(), np.where(bad, 0, 1).astype(np.uint8)), (op, N)
+            want = [p for p in PLANTED[b] if p < N] if op == "precomp" else []
+            assert np.flatnonzero(bad).tolist() == want, (op, N)
+            g0, g = h0[:N].numpy(), h[:, :N].numpy().T
+            if op == "precomp":
+                assert np.array_equal(g0, H.astype(np.float32), equal_nan=True), (op, N)
+                assert np.array_equal(g, hr.astype(np.float32), equal_nan=True), (op, N)
+                continue
+            tv, tg = OPERATOR_TOL[op]
+            e = (bound_use(g0.astype(np.float64), H, **tv), bound_use(g.astype(np.float64), hr, **tg))
+            worst[op] = tuple(max(a, b_) for a, b_ in zip(worst.get(op, (0.0, 0.0)), e))
+            assert np.allclose(g0, H, **tv), (op, N, e)
+            assert np.allclose(g, hr, **tg), (op, N, e)
+    print(f"operator_eval n={n} on {dev}: worst error / bound (value, gradient) " +
+          ", ".join(f"{op} {v:.2e} {g:.2e}" for op, (v, g) in worst.items()))
+
+
+# ------------------------------------------------------------------ gp_operator
+GP_OPERATOR_SHAPES = ((2, 2), (3, 3), (4, 4), (7, 7), (10, 10), (7, 4))
+_TIP_CASES: dict = {}
+
+
+def gp_operator_case(n, d, N):
+    """-> (x0 [N, n] float32-valued, evals [(H0, h, y, w)] in float64, table builder):
+    two small_gp(n) bands in two encodings, or the two JRC-TIP bands (d = 4)."""
+    if d == n:
+        c = C.nongp_case(n, N, (("gp", K.OBS_F32), ("gp", K.OBS_DN16)))
+        return c["x0"], c["evals"], lambda dev, pad: C.nongp_table(c, dev, pad)[0]
+    if N not in _TIP_CASES:
+        prob = C.tip_problem(N=N, seed=11, dn16=True, mask_frac=0.3)
+        x = C.f32(prob["x"])
+        _TIP_CASES[N] = (prob, x, C.oracle_bands(prob, x))
+    prob, x, evals = _TIP_CASES[N]
+    return x, evals, lambda dev, pad: C.table(prob, dev)
+
+
+@pytest.mark.parametrize("n,d", GP_OPERATOR_SHAPES)
+def test_gp_operator_shapes_vs_float64(dev, n, d):
+    """K2 split path, two bands per launch, each masked on a subset of the
+    pixels: d = n with small_gp(n) bands and (7, 4) with the two JRC-TIP bands.
+    Observed pixels against the float64 emulator (value 5e-6, gradient 5e-5),
+    masked pixels exact zeros in h0 and all n rows, padding untouched.  (10, 4)
+    keeps the coverage it has through the engine's split-path test
+    (tests/test_engine.py test_split_gp_operator_path_equals_fused)."""
+    worst = [0.0, 0.0]
+    for i in range(len(C.AUX_N)):
+        N, pad = C.aux_shape(GP_OPERATOR_SHAPES.index((n, d)) + i)
+        ld, ldh = N + pad, N + pad + 3
+        x0, evals, table = gp_operator_case(n, d, N)
+        tab = table(dev, pad)
+        h0, h = C.sentinel(2, ldh, dev), C.sentinel(2 * n, ldh, dev)
+        K.gp_operator(n, tab, C.padded(x0.T, ld, dev, fill=-777.0), h0, h, N=N, d=d)
+        h0, h = h0.cpu(), h.cpu()
+        assert pad_untouched(h0, N) and pad_untouched(h, N), (N, pad)
+        n_masked = 0
+        for b, (H, hr, _, w) in enumerate(evals):
+            on = w > 0
+            n_masked += int((~on).sum())
+            g0, g = h0[b, :N].numpy(), h[b * n:(b + 1) * n, :N].numpy().T
+            assert not g0[~on].any() and not g[~on].any(), (b, N)
+            assert not np.signbit(g0[~on]).any() and not np.signbit(g[~on]).any(), (b, N)
+            e = (bound_use(g0[on].astype(np.float64), H[on], 0, 5e-6), bound_use(g[on].astype(np.float64), hr[on], 0, 5e-5))
+            worst = [max(a, b_) for a, b_ in zip(worst, e)]
+            assert np.allclose(g0[on], H[on], rtol=0, atol=5e-6), (b, N, e)
+            assert np.allclose(g[on], hr[on], rtol=0, atol=5e-5), (b, N, e)
+        assert N < 63 or n_masked > 0, "the case must mask some pixels"
+    print(f"gp_operator n={n} d={d} on {dev}: worst error / bound value {worst[0]:.2e} gradient {worst[1]:.2e}")
 
 
 # ------------------------------------------------------------------ hessian
