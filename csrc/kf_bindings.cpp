@@ -448,6 +448,38 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     if (device) check_hip(dev_marginal(np, a, (hipStream_t)stream), "marginal");
     else check_host(host_marginal(np, a), "marginal");
   });
+  // physical-unit product planes with a credible interval and the QA byte (kf_core.h pixel_product):
+  // one transform (kind, scale, offset, lo, hi) per parameter, `sel` the mask of the parameters with a product
+  m.attr("PRODUCT_IDENTITY") = PRODUCT_IDENTITY;
+  m.attr("PRODUCT_LINEAR") = PRODUCT_LINEAR;
+  m.attr("PRODUCT_NEGLOG") = PRODUCT_NEGLOG;
+  m.def("product", [](int np, uintptr_t x, uintptr_t p, int kind, int64_t N, int64_t ld, uintptr_t idx,
+                      uintptr_t status, uintptr_t nobs, uintptr_t nrej, uintptr_t phys, uintptr_t qa, int64_t plane,
+                      uint32_t sel, float z, const std::vector<int>& kinds, const std::vector<float>& scale,
+                      const std::vector<float>& offset, const std::vector<float>& lo, const std::vector<float>& hi,
+                      bool device, uintptr_t stream) {
+    if (np < 1 || np > MAX_D || (int)kinds.size() != np || (int)scale.size() != np || (int)offset.size() != np ||
+        (int)lo.size() != np || (int)hi.size() != np)
+      throw std::invalid_argument("product: one transform entry per parameter");
+    ProductArgs a{};
+    a.N = N;
+    a.ld = ld;
+    a.x = P<const float>(x);
+    a.p = P<const float>(p);
+    a.kind = kind;
+    a.sel = sel;
+    a.idx = P<const int64_t>(idx);
+    a.status = P<const uint8_t>(status);
+    a.nobs = P<const uint8_t>(nobs);
+    a.nrej = P<const uint8_t>(nrej);
+    a.phys = P<float>(phys);
+    a.qa = P<uint8_t>(qa);
+    a.plane = plane;
+    a.z = z;
+    for (int j = 0; j < np; ++j) a.xf[j] = ProductTransform{kinds[j], scale[j], offset[j], lo[j], hi[j]};
+    if (device) check_hip(dev_product(np, a, (hipStream_t)stream), "product");
+    else check_host(host_product(np, a), "product");
+  });
   // RTS smoother, one backward step: filtered (x_a, p_a of `kind`) and the next step's smoothed
   // (x_next, covariance p_next) -> smoothed (x_out, covariance p_out), status 1 where a pixel fell back
   m.def("smooth", [](int np, uintptr_t x_a, uintptr_t p_a, int kind, uintptr_t x_next, uintptr_t p_next,

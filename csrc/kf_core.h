@@ -859,6 +859,141 @@ KF_HD void pixel_marginal(const RasterArgs& a, int64_t p) {
 }
 KF_PIXEL_OP(OpMarginal, RasterArgs, pixel_marginal);
 
+// Physical-unit product of pixel p: the stored state is in the filter's
+// transformed space (TeLAI = exp(-LAI / 2), ...); each selected parameter j is
+// carried back through its monotone transform T_j, with the credible interval
+// that is exact for a monotone transform of a Gaussian marginal: the transform
+// of the ends x_j -+ z sigma_j, sigma_j the marginal std (pixel_marginal's:
+// chol_packed + chol_inv_diag on precision rows, the diagonal of covariance
+// rows).  Every argument is clamped to [lo, hi] (bounds in transformed space)
+// first, so a product with finite bounds is finite.
+//   PRODUCT_IDENTITY: T(u) = u      PRODUCT_LINEAR: T(u) = scale u + offset
+//   PRODUCT_NEGLOG:   T(u) = -scale ln u (0 < lo <= hi < inf, checked by the host)
+// phys holds 3 n_sel planes, n_sel the number of bits of `sel`: plane
+// g n_sel + s of group g (0 median, 1 lower, 2 upper end) and selected
+// parameter s (ascending j).  The ends of a parameter are NaN where its sigma
+// is not available (pixel_marginal's rule: the whole pixel for a precision
+// block that is not SPD or not finite, the one parameter for a covariance
+// diagonal entry that is not finite and positive) or x_j is not finite; the
+// median is T(clamp(x_j)) regardless (NaN for a NaN x_j).
+// qa (optional, one byte per pixel; status / nobs / nrej optional, a null
+// pointer leaves its bits clear):
+//   bit 0  no observation assimilated: status has ST_NO_OBS, or every
+//          observation counted by the innovation check was rejected
+//          (nobs > 0 and nrej >= nobs)
+//   bit 1  the analysis fell back: ST_FALLBACK | ST_NONSPD | ST_NONFINITE | ST_BAD_OP
+//   bit 2  ST_OUT_OF_DOMAIN
+//   bit 3  nrej > 0
+//   bit 4  some selected parameter's interval is NaN (the rule above); with no
+//          parameter selected: the precision block is not SPD
+//   bit 5  some selected x_j strictly outside [lo, hi] (the median is clamped)
+//   bit 6  some interval end strictly outside [lo, hi] (clamped)
+//   bit 7  0
+constexpr int PRODUCT_IDENTITY = 0, PRODUCT_LINEAR = 1, PRODUCT_NEGLOG = 2;
+constexpr int QA_NO_OBS = 1, QA_FALLBACK = 2, QA_OUT_OF_DOMAIN = 4, QA_REJECTED = 8, QA_NO_INTERVAL = 16,
+              QA_MEDIAN_CLAMPED = 32, QA_END_CLAMPED = 64;
+struct ProductTransform {
+  int32_t kind;          // PRODUCT_*
+  float scale, offset;
+  float lo, hi;          // clamp of the argument (transformed space); -inf / +inf: none
+};
+struct ProductArgs {
+  int64_t N, ld;
+  const float* x;        // [NP][ld]
+  const float* p;        // [NT][ld] packed rows of `kind`
+  int32_t kind;          // MARG_PRECISION / MARG_COVARIANCE
+  uint32_t sel;          // bit j: parameter j has a product (xf[j])
+  const int64_t* idx;    // [N] raster cell of each pixel, or null
+  const uint8_t* status; // [N] ST_* of the timestep, or null
+  const uint8_t* nobs;   // [N] observations counted by the innovation check, or null
+  const uint8_t* nrej;   // [N] ... rejected by its gate, or null
+  float* phys;           // [3 n_sel][plane], or null when sel == 0
+  uint8_t* qa;           // [plane] or null
+  int64_t plane;
+  float z;               // Phi^-1((1 + level) / 2)
+  ProductTransform xf[MAX_D];
+};
+inline bool product_args_ok(int np, const ProductArgs& a) {
+  if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return false;
+  if (np < 1 || np > MAX_D || a.N < 0 || a.N > a.ld || (np < 32 && (a.sel >> np))) return false;
+  if (!a.x || !a.p || (a.sel && !a.phys) || (!a.phys && !a.qa) || !(a.z > 0.f) || !finitef(a.z)) return false;
+  if (!a.idx && a.plane < a.N) return false;
+  for (int j = 0; j < np; ++j) {
+    if (!((a.sel >> j) & 1u)) continue;
+    const ProductTransform& t = a.xf[j];
+    if (t.kind != PRODUCT_IDENTITY && t.kind != PRODUCT_LINEAR && t.kind != PRODUCT_NEGLOG) return false;
+    if (!(t.lo <= t.hi) || !finitef(t.scale) || !finitef(t.offset)) return false;
+    if (t.kind == PRODUCT_NEGLOG && !(t.lo > 0.f && finitef(t.hi))) return false;
+  }
+  return true;
+}
+
+// NaN stays NaN (fminf / fmaxf would turn it into a bound)
+KF_HD float product_clamp(float u, float lo, float hi) { return u < lo ? lo : (u > hi ? hi : u); }
+// kind is wave-uniform: it depends on the parameter only.  Plain logf: near
+// u = 1 the result goes to 0 and the fast intrinsic's absolute error does not.
+KF_HD float product_apply(const ProductTransform& t, float u) {
+  if (t.kind == PRODUCT_NEGLOG) return -t.scale * logf(u);
+  if (t.kind == PRODUCT_LINEAR) return fmaf(t.scale, u, t.offset);
+  return u;
+}
+
+template <int NP>
+KF_HD void pixel_product(const ProductArgs& a, int64_t p) {
+  constexpr int NT = ntri(NP);
+  KF_DCHECK(p >= 0 && p < a.N && a.N <= a.ld);
+  const float *x = a.x, *p_in = a.p;
+  const int64_t ld = a.ld, plane = a.plane;
+  const uint32_t sel = a.sel;
+  const float z = a.z;
+  const int64_t r = a.idx ? a.idx[p] : p;
+  KF_DCHECK(r >= 0 && r < plane);
+  float d[NP];
+  bool ok = true;
+  if (a.kind == MARG_COVARIANCE) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) d[j] = p_in[tri(NP, j, j) * ld + p];
+  } else {
+    float U[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) U[t] = p_in[t * ld + p];
+    ok = chol_packed<NP>(U);
+    chol_inv_diag<NP>(U, d);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) ok = ok && (d[j] > 0.f) && finitef(d[j]);
+  }
+  const int n_sel = __builtin_popcount(sel);
+  uint32_t q = (sel == 0u && !ok) ? (uint32_t)QA_NO_INTERVAL : 0u;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    if (!((sel >> j) & 1u)) continue;
+    const ProductTransform t = a.xf[j];
+    const int s = __builtin_popcount(sel & ((1u << j) - 1u));
+    const float xj = x[j * ld + p];
+    const bool have = ok && (d[j] > 0.f) && finitef(d[j]) && finitef(xj);
+    const float sd = sqrtf(have ? d[j] : 1.f);
+    const float um = fmaf(-z, sd, xj), up = fmaf(z, sd, xj);
+    const float fm = product_apply(t, product_clamp(um, t.lo, t.hi));
+    const float fp = product_apply(t, product_clamp(up, t.lo, t.hi));
+    const float nan = __builtin_nanf("");
+    a.phys[(int64_t)s * plane + r] = product_apply(t, product_clamp(xj, t.lo, t.hi));
+    a.phys[(int64_t)(n_sel + s) * plane + r] = have ? fminf(fm, fp) : nan;
+    a.phys[(int64_t)(2 * n_sel + s) * plane + r] = have ? fmaxf(fm, fp) : nan;
+    if (!have) q |= QA_NO_INTERVAL;
+    if (xj < t.lo || xj > t.hi) q |= QA_MEDIAN_CLAMPED;
+    if (have && (um < t.lo || um > t.hi || up < t.lo || up > t.hi)) q |= QA_END_CLAMPED;
+  }
+  if (!a.qa) return;
+  const uint32_t st = a.status ? a.status[p] : 0u;
+  const uint32_t no = a.nobs ? a.nobs[p] : 0u, nr = a.nrej ? a.nrej[p] : 0u;
+  if ((st & ST_NO_OBS) || (no > 0u && nr >= no)) q |= QA_NO_OBS;
+  if (st & (ST_FALLBACK | ST_NONSPD | ST_NONFINITE | ST_BAD_OP)) q |= QA_FALLBACK;
+  if (st & ST_OUT_OF_DOMAIN) q |= QA_OUT_OF_DOMAIN;
+  if (nr > 0u) q |= QA_REJECTED;
+  a.qa[r] = (uint8_t)q;
+}
+KF_PIXEL_OP(OpProduct, ProductArgs, pixel_product);
+
 template <int NP, class M = StructDense>
 KF_HD void symv(const float (&A)[ntri(NP)], const float (&x)[NP], float (&y)[NP]) {
 #pragma unroll

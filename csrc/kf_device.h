@@ -400,7 +400,7 @@ __global__ __launch_bounds__(BLOCK) void jacobi_kernel(JacobiArgs a) {
 }
 
 // Every auxiliary per-pixel pass (kf_core.h KF_PIXEL_OP: propagate, invert,
-// operator, gp_operator, hessian, unpack, marginal, smooth, innovation): one
+// operator, gp_operator, hessian, unpack, marginal, product, smooth, innovation): one
 // pixel per thread, grid-stride, every SoA row read and written coalesced.  The
 // pass is the tag OP; its arguments' N is the pixel count.
 template <int NP, class OP>

@@ -374,6 +374,7 @@ int host_marginal(int np, const RasterArgs& a) {
   if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return -1;
   return host_pixels<OpMarginal>(np, a);
 }
+int host_product(int np, const ProductArgs& a) { return product_args_ok(np, a) ? host_pixels<OpProduct>(np, a) : -1; }
 int host_smooth(int np, const SmoothArgs& a) { return smooth_args_ok(np, a) ? host_pixels<OpSmooth>(np, a) : -1; }
 int host_innovation(int np, const InnovationArgs& a) {
   if (!innovation_args_ok(np, a)) return -1;

@@ -641,6 +641,9 @@ hipError_t dev_marginal(int np, const RasterArgs& a, hipStream_t s) {
   if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return hipErrorInvalidValue;
   return launch_pixels<OpMarginal>(np, a, s);
 }
+hipError_t dev_product(int np, const ProductArgs& a, hipStream_t s) {
+  return product_args_ok(np, a) ? launch_pixels<OpProduct>(np, a, s) : hipErrorInvalidValue;
+}
 hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s) {
   return smooth_args_ok(np, a) ? launch_pixels<OpSmooth>(np, a, s) : hipErrorInvalidValue;
 }

@@ -51,6 +51,7 @@ hipError_t dev_gp_operator(int np, int d, const GpOperatorArgs& a, hipStream_t s
 bool gp_operator_supported(int np, int d);
 hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s);
 hipError_t dev_marginal(int np, const RasterArgs& a, hipStream_t s);       // a.kind: MARG_*
+hipError_t dev_product(int np, const ProductArgs& a, hipStream_t s);       // physical-unit planes, interval, QA byte
 hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s);         // one backward step of the RTS smoother
 hipError_t dev_innovation(int np, const InnovationArgs& a, hipStream_t s); // statistics and the chi-square gate
 hipError_t dev_reduce(const double* partials, int n, double* out, hipStream_t s);
@@ -90,6 +91,7 @@ int host_hessian(int np, const HessianArgs& a);
 int host_gp_operator(int np, const GpOperatorArgs& a);
 int host_unpack(int np, const RasterArgs& a);
 int host_marginal(int np, const RasterArgs& a);
+int host_product(int np, const ProductArgs& a);
 int host_smooth(int np, const SmoothArgs& a);
 int host_innovation(int np, const InnovationArgs& a);
 // obs_order chunk: pixels per scatter workgroup; local = 1 partitions each

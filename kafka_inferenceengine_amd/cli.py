@@ -167,13 +167,27 @@ def _build(args, comm, q_scale=None):
 
     def make_out(folder):
         """The run's output class and options, writing into ``folder`` (None: device-resident)."""
+        physical = getattr(args, "out_physical", None)
+        interval = getattr(args, "out_interval", None)
+        qa = bool(getattr(args, "out_qa", False))
+        if interval is not None and not physical:
+            raise SystemExit("--out-interval belongs to --out-physical")
+        interval = 0.95 if interval is None else interval
+        if not 0.0 < interval < 1.0:
+            raise SystemExit("--out-interval LEVEL: a credible level in (0, 1)")
+        from .models.transforms import TRANSFORM_TABLES, product_name
+        products = [product_name(p, t) for p, t in (TRANSFORM_TABLES[physical].items() if physical else ())
+                    if p in params]
+        if physical and not products:
+            raise SystemExit(f"--out-physical {physical}: none of its parameters is in this run's state "
+                             f"({', '.join(params)})")
         if not folder:
-            return k.DeviceOutput(params, uncertainty=args.out_unc)
+            return k.DeviceOutput(params, uncertainty=args.out_unc, physical=physical, level=interval, qa=qa)
 
         def _ranges(items, flag):
             rg = {}
             for name, lo, hi in items or []:
-                if name not in params:
+                if name not in params and not (flag == "--out-range" and name in products):
                     raise SystemExit(f"{flag} {name}: not a parameter of this run ({', '.join(params)})")
                 try:
                     rg[name] = (float(lo), float(hi))
@@ -191,7 +205,8 @@ def _build(args, comm, q_scale=None):
                              folder, prefix=args.prefix, level=args.out_level, gather=args.out_gather,
                              predictor=3 if args.out_fast else 1, strategy="rle" if args.out_fast else None,
                              keep_timesteps=args.out_keep, encoder=args.out_encoder,
-                             huffman=args.out_huffman, uncertainty=args.out_unc, **scaled)
+                             huffman=args.out_huffman, uncertainty=args.out_unc, physical=physical,
+                             interval=interval, qa=qa, **scaled)
 
     out = make_out(args.out)
     kf = k.LinearKalman(obs, out, mask, factory, params, state_propagation=prop,
@@ -415,6 +430,15 @@ def main(argv=None):
                    help="the _unc rasters: conditional, 1/sqrt(diag(P^-1)) (what the reference writes: every other "
                         "parameter of the pixel held fixed), or marginal, sqrt(diag(P)) (the posterior std of the "
                         "parameter itself; a separate pass over the stored state on every output date)")
+    r.add_argument("--out-physical", default=None, choices=["tip", "sail"],
+                   help="also write physical-unit products (tip: LAI from TeLAI; sail: cab, car, cw, cm, lai, ala): "
+                        "per product NAME_A%%Y%%j.tif with the credible interval's ends _lo.tif / _hi.tif, from a "
+                        "separate pass over the stored state on every output date")
+    r.add_argument("--out-interval", type=float, default=None, metavar="LEVEL",
+                   help="--out-physical: the central credible level of the interval, in (0, 1) (default 0.95)")
+    r.add_argument("--out-qa", action="store_true",
+                   help="also write QA_A%%Y%%j.tif, one quality byte per pixel (bit legend in the file's metadata; "
+                        "255 outside the state mask)")
     r.add_argument("--in-decoder", default="host", choices=["host", "device"],
                    help="--s2-folder granules: DEFLATE tiles inflated by the host thread pool (host), or shipped "
                         "compressed and inflated on the GPU (device: 256 x 256 tiles, 16-bit samples, predictor 1 / 2; "

@@ -162,6 +162,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         self._chunks = None               # per-chunk convergence state (config.convergence_chunk)
         self.last_chunk_iters = None      # {GN iterations: chunks} of the last date (chunked test)
         self.ood_history = None           # config.domain_history: ST_OUT_OF_DOMAIN on any date so far
+        self._qa_acc = None               # a QA output: the timestep's status / nobs / nrej folded over its dates
         self.last_innovation = None       # config.innovation_*: the last date's {"chi2", "nobs", "nrej"}
         self.gate_history = None          # config.innovation_gate: dates with a rejection, per pixel (int32)
         self.evidence = None              # config.innovation_evidence: the run's per-pixel accumulators
@@ -336,6 +337,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         self.current_timestep = timestep
         self._check_marginal_output()
         self._check_innovation()
+        self._qa_acc = None            # QA inputs of the timestep (status, nobs, nrej), folded over its dates
         t0 = time.perf_counter()
         forecast = state
         if advance:
@@ -586,6 +588,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                                                   order=prep[3] if ready and prep[3] is not None else False)
                 finally:
                     self._lookahead_fn = None
+                if self._qa_output():
+                    self._qa_accumulate()
             forecast = res.state
             if self.config.domain_history and getattr(self, "last_status", None) is not None and self.N:
                 # pixels whose GP inputs left an emulator's domain on any date of the run
@@ -1388,6 +1392,9 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             st = res.state
             total_iter += res.n_iter
             norms += res.norms
+            if self._qa_output():
+                # one band at a time: the fold over a date's bands is the fold over a timestep's dates
+                self._qa_accumulate()
         self.previous_state = Previous_State(step, st.x, None, st.P)
         return AssimilationResult(st, total_iter, norms, None)
 
@@ -1446,7 +1453,10 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         state.require_full("the output dump")
         with self.timer.phase("output"):
             if hasattr(self.output, "dump_state"):
-                self.output.dump_state(timestep, state, self)
+                if self._qa_output():
+                    self.output.dump_state(timestep, state, self, qa_inputs=self._qa_inputs())
+                else:
+                    self.output.dump_state(timestep, state, self)
                 return
             x, P = state.to_reference()
             if state.kind == PRECISION:
@@ -1460,8 +1470,52 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         """The output rasters are written by the analysis kernel itself
         (EngineConfig.fuse_output, an output with device rasters), not dumped
         from the state afterwards."""
-        return (self.config.fuse_output and not self._marginal_output()
+        return (self.config.fuse_output and not self._marginal_output() and not self._product_output()
                 and hasattr(self.output, "device_targets"))
+
+    def _product_output(self) -> bool:
+        """The output writes physical-unit products or the QA layer
+        (``physical=`` / ``qa=``): as for marginal rasters nothing is fused into
+        the analysis and every row of the state is stored; ``dump_state`` runs
+        the passes."""
+        spec = getattr(self.output, "products", None)
+        return spec is not None and bool(getattr(spec, "active", False))
+
+    def _qa_output(self) -> bool:
+        spec = getattr(self.output, "products", None)
+        return spec is not None and bool(getattr(spec, "qa", False))
+
+    def _qa_accumulate(self):
+        """Fold the analysis just run (a date; under ``band_sequential`` one band
+        of a date) into the timestep's QA inputs, per pixel on the device: ST_NO_OBS is kept where every date of the timestep has it
+        (AND), every other status bit where any date has it (OR); the counts of
+        observations checked and rejected by the innovation gate add up
+        (saturating at 255)."""
+        N = self.N
+        st = getattr(self, "last_status", None)
+        if st is None or not N:
+            return
+        st = st[:N]
+        li = self.last_innovation if self._screening() else None
+        acc = getattr(self, "_qa_acc", None)
+        if acc is None:
+            self._qa_acc = {"status": st.clone(), "nobs": None if li is None else li["nobs"].clone(),
+                            "nrej": None if li is None else li["nrej"].clone()}
+            return
+        no_obs = acc["status"] & st & K.ST_NO_OBS
+        acc["status"] = ((acc["status"] | st) & (0xFF ^ K.ST_NO_OBS)) | no_obs
+        if li is not None and acc["nobs"] is not None:
+            for key in ("nobs", "nrej"):
+                acc[key] = (acc[key].to(torch.int16) + li[key].to(torch.int16)).clamp_(max=255).to(torch.uint8)
+
+    def _qa_inputs(self):
+        """(status, nobs, nrej) of the timestep for the QA layer; a timestep
+        without a date: ST_NO_OBS everywhere and nothing else."""
+        acc = getattr(self, "_qa_acc", None)
+        if acc is None:
+            status = torch.full((max(self.N, 1),), int(K.ST_NO_OBS), dtype=torch.uint8, device=self.device)
+            return status, None, None
+        return acc["status"], acc["nobs"], acc["nrej"]
 
     def _marginal_output(self) -> bool:
         """The output writes marginal std rasters (``uncertainty="marginal"``): no
@@ -1476,6 +1530,9 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         if unc == "marginal" and self.config.spatial_gamma > 0:
             raise ValueError("uncertainty='marginal' with spatial_gamma > 0: under the spatial (GMRF) prior the "
                              "marginal std is not a per-pixel quantity")
+        if self._product_output() and self.config.spatial_gamma > 0:
+            raise ValueError("physical-unit products / QA with spatial_gamma > 0: their interval is a marginal one, "
+                             "which under the spatial (GMRF) prior is not a per-pixel quantity")
 
     def unc(self, state: KFState, kind: str = "conditional") -> torch.Tensor:
         """Per-parameter std, [n_p, N].  "conditional": 1/sqrt(diag(P^-1))

@@ -6,7 +6,7 @@ from .kf_tools import (NoHessianMethod, PropagatorSpec, blend_prior, evidence_bl
                        hessian_correction,
                        hessian_correction_multiband, hessian_correction_pixel, identity_propagation,
                        innovation_blocks,
-                       make_no_propagation, make_partial_prior_propagator, no_propagation,
+                       make_no_propagation, make_partial_prior_propagator, no_propagation, product_blocks,
                        propagate_and_blend_prior, propagate_information_filter, propagate_information_filter_approx_SLOW,
                        propagate_information_filter_LAI, propagate_information_filter_SLOW, propagate_standard_kalman,
                        rts_smooth_blocks, tip_prior_full, tip_prior_noLAI)

@@ -428,3 +428,79 @@ def evidence_blocks(P, y, w, H0, h, kind="precision", ok=None):
     nobs = counted.sum(axis=0).astype(np.int64)
     loglik = -0.5 * (d2 + logdet + nobs * np.log(2.0 * np.pi))
     return d2, logdet, nobs, loglik
+
+
+def product_blocks(x, blocks, transforms, z, kind="precision", status=None, nobs=None, nrej=None):
+    """Float64 oracle of ``ops.kernels.product`` (csrc/kf_core.h ``pixel_product``):
+    the same definitions on the float32-rounded inputs and the float32 ``z``.
+
+    ``x`` [N, n]; ``blocks`` [N, n, n], the precision (``kind="precision"``) or
+    covariance blocks; ``transforms``: one ``ParameterTransform`` or None per
+    parameter; ``status`` / ``nobs`` / ``nrej``: optional uint8 [N].  Returns
+    ``(med, lower, upper, qa, clamped)``: the three [N, n_sel] product planes of
+    the selected parameters (state order), the QA bytes [N] and ``clamped``
+    [3, N, n_sel], the clamped arguments (of the median, of x - z sigma and of
+    x + z sigma) the transforms were applied to."""
+    from ..ops.kernels import ST_BAD_OP, ST_FALLBACK, ST_NO_OBS, ST_NONFINITE, ST_NONSPD, ST_OUT_OF_DOMAIN
+    if kind not in ("precision", "covariance"):
+        raise ValueError("kind must be 'precision' or 'covariance'")
+    x = np.asarray(x, dtype=np.float32).astype(np.float64)
+    A = np.asarray(blocks, dtype=np.float32).astype(np.float64)
+    N, n = x.shape
+    z = float(np.float32(z))
+    transforms = list(transforms)
+    if len(transforms) != n or A.shape != (N, n, n):
+        raise ValueError("x [N, n], blocks [N, n, n] and one transform (or None) per parameter")
+    var = np.full((N, n), np.nan)
+    if kind == "covariance":
+        var = np.diagonal(A, axis1=1, axis2=2).copy()
+        block_ok = np.ones(N, bool)
+    else:
+        block_ok = np.isfinite(A).all(axis=(1, 2))
+        for i in np.nonzero(block_ok)[0]:
+            try:
+                np.linalg.cholesky(A[i])
+                var[i] = np.diagonal(np.linalg.inv(A[i]))
+            except np.linalg.LinAlgError:
+                block_ok[i] = False
+        with np.errstate(invalid="ignore"):
+            block_ok &= (np.isfinite(var) & (var > 0)).all(axis=1)
+    with np.errstate(invalid="ignore"):
+        var_ok = block_ok[:, None] & np.isfinite(var) & (var > 0)
+    sel = [j for j, t in enumerate(transforms) if t is not None]
+    med, lower, upper = (np.full((N, len(sel)), np.nan) for _ in range(3))
+    clamped = np.full((3, N, len(sel)), np.nan)
+    qa = np.zeros(N, dtype=np.uint8)
+    if not sel and kind == "precision":
+        qa[~block_ok] |= 16
+
+    def clamp(u, lo, hi):                       # NaN stays NaN, as the kernel's
+        with np.errstate(invalid="ignore"):
+            return np.where(u < lo, lo, np.where(u > hi, hi, u))
+
+    for s, j in enumerate(sel):
+        t = transforms[j]
+        _, _, lo, hi = t.f32()
+        xj = x[:, j]
+        have = var_ok[:, j] & np.isfinite(xj)
+        sd = np.sqrt(np.where(have, var[:, j], 1.0))
+        um, up = xj - z * sd, xj + z * sd
+        c = clamped[:, :, s]
+        c[0], c[1], c[2] = clamp(xj, lo, hi), clamp(um, lo, hi), clamp(up, lo, hi)
+        f0, fm, fp = t.apply(c[0]), t.apply(c[1]), t.apply(c[2])
+        med[:, s] = f0
+        lower[:, s] = np.where(have, np.minimum(fm, fp), np.nan)
+        upper[:, s] = np.where(have, np.maximum(fm, fp), np.nan)
+        c[1:, ~have] = np.nan
+        with np.errstate(invalid="ignore"):
+            qa[~have] |= 16
+            qa[(xj < lo) | (xj > hi)] |= 32
+            qa[have & ((um < lo) | (um > hi) | (up < lo) | (up > hi))] |= 64
+    st = np.zeros(N, np.uint8) if status is None else np.asarray(status, dtype=np.uint8)[:N]
+    no = np.zeros(N, np.uint8) if nobs is None else np.asarray(nobs, dtype=np.uint8)[:N]
+    nr = np.zeros(N, np.uint8) if nrej is None else np.asarray(nrej, dtype=np.uint8)[:N]
+    qa[((st & ST_NO_OBS) != 0) | ((no > 0) & (nr >= no))] |= 1
+    qa[(st & (ST_FALLBACK | ST_NONSPD | ST_NONFINITE | ST_BAD_OP)) != 0] |= 2
+    qa[(st & ST_OUT_OF_DOMAIN) != 0] |= 4
+    qa[nr > 0] |= 8
+    return med, lower, upper, qa, clamped

@@ -21,6 +21,7 @@ from queue import Queue
 import numpy as np
 import torch
 
+from ..models.transforms import QA_FILL, QA_LEGEND, TRANSFORM_TABLES, credible_z, resolve_products
 from ..ops import kernels as K
 from .tiff import write_tiff
 
@@ -32,6 +33,64 @@ def _check_uncertainty(uncertainty):
     if uncertainty not in UNCERTAINTY_KINDS:
         raise ValueError("uncertainty must be 'conditional' or 'marginal'")
     return uncertainty
+
+
+class ProductSpec:
+    """The physical-unit products and the QA layer of an output (``physical=``,
+    ``level=``, ``qa=`` of the output classes): ``items`` [(j, name, transform)]
+    in state order, ``z`` the interval's half width in standard deviations."""
+
+    def __init__(self, parameter_list, physical=None, level=0.95, qa=False):
+        if isinstance(physical, str):
+            if physical not in TRANSFORM_TABLES:
+                raise ValueError("physical: a mapping parameter -> ParameterTransform, 'tip' or 'sail'")
+            physical = TRANSFORM_TABLES[physical]
+        self.items = resolve_products(parameter_list, physical)
+        if any(name.upper() == "QA" for _, name, _ in self.items) and qa:
+            raise ValueError("product name 'QA' collides with the QA layer")
+        self.level = float(level)
+        self.z = credible_z(level)
+        self.qa = bool(qa)
+        self.names = [name for _, name, _ in self.items]
+
+    @property
+    def active(self) -> bool:
+        return bool(self.items) or self.qa
+
+    @property
+    def n_sel(self) -> int:
+        return len(self.items)
+
+    def table(self, n):
+        """One transform (or None) per parameter of an n-parameter state."""
+        t = [None] * n
+        for j, _, tr in self.items:
+            if j >= n:
+                raise ValueError("a product's parameter lies outside the state")
+            t[j] = tr
+        return t
+
+    def metadata(self, s):
+        """GDAL_METADATA items of product s's files."""
+        _, _, tr = self.items[s]
+        return {"TRANSFORM": tr.describe(), "UNITS": tr.units, "LEVEL": repr(self.level)}
+
+    @staticmethod
+    def qa_metadata():
+        return {f"QA_BIT_{i}": text.split(": ", 1)[1] for i, text in enumerate(QA_LEGEND)} | {"QA_FILL": str(QA_FILL)}
+
+    def from_blocks(self, x_analysis, P, P_inv, n, status=None):
+        """The reference-API path: (med, lower, upper [N, n_sel], qa [N]) in
+        float64 by ``inference.kf_tools.product_blocks``, from the covariance
+        where it was handed in, else the precision blocks."""
+        from ..inference.kf_tools import product_blocks
+        from ..utils.blocks import sparse_to_blocks
+        m = P if P is not None else P_inv
+        blocks = m.blocks() if hasattr(m, "blocks") else sparse_to_blocks(m, n)
+        x = np.asarray(x_analysis, dtype=np.float64).reshape(-1, n)
+        med, lower, upper, qa, _ = product_blocks(x, blocks, self.table(n), self.z,
+                                                  kind="covariance" if P is not None else "precision", status=status)
+        return med, lower, upper, qa
 
 
 def _marginal_from_blocks(P, P_inv, n):
@@ -178,14 +237,38 @@ class KafkaOutput:
     pixel from the stored analysis state by ``ops.kernels.marginal``; the
     engine then dumps the state after the analysis instead of fusing the
     rasters into it.  A pixel whose precision is not SPD is NaN.  The files
-    keep their names and carry an ``UNCERTAINTY`` item in GDAL_METADATA."""
+    keep their names and carry an ``UNCERTAINTY`` item in GDAL_METADATA.
+
+    ``physical`` / ``interval`` / ``qa``: physical-unit products with a
+    credible interval, and a QA layer.  ``physical``: a mapping parameter ->
+    ``models.transforms.ParameterTransform`` (or ``TIP_TRANSFORMS`` /
+    ``SAIL_TRANSFORMS``, or "tip" / "sail").  Each listed parameter of
+    ``parameter_list`` gets three more files per timestep,
+    ``{name}_A%Y%j.tif`` (the transform of the state), ``..._lo.tif`` and
+    ``..._hi.tif`` (the ends of the central credible interval of level
+    ``interval``, 0.95 by default -- the other output classes call it
+    ``level``, which here is the DEFLATE level), ``name`` the transform's or
+    ``<parameter>_phys``; GDAL_METADATA carries ``TRANSFORM``, ``UNITS`` and
+    ``LEVEL``.  ``qa=True`` adds ``QA_A%Y%j.tif``: one uint8 per pixel
+    (``models.transforms.QA_LEGEND``, in the file's metadata; 255 outside the
+    state mask), written as it is by the writer thread.  Both come from one
+    ``ops.kernels.product`` pass over the stored state after the standard
+    planes (the engine then takes the launches ``uncertainty="marginal"``
+    takes) and go through the same host / device encoder path as a second
+    channel; the standard rasters are those of the unfused run
+    (``fuse_output=False``), which in the information form are the fused run's.  With ``sample_type="uint16"``
+    a product's range is the transform's physical range where its bounds are
+    finite, else ``ranges[name]``."""
 
     def __init__(self, parameter_list, geotransform, projection, folder, prefix=None, fmt="GTiff",
                  compress="deflate", asynchronous=True, level: int = 6, tile: int = 256, gather: bool = False,
                  threads: int | None = None, predictor: int = 1, strategy: str | None = None,
                  keep_timesteps: int | None = None, encoder: str = "auto", huffman: str = "fixed",
-                 sample_type: str = "float32", ranges=None, unc_ranges=None, uncertainty: str = "conditional"):
+                 sample_type: str = "float32", ranges=None, unc_ranges=None, uncertainty: str = "conditional",
+                 physical=None, interval: float = 0.95, qa: bool = False):
         self.uncertainty = _check_uncertainty(uncertainty)
+        self.products = ProductSpec(list(parameter_list), physical, interval, qa)
+        self.physical, self.interval, self.qa = physical, self.products.level, self.products.qa
         if encoder not in ("auto", "device", "host"):
             raise ValueError("encoder must be 'auto', 'device' or 'host'")
         if huffman not in ("fixed", "dynamic"):
@@ -206,6 +289,18 @@ class KafkaOutput:
                 both.append([(float(rg[p][0]), float(rg[p][1])) for p in parameter_list])
                 K.TileEncoder.quantiser(both[-1])       # hi <= lo or non-finite bounds: ValueError
             self._ranges = tuple(both)
+            # a product's range: the transform's physical range where its bounds are finite (the clamp
+            # guarantees it), else ranges[product name]
+            prg = []
+            for _, name, tr in self.products.items:
+                rg_p = ranges[name] if name in ranges else tr.physical_range()
+                if rg_p is None:
+                    raise ValueError(f"sample_type='uint16': product {name!r} has an unbounded transform and needs "
+                                     f"ranges[{name!r}] = (lo, hi)")
+                prg.append((float(rg_p[0]), float(rg_p[1])))
+            if prg:
+                K.TileEncoder.quantiser(prg)
+            self._prod_ranges = prg
         elif ranges is not None or unc_ranges is not None:
             raise ValueError("ranges / unc_ranges belong to sample_type='uint16'")
         self.saturated = 0        # uint16: samples clamped to their range so far
@@ -214,7 +309,8 @@ class KafkaOutput:
         self.huffman = huffman
         self._enc = None          # ops.kernels.TileEncoder (device encoder)
         self._copier = None       # device encoder: the thread bringing compressed tiles to pinned memory
-        self._eslots = []         # device encoder: ring of 2 (packed device buffer, meta pinned, host pinned, done)
+        self._eslots = {}         # device encoder, per channel: ring of 2 (packed device buffer, meta pinned,
+        self._eturn = {}          # host pinned, done)
         self.geotransform = geotransform
         self.projection = projection
         self.folder = folder
@@ -235,7 +331,8 @@ class KafkaOutput:
         os.makedirs(folder, exist_ok=True)
         self._w = _Writer() if asynchronous else None
         self._dev = None          # DeviceOutput: device planes the analysis kernel writes
-        self._host = []           # pinned host planes in flight (ring of 2)
+        self._host = {}           # per channel: pinned host planes in flight (ring of 2)
+        self._turn = {}
         self._stream = None
         self.written = []
         self.write_s = []         # per timestep: encode + write wall seconds (writer thread)
@@ -258,33 +355,67 @@ class KafkaOutput:
             return f"{self.prefix}_r{engine.comm.rank}" if self.prefix is not None else f"r{engine.comm.rank}"
         return self.prefix
 
-    def _write_all(self, timestep, mean, unc, gt, prefix):
+    def _std_groups(self, mean, unc):
+        """The standard rasters as file groups: (planes, suffix, uint16 ranges, per-file metadata)."""
+        rg = self._ranges if self._ranges is not None else (None, None)
+        n = len(self.parameter_list)
+        return [(mean, "", rg[0], [self._metadata("")] * n), (unc, "_unc", rg[1], [self._metadata("_unc")] * n)]
+
+    def _write_all(self, timestep, names_in, groups, gt, prefix, extend=False, qa=None):
+        """Encode and write the files of one channel: ``groups`` of host planes
+        (``_std_groups`` / ``_product_groups``) over the file names ``names_in``;
+        ``qa``: the QA plane [H, W] uint8, written with them.  ``extend``: the
+        files belong to the timestep whose standard rasters were written last."""
         t0 = time.perf_counter()
         names = []
         u16 = self.sample_type == "uint16"
         sat_last = {}
-        for kind, (planes, suffix) in enumerate(((mean, ""), (unc, "_unc"))):
+        for planes, suffix, rg, metas in groups:
             if u16:
                 # the host runner of the device encoder's quantiser: the same samples on both paths
-                rg = self._ranges[kind]
                 _, _, scale, offset = K.TileEncoder.quantiser(rg)
                 planes, sat = K.quantise_u16(np.ascontiguousarray(planes, dtype=np.float32), rg)
-            for ii, param in enumerate(self.parameter_list):
+            for ii, param in enumerate(names_in):
                 fn = _fname(self.folder, param, timestep, prefix, suffix)
                 if u16:
                     write_tiff(fn, planes[ii], gt, self.projection, self.compress, level=self.level, tile=self.tile,
                                threads=self.threads, predictor=2, strategy=self.strategy, nodata=65535,
-                               scale=scale[ii], offset=offset[ii], metadata=self._metadata(suffix))
+                               scale=scale[ii], offset=offset[ii], metadata=metas[ii])
                     sat_last[os.path.basename(fn)] = int(sat[ii])
                     self.saturated += int(sat[ii])
                 else:
                     write_tiff(fn, planes[ii], gt, self.projection, self.compress, level=self.level, tile=self.tile,
                                threads=self.threads, predictor=self.predictor, strategy=self.strategy,
-                               metadata=self._metadata(suffix))
+                               metadata=metas[ii])
                 self.written.append(fn)
                 names.append(fn)
                 self.bytes_in += planes[ii].nbytes
                 self.bytes_out += os.path.getsize(fn)
+        if qa is not None:
+            names.append(self._write_qa(timestep, qa, gt, prefix))
+        self._written_step(names, sat_last, t0, extend)
+
+    def _write_qa(self, timestep, qa, gt, prefix):
+        fn = _fname(self.folder, "QA", timestep, prefix)
+        qa = np.ascontiguousarray(qa, dtype=np.uint8)
+        write_tiff(fn, qa, gt, self.projection, "deflate", level=self.level, tile=self.tile or 256,
+                   threads=self.threads, nodata=QA_FILL, metadata=ProductSpec.qa_metadata())
+        self.written.append(fn)
+        self.bytes_in += qa.nbytes
+        self.bytes_out += os.path.getsize(fn)
+        return fn
+
+    def _written_step(self, names, sat_last, t0, extend):
+        """Bookkeeping of one channel's files: the product channel (``extend``)
+        adds to the timestep its standard rasters opened."""
+        u16 = self.sample_type == "uint16"
+        if extend and self.write_s:
+            if u16:
+                self.saturated_last.update(sat_last)
+            self.write_s[-1] += time.perf_counter() - t0
+            if self.keep_timesteps is not None and self._by_step:
+                self._by_step[-1].extend(names)
+            return
         if u16:
             self.saturated_last = sat_last
         self.write_s.append(time.perf_counter() - t0)
@@ -341,19 +472,21 @@ class KafkaOutput:
         return ("libdeflate" if fast and self.strategy in (None, "default") else "zlib") + u16
 
     # ------------------------------------------------------- device path
-    def device_targets(self, engine, dev, alias: bool = True):
+    def _device_output(self):
         if self._dev is None:
-            self._dev = DeviceOutput(self.parameter_list, uncertainty=self.uncertainty)
-        return self._dev.device_targets(engine, dev, alias)
+            self._dev = DeviceOutput(self.parameter_list, uncertainty=self.uncertainty, physical=self.physical,
+                                     level=self.interval, qa=self.qa)
+        return self._dev
+
+    def device_targets(self, engine, dev, alias: bool = True):
+        return self._device_output().device_targets(engine, dev, alias)
 
     def mark_written(self, timestep, state, engine):
         self._dev.mark_written(timestep, state, engine)
         self._ship(timestep, engine)
 
-    def dump_state(self, timestep, state, engine):
-        if self._dev is None:
-            self._dev = DeviceOutput(self.parameter_list, uncertainty=self.uncertainty)
-        self._dev.dump_state(timestep, state, engine)
+    def dump_state(self, timestep, state, engine, qa_inputs=None):
+        self._device_output().dump_state(timestep, state, engine, qa_inputs=qa_inputs)
         self._ship(timestep, engine)
 
     def _device_encode(self, cuda: bool) -> bool:
@@ -367,68 +500,120 @@ class KafkaOutput:
         return ok
 
     def _ship(self, timestep, engine):
-        """Device planes -> pinned host (async, side stream) -> writer thread."""
-        mean_d, unc_d = self._dev.mean, self._dev.unc
-        n, HW = mean_d.shape
+        """Device planes -> pinned host (async, side stream) -> writer thread.
+        Two channels: the standard rasters (mean, unc over the parameters), then
+        -- where asked for -- the products (median, lo, hi over the product
+        names) with the QA plane; both take the same path."""
+        dv = self._dev
         H, W = engine.partition.strip_shape
         gt, pf = self._geo(engine), self._prefix(engine)
-        if self._gathering(engine):
-            both = torch.cat([mean_d, unc_d], 0)
-            rows = [b - a for a, b in engine.partition.bounds]
-            full = engine.comm.gather_to_root(both, [r * W for r in rows])
-            if engine.comm.rank != 0:
-                return
-            mean_d, unc_d = full[:n], full[n:]
-            H = sum(rows)
-        cuda = mean_d.is_cuda
-        if self._device_encode(cuda):
-            self._ship_encoded(timestep, mean_d, unc_d, n, H, W, gt, pf, release=not self._gathering(engine))
-            return
+        gathering = self._gathering(engine)
+        channels = [("std", self.parameter_list, [dv.mean, dv.unc], None)]
+        spec = self.products
+        if spec.active and (dv.phys is not None or dv.qa_plane is not None):
+            ns = spec.n_sel
+            channels.append(("prod", spec.names, [dv.phys[g * ns:(g + 1) * ns] for g in range(3)] if ns else [],
+                             dv.qa_plane))
+        last = None
+        for key, names, planes, qa_d in channels:
+            Hc = H
+            if gathering:
+                sizes = [pl.shape[0] for pl in planes]
+                parts = list(planes) + ([qa_d.to(torch.float32)[None]] if qa_d is not None else [])
+                rows = [b - a for a, b in engine.partition.bounds]
+                full = engine.comm.gather_to_root(torch.cat(parts, 0), [r * W for r in rows])
+                if engine.comm.rank != 0:
+                    continue
+                planes, at = [], 0
+                for m in sizes:
+                    planes.append(full[at:at + m])
+                    at += m
+                if qa_d is not None:
+                    qa_d = full[at].to(torch.uint8)
+                Hc = sum(rows)
+            cuda = (planes[0] if planes else qa_d).is_cuda
+            groups = self._std_groups(*planes) if key == "std" else (self._product_groups(planes) if planes else [])
+            if planes and self._device_encode(cuda):
+                last = self._ship_encoded(timestep, key, names, groups, qa_d, Hc, W, gt, pf)
+            else:
+                last = self._ship_planes(timestep, key, names, groups, qa_d, Hc, W, gt, pf, cuda)
+        if last is not None and not gathering:
+            # the planes' next writer waits for the last copy / encode of this date (DeviceOutput.release)
+            self._dev.release(last)
+
+    def _product_groups(self, phys):
+        """The product rasters as file groups: ``phys`` the [3 n_sel, ...] planes or
+        their three [n_sel, ...] thirds -- median, ``_lo`` and ``_hi``."""
+        spec = self.products
+        ns = spec.n_sel
+        metas = [spec.metadata(i) for i in range(ns)]
+        rg = self._prod_ranges if self._ranges is not None else None
+        if not isinstance(phys, (list, tuple)):
+            phys = [phys[g * ns:(g + 1) * ns] for g in range(3)]
+        return [(pl, suffix, rg, metas) for pl, suffix in zip(phys, ("", "_lo", "_hi"))]
+
+    def _ship_planes(self, timestep, key, names, groups, qa_d, H, W, gt, pf, cuda):
+        """Host encoder: the raw planes of one channel to pinned memory on the side
+        stream, encoded and written by the writer thread.  Returns the copy's event."""
+        first = groups[0][0] if groups else qa_d
         if cuda and self._stream is None:
-            self._stream = torch.cuda.Stream(mean_d.device)
-        # ring of two pinned buffer pairs; a pair is reused once its writer job is done
-        slot = self._next_slot(n, mean_d.shape[1], cuda)
-        hm, hu, done = slot
+            self._stream = torch.cuda.Stream(first.device)
+        n = groups[0][0].shape[0] if groups else 0
+        # ring of two pinned buffer sets; a set is reused once its writer job is done
+        hbufs, hqa, done = self._next_slot(key, len(groups), n, H * W, cuda, qa_d is not None)
         done.clear()
         ev = None
         if cuda:
-            self._stream.wait_stream(torch.cuda.current_stream(mean_d.device))
+            self._stream.wait_stream(torch.cuda.current_stream(first.device))
             with torch.cuda.stream(self._stream):
-                hm.copy_(mean_d, non_blocking=True)
-                hu.copy_(unc_d, non_blocking=True)
+                for hb, g in zip(hbufs, groups):
+                    hb.copy_(g[0][:, :H * W], non_blocking=True)
+                if qa_d is not None:
+                    hqa.copy_(qa_d[:H * W], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self._stream)
-            # the planes' next writer waits for this copy (DeviceOutput.release); an
-            # aliased mean (the state's x) is not recycled by the allocator before it
-            mean_d.record_stream(self._stream)
-            if not self._gathering(engine):
-                self._dev.release(ev)
+            # an aliased mean (the state's x) is not recycled by the allocator before the copy
+            for g in groups:
+                g[0].record_stream(self._stream)
         else:
-            hm.copy_(mean_d)
-            hu.copy_(unc_d)
+            for hb, g in zip(hbufs, groups):
+                hb.copy_(g[0][:, :H * W])
+            if qa_d is not None:
+                hqa.copy_(qa_d[:H * W])
 
-        def job(hm=hm, hu=hu, ev=ev, done=done):
+        def job(ev=ev, done=done):
             try:
                 if ev is not None:
                     t0 = time.perf_counter()
                     ev.synchronize()
                     self.d2h_s += time.perf_counter() - t0
-                self._write_all(timestep, hm.numpy().reshape(n, H, W), hu.numpy().reshape(n, H, W), gt, pf)
+                host = [(hb.numpy().reshape(n, H, W),) + tuple(g[1:]) for hb, g in zip(hbufs, groups)]
+                self._write_all(timestep, names, host, gt, pf, extend=key != "std",
+                                qa=None if hqa is None else hqa.numpy().reshape(H, W))
             finally:
                 done.set()
 
-        if self._w is not None:
-            self._w.submit(job)
-        else:
+        if self._w is None:
             job()
+        elif key != "std" and self._copier is not None:
+            # the standard channel went through the device encoder (copier thread, then writer): the
+            # same chain, so this timestep's files are written after its standard rasters
+            self._copier.submit(lambda: self._w.submit(job))
+        else:
+            self._w.submit(job)
+        return ev
 
-    def _ship_encoded(self, timestep, mean_d, unc_d, n, H, W, gt, pf, release: bool):
-        """Device encoder: both rasters' tiles encoded and packed into one device
-        buffer on the side stream, their sizes / offsets to pinned host memory;
-        the writer thread then copies exactly the compressed bytes and writes
-        the files (no encode on the host)."""
+    def _ship_encoded(self, timestep, key, names, groups, qa_d, H, W, gt, pf):
+        """Device encoder: every raster group's tiles encoded and packed into one
+        device buffer on the side stream, their sizes / offsets to pinned host
+        memory; the writer thread then copies exactly the compressed bytes and
+        writes the files (no encode on the host).  The QA plane (a byte per
+        pixel) goes to pinned memory as it is.  Returns the event after the encode."""
         from ..ops.kernels import TileEncoder
-        dev = mean_d.device
+        planes = [g[0] for g in groups]
+        G = len(planes)
+        n = planes[0].shape[0]
+        dev = planes[0].device
         if self._stream is None:
             self._stream = torch.cuda.Stream(dev)
         if self._enc is None:
@@ -441,29 +626,38 @@ class KafkaOutput:
         # pinned host bytes for the compressed tiles: allocated with the slot (a
         # multi-GB pinned allocation in the writer thread would stall a timed
         # date), sized for the raw planes plus the fixed-Huffman worst case
-        host_bytes = int(2 * n * H * W * (2 if u16 else 4) * 1.13) + 2 * nt * 64 + (1 << 20)
-        # meta: sizes and offsets of both rasters' tiles, then (uint16) the planes' saturation counts
-        meta_n = 4 * nt + (2 * n if u16 else 0)
-        packed, meta_h, host_box, done = self._next_enc_slot(2 * nt * bound, meta_n, dev, host_bytes)
+        host_bytes = int(G * n * H * W * (2 if u16 else 4) * 1.13) + G * nt * 64 + (1 << 20)
+        # meta: sizes and offsets of every group's tiles, then (uint16) the planes' saturation counts
+        meta_n = 2 * G * nt + (G * n if u16 else 0)
+        packed, meta_h, host_box, done = self._next_enc_slot(key, G * nt * bound, meta_n, dev, host_bytes)
         done.clear()
+        hqa = None
+        if qa_d is not None:
+            if len(host_box) < 2 or host_box[1].numel() != H * W:
+                del host_box[1:]
+                host_box.append(torch.empty(H * W, dtype=torch.uint8, pin_memory=True))
+            hqa = host_box[1]
         self._stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(self._stream):
-            if u16:
-                _, sm, om, qm = self._enc.encode(mean_d, H, W, packed=packed, ranges=self._ranges[0])
-                _, su, ou, qu = self._enc.encode(unc_d, H, W, packed=packed, base=om[-1:] + sm[-1:],
-                                                 ranges=self._ranges[1])
-                meta_h.copy_(torch.cat([sm, om, su, ou, qm, qu]), non_blocking=True)
-            else:
-                _, sm, om = self._enc.encode(mean_d, H, W, packed=packed)
-                _, su, ou = self._enc.encode(unc_d, H, W, packed=packed, base=om[-1:] + sm[-1:])
-                meta_h.copy_(torch.cat([sm, om, su, ou]), non_blocking=True)
+            meta, sats, base = [], [], None
+            for pl, g in zip(planes, groups):
+                kw = {} if base is None else {"base": base}
+                if u16:
+                    _, sz, of, q = self._enc.encode(pl, H, W, packed=packed, ranges=g[2], **kw)
+                    sats.append(q)
+                else:
+                    _, sz, of = self._enc.encode(pl, H, W, packed=packed, **kw)
+                meta += [sz, of]
+                base = of[-1:] + sz[-1:]
+            meta_h.copy_(torch.cat(meta + sats), non_blocking=True)
+            if hqa is not None:
+                hqa.copy_(qa_d[:H * W], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._stream)
-        mean_d.record_stream(self._stream)
-        unc_d.record_stream(self._stream)
-        if release:
-            self._dev.release(ev)
+        for pl in planes:
+            pl.record_stream(self._stream)
         wstream = self._wstream = getattr(self, "_wstream", None) or torch.cuda.Stream(dev)
+        gspec = [tuple(g[1:]) for g in groups]
 
         # two stages on two threads: the copier brings date t + 1's compressed
         # tiles to pinned memory while the writer writes date t's files (the
@@ -471,7 +665,8 @@ class KafkaOutput:
         # write; the ring of two keeps the stages one date apart)
         def write(host, m, done=done):
             try:
-                self._write_encoded(timestep, host, m, n, per, H, W, gt, pf)
+                self._write_encoded(timestep, host, m, names, gspec, n, per, H, W, gt, pf, extend=key != "std",
+                                    qa=None if hqa is None else hqa.numpy().reshape(H, W))
             finally:
                 done.set()
 
@@ -480,7 +675,7 @@ class KafkaOutput:
                 t0 = time.perf_counter()
                 ev.synchronize()
                 m = meta_h.numpy().copy()
-                total = int(m[4 * nt - 1] + m[3 * nt - 1])
+                total = int(m[2 * G * nt - 1] + m[(2 * G - 1) * nt - 1])
                 host = host_box[0]
                 if host is None or host.numel() < total:
                     host = host_box[0] = torch.empty(int(total * 1.25) + 4096, dtype=torch.uint8, pin_memory=True)
@@ -502,71 +697,76 @@ class KafkaOutput:
             self._copier.submit(copy)
         else:
             copy()
+        return ev
 
-    def _write_encoded(self, timestep, host, meta, n, per, H, W, gt, prefix):
+    def _write_encoded(self, timestep, host, meta, names_in, gspec, n, per, H, W, gt, prefix, extend=False, qa=None):
         from .tiff import write_tiff_tiles
         t0 = time.perf_counter()
         names = []
         nt = n * per
-        sm, om, su, ou = meta[:4 * nt].reshape(4, nt)
+        G = len(gspec)
+        so = meta[:2 * G * nt].reshape(2 * G, nt)
         u16 = self.sample_type == "uint16"
         sat_last = {}
-        for kind, (sizes, offs, suffix) in enumerate(((sm, om, ""), (su, ou, "_unc"))):
+        for kind, (suffix, rg, metas) in enumerate(gspec):
+            sizes, offs = so[2 * kind], so[2 * kind + 1]
             if u16:
-                _, _, scale, offset = K.TileEncoder.quantiser(self._ranges[kind])
-                sat = meta[4 * nt + kind * n:4 * nt + (kind + 1) * n]
-            for ii, param in enumerate(self.parameter_list):
+                _, _, scale, offset = K.TileEncoder.quantiser(rg)
+                sat = meta[2 * G * nt + kind * n:2 * G * nt + (kind + 1) * n]
+            for ii, param in enumerate(names_in):
                 fn = _fname(self.folder, param, timestep, prefix, suffix)
                 sl = slice(ii * per, (ii + 1) * per)
                 if u16:
                     write_tiff_tiles(fn, H, W, host, offs[sl], sizes[sl], gt, self.projection, threads=self.threads,
-                                     dtype="uint16", scale=scale[ii], offset=offset[ii],
-                                     metadata=self._metadata(suffix))
+                                     dtype="uint16", scale=scale[ii], offset=offset[ii], metadata=metas[ii])
                     sat_last[os.path.basename(fn)] = int(sat[ii])
                     self.saturated += int(sat[ii])
                 else:
                     write_tiff_tiles(fn, H, W, host, offs[sl], sizes[sl], gt, self.projection, predictor=3,
-                                     threads=self.threads, metadata=self._metadata(suffix))
+                                     threads=self.threads, metadata=metas[ii])
                 self.written.append(fn)
                 names.append(fn)
                 self.bytes_in += H * W * (2 if u16 else 4)
                 self.bytes_out += os.path.getsize(fn)
-        if u16:
-            self.saturated_last = sat_last
-        self.write_s.append(time.perf_counter() - t0)
-        self._prune(names)
+        if qa is not None:
+            names.append(self._write_qa(timestep, qa, gt, prefix))
+        self._written_step(names, sat_last, t0, extend)
 
-    def _next_enc_slot(self, packed_bytes, meta_n, dev, host_bytes):
-        if not self._eslots or self._eslots[0][0].numel() < packed_bytes or self._eslots[0][1].numel() != meta_n:
-            for sl in self._eslots:
+    def _next_enc_slot(self, key, packed_bytes, meta_n, dev, host_bytes):
+        ring = self._eslots.get(key)
+        if not ring or ring[0][0].numel() < packed_bytes or ring[0][1].numel() != meta_n:
+            for sl in ring or []:
                 sl[3].wait()                # a writer job still reading a slot being replaced
-            self._eslots = []
+            ring = self._eslots[key] = []
             for _ in range(2):
                 ev = threading.Event()
                 ev.set()
-                self._eslots.append((torch.empty(packed_bytes, dtype=torch.uint8, device=dev),
-                                     torch.empty(meta_n, dtype=torch.int64, pin_memory=True),
-                                     [torch.empty(host_bytes, dtype=torch.uint8, pin_memory=True)], ev))
-            self._eturn = 0
-        slot = self._eslots[self._eturn % 2]
-        self._eturn += 1
+                ring.append((torch.empty(packed_bytes, dtype=torch.uint8, device=dev),
+                             torch.empty(meta_n, dtype=torch.int64, pin_memory=True),
+                             [torch.empty(host_bytes, dtype=torch.uint8, pin_memory=True)], ev))
+            self._eturn[key] = 0
+        slot = ring[self._eturn[key] % 2]
+        self._eturn[key] += 1
         t0 = time.perf_counter()
         slot[3].wait()                      # its previous writer job has copied its tiles out
         self.slot_wait_s += time.perf_counter() - t0
         return slot
 
-    def _next_slot(self, n, cols, cuda):
-        if not self._host or self._host[0][0].shape != (n, cols):
+    def _next_slot(self, key, G, n, cols, cuda, qa):
+        sig = (G, n, cols, bool(qa))
+        ring = self._host.get(key)
+        if not ring or ring[0] != sig:
             pin = cuda and torch.cuda.is_available()
-            self._host = []
+            slots = []
             for _ in range(2):
                 ev = threading.Event()
                 ev.set()
-                self._host.append((torch.empty((n, cols), dtype=torch.float32, pin_memory=pin),
-                                   torch.empty((n, cols), dtype=torch.float32, pin_memory=pin), ev))
-            self._turn = 0
-        slot = self._host[self._turn % 2]
-        self._turn += 1
+                slots.append(([torch.empty((n, cols), dtype=torch.float32, pin_memory=pin) for _ in range(G)],
+                              torch.empty(cols, dtype=torch.uint8, pin_memory=pin) if qa else None, ev))
+            ring = self._host[key] = (sig, slots)
+            self._turn[key] = 0
+        slot = ring[1][self._turn[key] % 2]
+        self._turn[key] += 1
         t0 = time.perf_counter()
         slot[2].wait()                      # its previous writer job has finished with it
         self.slot_wait_s += time.perf_counter() - t0
@@ -584,7 +784,21 @@ class KafkaOutput:
         for ii in range(n_params):
             mean[ii][sm] = x_analysis[ii::n_params]
             unc[ii][sm] = sd[:, ii] if self.uncertainty == "marginal" else 1. / np.sqrt(d[ii::n_params])
-        self._write_all(timestep, mean, unc, self.geotransform, self.prefix)
+        self._write_all(timestep, self.parameter_list, self._std_groups(mean, unc), self.geotransform, self.prefix)
+        if self.products.active:
+            # the same definitions in float64 (inference.kf_tools.product_blocks); no status on this path
+            spec = self.products
+            med, lower, upper, qa = spec.from_blocks(x_analysis, P_analysis, P_analysis_inv, n_params)
+            phys = np.zeros((3 * spec.n_sel,) + sm.shape, dtype=np.float32)
+            for g, vals in enumerate((med, lower, upper)):
+                for i in range(spec.n_sel):
+                    phys[g * spec.n_sel + i][sm] = vals[:, i]
+            qa_plane = None
+            if spec.qa:
+                qa_plane = np.full(sm.shape, QA_FILL, dtype=np.uint8)
+                qa_plane[sm] = qa
+            self._write_all(timestep, spec.names, self._product_groups(phys) if spec.n_sel else [],
+                            self.geotransform, self.prefix, extend=True, qa=qa_plane)
 
     def flush(self):
         if self._copier is not None:
@@ -596,9 +810,12 @@ class KafkaOutput:
 class KafkaOutputMemory:
     """In-memory output (kafka_test.py:135-145)."""
 
-    def __init__(self, parameter_list, uncertainty: str = "conditional"):
+    def __init__(self, parameter_list, uncertainty: str = "conditional", physical=None, level: float = 0.95,
+                 qa: bool = False):
         self.parameter_list = list(parameter_list)
         self.uncertainty = _check_uncertainty(uncertainty)
+        self.products = ProductSpec(self.parameter_list, physical, level, qa)
+        self.physical, self.level, self.qa = physical, self.products.level, self.products.qa
         self.output = {}
 
     def dump_data(self, timestep, x_analysis, P_analysis, P_analysis_inv, state_mask, n_params=None):
@@ -613,6 +830,13 @@ class KafkaOutputMemory:
             d = P_analysis_inv.diagonal()
             for ii, p in enumerate(self.parameter_list):
                 sol[p + "_unc"] = 1. / np.sqrt(d[ii::n])
+        if self.products.active and (P_analysis is not None or P_analysis_inv is not None):
+            # physical-unit products: ``name``, ``name_lo``, ``name_hi`` and the ``QA`` bytes
+            med, lower, upper, qa = self.products.from_blocks(x_analysis, P_analysis, P_analysis_inv, n)
+            for i, name in enumerate(self.products.names):
+                sol[name], sol[name + "_lo"], sol[name + "_hi"] = med[:, i].copy(), lower[:, i].copy(), upper[:, i].copy()
+            if self.products.qa:
+                sol["QA"] = qa
         self.output[timestep] = sol
 
 
@@ -637,12 +861,25 @@ class DeviceOutput:
     writes that, so the engine does not ask for ``device_targets``: every date
     goes through ``dump_state``, one ``ops.kernels.marginal`` pass over the
     stored state (precision or, for the gain form, covariance) that writes the
-    mean planes as well."""
+    mean planes as well.
+
+    ``physical`` / ``level`` / ``qa``: physical-unit products with a credible
+    interval and the QA byte (see ``KafkaOutput``).  They too go through
+    ``dump_state``: after the standard planes, one ``ops.kernels.product`` pass
+    writes ``phys`` ([3 n_sel, plane]: the medians of the selected parameters,
+    then the lower, then the upper ends) and ``qa_plane`` (uint8, 255 outside
+    the state mask); ``keep_history`` keeps them in ``product_history``."""
 
     def __init__(self, parameter_list, keep_history: bool = False, alias_state: bool = True,
-                 uncertainty: str = "conditional"):
+                 uncertainty: str = "conditional", physical=None, level: float = 0.95, qa: bool = False):
         self.parameter_list = list(parameter_list)
         self.uncertainty = _check_uncertainty(uncertainty)
+        self.products = ProductSpec(self.parameter_list, physical, level, qa)
+        self.physical, self.level, self.qa = physical, self.products.level, self.products.qa
+        self.phys = None               # [3 n_sel, plane]: median, lower and upper planes of the products
+        self.qa_plane = None           # uint8 [plane], QA_FILL outside the state mask
+        self.product_history = {}      # keep_history: timestep -> (phys, qa_plane) clones (None where not asked for)
+        self._phys_bufs = self._qa_bufs = None
         self.keep_history = keep_history
         self.alias_state = bool(alias_state)
         self.mean = None
@@ -669,6 +906,12 @@ class DeviceOutput:
             self._idx = torch.from_numpy(idx).to(dev)
             self._identity = part.N == H * W
             self._plane = H * W
+            # the product planes alternate with the uncertainty planes (the same reader event guards a pair)
+            ns = self.products.n_sel
+            self._phys_bufs = [torch.zeros((3 * ns, H * W), dtype=torch.float32, device=dev) for _ in range(2)] \
+                if ns else None
+            self._qa_bufs = [torch.full((H * W,), QA_FILL, dtype=torch.uint8, device=dev) for _ in range(2)] \
+                if self.products.qa else None
         if self.unc is None:
             self.unc = self._unc_bufs[0]
 
@@ -717,7 +960,9 @@ class DeviceOutput:
         if self.keep_history:
             self.history[timestep] = (self.mean.clone(), self.unc.clone())
 
-    def dump_state(self, timestep, state, engine):
+    def dump_state(self, timestep, state, engine, qa_inputs=None):
+        """``qa_inputs``: the timestep's (status, nobs, nrej), each uint8 [>= N] on
+        the state's device or None -- the inputs of the QA bits 0-3."""
         n = engine.n_params
         self._ensure(engine, state.x.device)
         marginal = self.uncertainty == "marginal"
@@ -731,6 +976,20 @@ class DeviceOutput:
         elif state.N:
             K.unpack(n, st.x, st.P, mean, unc, idx=idx, N=state.N)
         self._pending, self._alias = unc, False
+        if self.products.active:
+            # one more pass over the state as it is stored (a covariance state holds the variances
+            # on its diagonal rows); the planes of the buffer pair _next_unc has just made current
+            spec = self.products
+            self.phys = self._phys_bufs[self._turn] if spec.n_sel else None
+            self.qa_plane = self._qa_bufs[self._turn] if spec.qa else None
+            if state.N:
+                sp = st if marginal else engine._materialize(state)
+                status, nobs, nrej = qa_inputs if qa_inputs is not None else (None, None, None)
+                K.product(n, sp.x, sp.P, spec.table(n), spec.z, phys=self.phys, qa=self.qa_plane, idx=idx,
+                          N=state.N, kind=sp.kind, status=status, nobs=nobs, nrej=nrej)
+            if self.keep_history:
+                self.product_history[timestep] = (None if self.phys is None else self.phys.clone(),
+                                                  None if self.qa_plane is None else self.qa_plane.clone())
         self.mark_written(timestep, state, engine)
 
     def to_host(self, shape=None):

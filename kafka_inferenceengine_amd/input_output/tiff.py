@@ -103,6 +103,11 @@ def _parse_item(text, name):
     return m.group(1) if m else None
 
 
+def _parse_items(text) -> dict:
+    """Every plain (role-less) item of a tag 42112 text, name -> text."""
+    return {m.group(1): m.group(2) for m in re.finditer(r'<Item name="([A-Za-z0-9_]+)">([^<]*)</Item>', text or "")}
+
+
 def _parse_scale_metadata(text) -> tuple:
     """(scale, offset) of a tag 42112 text; None where the item is absent."""
     out = []
@@ -283,6 +288,8 @@ def _geo_from_native(info) -> dict:
     out["scale"], out["offset"] = _parse_scale_metadata(info.get("gdal_metadata", ""))
     if _parse_item(info.get("gdal_metadata", ""), "UNCERTAINTY") is not None:
         out["uncertainty"] = _parse_item(info.get("gdal_metadata", ""), "UNCERTAINTY")
+    if _parse_items(info.get("gdal_metadata", "")):
+        out["metadata"] = _parse_items(info.get("gdal_metadata", ""))
     return out
 
 
@@ -443,6 +450,8 @@ def _read_tiff_py(path):
     info["scale"], info["offset"] = _parse_scale_metadata(tags.get(42112, ""))
     if _parse_item(tags.get(42112, ""), "UNCERTAINTY") is not None:
         info["uncertainty"] = _parse_item(tags.get(42112, ""), "UNCERTAINTY")
+    if _parse_items(tags.get(42112, "")):
+        info["metadata"] = _parse_items(tags.get(42112, ""))
     return arr.astype(dtype.newbyteorder("=")), info
 
 

@@ -6,4 +6,6 @@ from .operators import (OP_GP, OP_LINEAR, OP_PRECOMP, OP_SAR, TIP_BAND_MAPPER, L
                         create_sar_observation_operator, gp_spec)
 from .priors import (SAIL_PARAMETERS, TIP_PARAMETERS, DevicePrior, GaussianPrior, JRCPrior,  # noqa: F401
                      SAILPrior, sail_prior, tip_prior)
+from .transforms import (QA_FILL, QA_LEGEND, SAIL_TRANSFORMS, TIP_TRANSFORMS, ParameterTransform,  # noqa: F401
+                         credible_z, resolve_products)
 from .sar import WaterCloudModel, sar_observation_operator  # noqa: F401

@@ -1581,6 +1581,66 @@ def marginal(n_params, x, p, mean=None, unc=None, idx=None, N=None, kind="precis
                x.shape[1], _ptr(idx), _ptr(mean), _ptr(unc), plane, _dev(x), _stream(x))
 
 
+def product(n_params, x, p, transforms, z, phys=None, qa=None, idx=None, N=None, kind="precision", status=None,
+            nobs=None, nrej=None):
+    """Physical-unit product planes with a credible interval, and the QA byte
+    (csrc/kf_core.h ``pixel_product``).  ``transforms``: one entry per parameter,
+    a ``models.transforms.ParameterTransform`` or None (no product); ``z``: the
+    interval's half width in marginal standard deviations
+    (``models.transforms.credible_z``).  ``p``: the packed rows of P^-1
+    (``kind="precision"``) or of P (``kind="covariance"``), as ``marginal``.
+    ``phys`` [3 n_sel, plane] float32: the median planes of the n_sel selected
+    parameters (state order), then their lower and their upper ends; ``qa``
+    uint8 [plane]: the QA byte (the caller pre-fills both outside the raster
+    map).  ``status`` / ``nobs`` / ``nrej``: optional uint8 [>= N] inputs of the
+    QA bits 0-3.  At least one of ``phys`` / ``qa`` is written."""
+    from ..models.transforms import TRANSFORM_KINDS, ParameterTransform
+    check_np(n_params)
+    if kind not in MARGINAL_KINDS:
+        raise ValueError("kind must be 'precision' or 'covariance'")
+    transforms = list(transforms)
+    if len(transforms) != n_params:
+        raise ValueError(f"transforms: one entry (or None) per parameter, got {len(transforms)} for {n_params}")
+    z = float(z)
+    if not (z > 0.0 and np.isfinite(np.float32(z))):
+        raise ValueError("z must be positive and finite")
+    N = int(x.shape[1] if N is None else N)
+    dev = x.device
+    _check_soa(x, n_params, N, "x")
+    _check_soa(p, ntri(n_params), N, "p", device=dev)
+    if p is None or p.shape[1] != x.shape[1]:
+        raise ValueError("x and p must share their row stride")
+    sel, kinds, scale, offset, lo, hi = 0, [], [], [], [], []
+    for j, t in enumerate(transforms):
+        if t is not None and not isinstance(t, ParameterTransform):
+            raise ValueError(f"transforms[{j}] is not a ParameterTransform")
+        sel |= (t is not None) << j
+        s, o, a, b = t.f32() if t is not None else (1.0, 0.0, float("-inf"), float("inf"))
+        kinds.append(TRANSFORM_KINDS.index(t.kind) if t is not None else 0)
+        scale.append(s), offset.append(o), lo.append(a), hi.append(b)
+    n_sel = bin(sel).count("1")
+    if phys is None and qa is None:
+        raise ValueError("nothing to write: phys and qa are both None")
+    if (phys is None) != (n_sel == 0):
+        raise ValueError("phys goes with at least one transform, and every transform needs phys")
+    plane = phys.shape[1] if phys is not None else qa.shape[0]
+    if phys is not None:
+        _check_soa(phys, 3 * n_sel, 0, "phys", device=dev)
+    _check_vec(qa, plane, "qa", torch.uint8, dev)
+    if qa is not None and qa.shape[0] != plane:
+        raise ValueError("phys and qa planes differ in size")
+    if idx is not None:
+        _check_vec(idx, N, "idx", torch.int64, dev)
+    elif plane < N:
+        raise ValueError("output plane smaller than N without an index map")
+    for t, name in ((status, "status"), (nobs, "nobs"), (nrej, "nrej")):
+        _check_vec(t, N, name, torch.uint8, dev)
+    e = ext()
+    e.product(n_params, _ptr(x), _ptr(p), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION, N,
+              x.shape[1], _ptr(idx), _ptr(status), _ptr(nobs), _ptr(nrej), _ptr(phys), _ptr(qa), plane, sel, z,
+              kinds, scale, offset, lo, hi, _dev(x), _stream(x))
+
+
 def smooth(n_params, x_a, p_a, x_next, p_next, x_out, p_out, status, *, kind, prop_mask, m, q, q_pix=None, N=None):
     """One backward step of the fixed-interval (RTS) smoother, per pixel
     (csrc/kf_core.h ``pixel_smooth``).  ``x_a`` / ``p_a``: the filtered state of
