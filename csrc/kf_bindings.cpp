@@ -37,6 +37,7 @@ static py::dict plan_dict(const KernelPlan& p) {
   d["family"] = name.substr(0, name.find('<'));
   d["np"] = p.np, d["fd"] = p.fd, d["obs"] = p.obs, d["bs"] = p.bs, d["minw"] = p.minw, d["layout"] = p.layout;
   d["il"] = p.il, d["spec"] = p.spec, d["mixlo"] = p.mixlo, d["pf"] = p.pf, d["rows"] = p.rows, d["out"] = p.out;
+  d["joint"] = p.joint;
   return d;
 }
 
@@ -516,8 +517,13 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
   m.def("innovation", [](int np, uintptr_t x, uintptr_t p, int kind, uintptr_t bands, int nb, uintptr_t grp,
                          double gate, int scope, uintptr_t z, int64_t ldz, uintptr_t chi2, uintptr_t nobs,
                          uintptr_t nrej, uintptr_t status, uintptr_t screened, int64_t N, int64_t ld, bool device,
-                         uintptr_t stream, uintptr_t d2, uintptr_t logdet) {
+                         uintptr_t stream, uintptr_t d2, uintptr_t logdet, bool want_mfma,
+                         const std::vector<BandDesc>& host_bands, int gpm_frags, int band_layout) {
+    // want_mfma with host_bands (host copies of the nb descriptors), gpm_frags and band_layout as the band
+    // table has them: the matrix-core kernel where innovation_plan has one (kf_plan.h), device launches only
     InnovationArgs a{};
+    a.gpm_frags = gpm_frags;
+    a.band_layout = band_layout;
     a.d2 = P<float>(d2);           // joint statistic [N] (either one selects the joint instantiation)
     a.logdet = P<float>(logdet);
     a.N = N;
@@ -537,8 +543,34 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     a.nrej = P<uint8_t>(nrej);
     a.status = P<uint8_t>(status);
     a.screened = P<void* const>(screened);
-    if (device) check_hip(dev_innovation(np, a, (hipStream_t)stream), "innovation");
-    else check_host(host_innovation(np, a), "innovation");
+    if (device) {
+      const bool hb = want_mfma && (int)host_bands.size() == nb;
+      check_hip(dev_innovation(np, a, innovation_plan(np, a, hb, hb ? host_bands.data() : nullptr),
+                               (hipStream_t)stream), "innovation");
+    } else {
+      check_host(host_innovation(np, a), "innovation");
+    }
+  });
+  // the kernel a device launch of the innovation check takes (kf_plan.h innovation_plan); no device needed.
+  // bands: host descriptors; joint: d2 or logdet asked for.  innovation_table: the matrix-core kernels' names
+  m.def("innovation_plan", [](int np, const std::vector<BandDesc>& bands, int gpm_frags, int band_layout, bool joint,
+                              bool want_mfma) {
+    InnovationArgs a{};
+    a.nb = (int)bands.size();
+    a.gpm_frags = gpm_frags;
+    a.band_layout = band_layout;
+    static float joint_out;
+    if (joint) a.d2 = &joint_out;   // innovation_joint: either output asked for (never written here)
+    py::dict d = plan_dict(innovation_plan(np, a, want_mfma, bands.data()));
+    d["band_layout"] = d["family"].cast<std::string>() == "innovation_mfma_g_kernel" ? band_layout : 0;
+    return d;
+  });
+  m.def("innovation_table", []() {
+    std::vector<KernelPlan> plans;
+    launch_table_innovation(plans);
+    std::vector<std::string> names;
+    for (const KernelPlan& p : plans) names.push_back(plan_name(p));
+    return names;
   });
   // GeoTIFF tile encoder (predictor 3 + one zlib stream per 256^2 tile; mode:
   // fixed Huffman, or a dynamic table per tile where that is smaller)

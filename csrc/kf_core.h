@@ -1658,6 +1658,9 @@ struct InnovationArgs {
   void* const* screened;   // optional [nb] plane pointers (an entry may be null)
   float* d2;               // optional [N]: joint r^T S^-1 r (pixel_innovation<NP, true> only)
   float* logdet;           // optional [N]: log det S        (pixel_innovation<NP, true> only)
+  // the matrix-core kernels only (kf_gp_mfma.h pixel_innovation_mfma; both 0: the VALU launch)
+  int32_t gpm_frags;       // LDS fragments of all bands' split-f16 tables + the shared zero fragment
+  int32_t band_layout;     // BAND_LAYOUT_SHARED_X: one exponent operand per pixel group for every band
 };
 inline bool innovation_joint(const InnovationArgs& a) { return a.d2 || a.logdet; }
 inline bool innovation_args_ok(int np, const InnovationArgs& a) {
@@ -1724,6 +1727,52 @@ KF_HD bool joint_band_step(float (&C)[ntri(NP)], float (&delta)[NP], const float
     for (int j = i; j < NP; ++j) C[tri(NP, i, j)] = fmaf(-f, c[j], C[tri(NP, i, j)]);
   }
   return true;
+}
+
+// The band-independent tail of the check (pixel_innovation and the matrix-core
+// body kf_gp_mfma.h pixel_innovation_mfma): the decision masks -> rej, the
+// second pass over the bands that writes the screened planes, the final stores.
+template <bool JOINT>
+KF_HD void innovation_tail(const InnovationArgs& a, int64_t p, bool ok, bool jok, uint64_t counted, uint64_t over,
+                           uint64_t gbad, float chi2, float d2, float logdet) {
+  const float nan = __builtin_nanf("");
+  uint64_t rej = over;
+  if (a.scope == INNOV_SCOPE_GROUP && gbad) {
+    rej = 0;
+    for (int b = 0; b < a.nb; ++b) {
+      const int g = a.grp ? (cptr(a.grp)[b] & 63) : 0;
+      if ((gbad >> g) & 1u) rej |= 1ull << b;
+    }
+    rej &= counted;
+  }
+  if (a.screened) {
+    for (int b = 0; b < a.nb; ++b) {
+      void* out = cptr(a.screened)[b];
+      if (!out) continue;
+      const KF_CONST_AS BandDesc* bd = cptr(a.bands) + b;
+      const bool r = (rej >> b) & 1u;
+      const int obs = bd->obs;
+      if (obs == OBS_F32) {
+        const uint32_t v = reinterpret_cast<const uint32_t*>(bd->w)[p];
+        reinterpret_cast<uint32_t*>(out)[p] = r ? 0u : v;
+      } else if (obs == OBS_DN16) {
+        reinterpret_cast<uint16_t*>(out)[p] = r ? (uint16_t)0 : bd->dn[p];
+      } else if (obs == OBS_BF16) {
+        reinterpret_cast<uint16_t*>(out)[p] = r ? (uint16_t)0 : reinterpret_cast<const uint16_t*>(bd->w)[p];
+      } else if (obs == OBS_BF16Y) {
+        reinterpret_cast<uint16_t*>(out)[p] = r ? (uint16_t)0x7FC0 : reinterpret_cast<const uint16_t*>(bd->y)[p];
+      }
+    }
+  }
+  if constexpr (JOINT) {
+    jok = jok && ok;
+    if (a.d2) a.d2[p] = jok ? d2 : nan;
+    if (a.logdet) a.logdet[p] = jok ? logdet : nan;
+  }
+  if (a.chi2) a.chi2[p] = ok ? chi2 : nan;
+  if (a.nobs) a.nobs[p] = (uint8_t)__builtin_popcountll(counted);
+  if (a.nrej) a.nrej[p] = (uint8_t)__builtin_popcountll(rej);
+  a.status[p] = ok ? 0 : 1;
 }
 
 template <int NP, bool JOINT = false>
@@ -1808,43 +1857,7 @@ KF_HD void pixel_innovation(const InnovationArgs& a, int64_t p) {
     }
     if (a.z) a.z[b * a.ldz + p] = zb;
   }
-  uint64_t rej = over;
-  if (a.scope == INNOV_SCOPE_GROUP && gbad) {
-    rej = 0;
-    for (int b = 0; b < a.nb; ++b) {
-      const int g = a.grp ? (cptr(a.grp)[b] & 63) : 0;
-      if ((gbad >> g) & 1u) rej |= 1ull << b;
-    }
-    rej &= counted;
-  }
-  if (a.screened) {
-    for (int b = 0; b < a.nb; ++b) {
-      void* out = cptr(a.screened)[b];
-      if (!out) continue;
-      const KF_CONST_AS BandDesc* bd = cptr(a.bands) + b;
-      const bool r = (rej >> b) & 1u;
-      const int obs = bd->obs;
-      if (obs == OBS_F32) {
-        const uint32_t v = reinterpret_cast<const uint32_t*>(bd->w)[p];
-        reinterpret_cast<uint32_t*>(out)[p] = r ? 0u : v;
-      } else if (obs == OBS_DN16) {
-        reinterpret_cast<uint16_t*>(out)[p] = r ? (uint16_t)0 : bd->dn[p];
-      } else if (obs == OBS_BF16) {
-        reinterpret_cast<uint16_t*>(out)[p] = r ? (uint16_t)0 : reinterpret_cast<const uint16_t*>(bd->w)[p];
-      } else if (obs == OBS_BF16Y) {
-        reinterpret_cast<uint16_t*>(out)[p] = r ? (uint16_t)0x7FC0 : reinterpret_cast<const uint16_t*>(bd->y)[p];
-      }
-    }
-  }
-  if constexpr (JOINT) {
-    jok = jok && ok;
-    if (a.d2) a.d2[p] = jok ? d2 : nan;
-    if (a.logdet) a.logdet[p] = jok ? logdet : nan;
-  }
-  if (a.chi2) a.chi2[p] = ok ? chi2 : nan;
-  if (a.nobs) a.nobs[p] = (uint8_t)__builtin_popcountll(counted);
-  if (a.nrej) a.nrej[p] = (uint8_t)__builtin_popcountll(rej);
-  a.status[p] = ok ? 0 : 1;
+  innovation_tail<JOINT>(a, p, ok, jok, counted, over, gbad, chi2, d2, logdet);
 }
 // JOINT (innovation_joint): an instantiation of its own, so a launch without the
 // joint statistic runs at the plain body's register count

@@ -435,6 +435,47 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(const T* src, const int64
   }
 }
 
+// The innovation check with the GP bands on the matrix cores (kf_gp_mfma.h
+// pixel_innovation_mfma), opt-in beside pixel_kernel<NP, OpInnovation<JOINT>>.
+// InnovationArgs has no visiting order, so the walk is written out: each wave
+// takes 64 consecutive pixels, grid-stride; the tail lanes past N run on pixel
+// N - 1 with act = false (they take part in every MFMA, store and count nothing).
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class F>
+__device__ __forceinline__ void innovation_tiles(const InnovationArgs& a, F&& f) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * BLOCK;
+  for (int64_t base = (int64_t)blockIdx.x * BLOCK + (threadIdx.x - lane); base < a.N; base += stride) {
+    const int64_t q = base + lane;
+    const bool act = q < a.N;
+    f(act ? q : a.N - 1, act);
+  }
+}
+#endif
+
+// JRC-TIP (7 parameters, 4-input band GPs): the tables staged in LDS once per
+// workgroup (a.gpm_frags x 16 B of dynamic LDS), as gain_mfma_kernel.
+template <int NP, int D, bool JOINT>
+__global__ __launch_bounds__(BLOCK, 3) void innovation_mfma_kernel(InnovationArgs a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  extern __shared__ kf_h8 gpm_lds[];
+  stage_tables<BLOCK, D>(a, a.nb, gpm_lds);
+  innovation_tiles(a, [&](int64_t p, bool act) { pixel_innovation_mfma<NP, D, false, JOINT>(a, p, act, gpm_lds); });
+#endif
+}
+
+// PROSAIL and the multi-sensor state (10 parameters, full-state GPs): the
+// tables read from global memory through bd->gpm, no LDS tables.  2 waves per
+// SIMD by the launch bound, as gain_mfma_g_kernel: the JOINT body holds two
+// packed 55-float matrices per lane.
+template <int NP, int D, bool JOINT>
+__global__ __launch_bounds__(BLOCK, 2) void innovation_mfma_g_kernel(InnovationArgs a) {
+  static_assert(BLOCK / 64 == GPM_G_WAVES, "per-wave LDS transpose buffers of gp_mfma_sums_g_xb");
+#if defined(__HIP_DEVICE_COMPILE__)
+  innovation_tiles(a, [&](int64_t p, bool act) { pixel_innovation_mfma<NP, D, true, JOINT>(a, p, act, nullptr); });
+#endif
+}
+
 // ---------------------------------------------------------------------------
 // launchers
 inline int grid_for(int64_t N, int max_blocks) {
@@ -534,6 +575,13 @@ struct LaunchRow {
   KF_ROW(gain_mfma_g_kernel, 10, 10, OBS_DN16)      \
   KF_ROW(gain_mfma_g_kernel, 10, 10, OBS_F32)       \
   KF_ROW(gain_mfma_g_mixlo_kernel, 10, 10, OBS_DN16)
+
+// the innovation check on the matrix cores: a table of its own (kf_innovation_mfma.hip)
+#define KF_INNOV_ROWS                              \
+  KF_ROW(innovation_mfma_kernel, 7, 4, false)      \
+  KF_ROW(innovation_mfma_kernel, 7, 4, true)       \
+  KF_ROW(innovation_mfma_g_kernel, 10, 10, false)  \
+  KF_ROW(innovation_mfma_g_kernel, 10, 10, true)
 
 // Launch of the table's kernel for a plan, hipErrorInvalidValue where it has
 // none (PLAN_NONE included), on the static grid-stride mapping: norm partials

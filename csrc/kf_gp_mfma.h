@@ -1319,5 +1319,157 @@ __device__ __forceinline__ float pixel_gain_mfma(const GainArgs& a, int64_t p, b
     return use;
   });
 }
+
+// The innovation check (kf_core.h pixel_innovation) with every GP band's value
+// and Jacobian row on the matrix cores: lane = pixel, the per-lane prologue
+// (loads, class tests, chol_packed) and statistics are pixel_innovation's,
+// operation for operation; only H0 and h come from the wave-cooperative sums
+// instead of the VALU record loop.  Every lane of the wave runs the band loop
+// (act = false for the tail lanes past N: they store and count nothing); a band
+// no lane of the wave uses (no observation, or an unscreenable pixel) skips the
+// sums, so whole waves under cloud stay cheap.  A lane that does not use the
+// band feeds the band's centre (xi = 0, c = 0) into the wave's operands: its
+// column of the two GEMMs is its own and is discarded, and no NaN state reaches
+// the matrix cores.
+//
+// GT: the tables from global memory (bd->gpm).  With BAND_LAYOUT_SHARED_X
+// (InnovationArgs.band_layout) the check is the layout's best case -- every band
+// is evaluated at the one point x -- so the exponent operand is built once per
+// pixel group, before the band loop, and each band patches its constant in
+// (gpm_patch_c); the centred inputs are recomputed per band (the same
+// subtraction, ten registers fewer across the band loop, as pixel_gain_mfma).
+// !GT: the tables staged in LDS (stage_tables), the offset accumulated over the
+// bands, the shared zero fragment at gpm_frags - 1.
+template <int NP, int D, bool GT, bool JOINT>
+__device__ __forceinline__ void pixel_innovation_mfma(const InnovationArgs& a, int64_t p, bool act,
+                                                      const kf_h8* lds) {
+  constexpr int NT = ntri(NP);
+  KF_DCHECK(p >= 0 && p < a.N && a.N <= a.ld);
+  const int64_t ld = a.ld;
+  const float nan = __builtin_nanf("");
+  float x[NP], A[NT];
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    x[j] = a.x[j * ld + p];
+    ok = ok && finitef(x[j]);
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    A[t] = a.p[t * ld + p];
+    ok = ok && finitef(A[t]);
+  }
+  const bool cov = a.kind == MARG_COVARIANCE;
+  if (cov) {
+    float U[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) U[t] = A[t];
+    ok = chol_packed<NP>(U) && ok;
+  } else {
+    ok = chol_packed<NP>(A) && ok;
+  }
+  const float k = a.gate;
+  uint64_t counted = 0, over = 0, gbad = 0;
+  float chi2 = 0.f;
+  float C[JOINT ? NT : 1], delta[JOINT ? NP : 1], d2 = 0.f, logdet = 0.f;
+  bool jok = true;
+  if constexpr (JOINT) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      delta[i] = 0.f;
+#pragma unroll
+      for (int j = i; j < NP; ++j) C[tri(NP, i, j)] = cov ? A[tri(NP, i, j)] : (i == j ? 1.f : 0.f);
+    }
+  }
+  // the shared exponent operand of the whole date (BAND_LAYOUT_SHARED_X: every
+  // band has band 0's centre and the identity map); an unscreenable lane's
+  // column is built at the centre
+  constexpr bool SXC = GT && D == NP && D % 2 == 0;
+  bool sx = false;
+  kf_h8 sxb[2][gpm_k_steps(D)];
+  if constexpr (SXC) {
+    sx = a.band_layout == BAND_LAYOUT_SHARED_X && a.nb > 0 && __any(act && ok);
+    if (sx) {
+      const KF_CONST_AS BandDesc* b0 = cptr(a.bands);
+      float xi0[D], c0;
+#pragma unroll
+      for (int d = 0; d < D; ++d) xi0[d] = ok ? x[d] - b0->center[d] : 0.f;
+      gpm_operands<D>(xi0, 0.f, sxb, c0);
+    }
+  }
+  int off = 0;
+  for (int b = 0; b < a.nb; ++b) {
+    const KF_CONST_AS BandDesc* bdp = cptr(a.bands) + b;
+    float y, w, zb = nan;
+    decode_obs<0>(*bdp, p, y, w);
+    const bool use = act && ok && w > 0.f;
+    const int nch = bdp->gpm_nchunk;
+    // wave-uniform: a wave under cloud branches over the band's sums
+    if (__any(use)) {
+      float xi[D], c = 0.f;
+      gpm_inputs<NP, D>(bdp, x, xi, c);
+      if (!(SXC && sx ? ok : use)) {
+        // the band's centre: finite operands whatever the lane's state holds
+#pragma unroll
+        for (int d = 0; d < D; ++d) xi[d] = 0.f;
+        c = 0.f;
+      }
+      c *= -0.5f * LOG2E;
+      float S[D + 1];
+      if constexpr (GT) {
+        if (SXC && sx) gp_mfma_sums_g_sx<D, false, true, false>(bdp, nch, sxb, c, S);
+        else gp_mfma_sums_g<D, false, true, false>(bdp->gpm, nch, xi, c, S);
+      } else {
+        gp_mfma_sums<D, false, false>(lds + off, lds + a.gpm_frags - 1, nch, xi, c, S);
+      }
+      if (use) {
+        const KF_CONST_AS BandDesc* q = opaque(bdp);   // epilogue fields: not live across the chunk loop
+        const float sc = q->gpm_scale;
+        float Sd[D], H0, h[NP];
+#pragma unroll
+        for (int d = 0; d < D; ++d) Sd[d] = S[1 + d] * sc;
+        gpm_epilogue<NP, D>(q, xi, S[0] * sc, Sd, H0, h);
+        bool fin = finitef(H0);
+#pragma unroll
+        for (int j = 0; j < NP; ++j) fin = fin && finitef(h[j]);
+        if (fin) {
+          // pixel_innovation's statistics, in its order
+          float s;
+          [[maybe_unused]] float v[JOINT ? NP : 1];
+          if (cov) {
+            float ph[NP];
+            symv<NP>(A, h, ph);
+            s = 0.f;
+#pragma unroll
+            for (int j = 0; j < NP; ++j) s = fmaf(h[j], ph[j], s);
+            if constexpr (JOINT) {
+#pragma unroll
+              for (int j = 0; j < NP; ++j) v[j] = h[j];
+            }
+          } else {
+            if constexpr (JOINT) s = chol_fwd_solve<NP>(A, h, v);
+            else s = chol_fwd_norm2<NP>(A, h);
+          }
+          const float zz = (y - H0) * kf_rsqrt(s + kf_rcp(w));
+          if (finitef(zz)) {
+            zb = zz;
+            counted |= 1ull << b;
+            chi2 = fmaf(zz, zz, chi2);
+            if constexpr (JOINT) {
+              if (jok) jok = joint_band_step<NP>(C, delta, v, y - H0, kf_rcp(w), d2, logdet);
+            }
+            if (k > 0.f && fabsf(zz) > k) {
+              over |= 1ull << b;
+              gbad |= 1ull << (a.grp ? (cptr(a.grp)[b] & 63) : 0);
+            }
+          }
+        }
+      }
+    }
+    off += nch * gpm_frags_per_chunk(D);
+    if (act && a.z) a.z[b * a.ldz + p] = zb;
+  }
+  if (act) innovation_tail<JOINT>(a, p, ok, jok, counted, over, gbad, chi2, d2, logdet);
+}
 #endif
 }  // namespace kf

@@ -647,8 +647,11 @@ hipError_t dev_product(int np, const ProductArgs& a, hipStream_t s) {
 hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s) {
   return smooth_args_ok(np, a) ? launch_pixels<OpSmooth>(np, a, s) : hipErrorInvalidValue;
 }
-hipError_t dev_innovation(int np, const InnovationArgs& a, hipStream_t s) {
-  if (!innovation_args_ok(np, a)) return hipErrorInvalidValue;
+hipError_t dev_innovation(int np, const InnovationArgs& a, const KernelPlan& plan, hipStream_t s) {
+  if (!innovation_args_ok(np, a) || plan.np != np || plan.joint != innovation_joint(a)) return hipErrorInvalidValue;
+  if (plan.family == PLAN_INNOVATION_MFMA || plan.family == PLAN_INNOVATION_MFMA_G)   // kf_innovation_mfma.hip
+    return a.N > 0 ? dev_innovation_mfma(plan, a, dev_grid(a.N), s) : hipSuccess;
+  if (plan.family != PLAN_INNOVATION) return hipErrorInvalidValue;
   return innovation_joint(a) ? launch_pixels<OpInnovation<true>>(np, a, s) : launch_pixels<OpInnovation<false>>(np, a, s);
 }
 // the (np, d) pairs with a kernel: gp_operator_supported's list

@@ -53,7 +53,11 @@ hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s);
 hipError_t dev_marginal(int np, const RasterArgs& a, hipStream_t s);       // a.kind: MARG_*
 hipError_t dev_product(int np, const ProductArgs& a, hipStream_t s);       // physical-unit planes, interval, QA byte
 hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s);         // one backward step of the RTS smoother
-hipError_t dev_innovation(int np, const InnovationArgs& a, hipStream_t s); // statistics and the chi-square gate
+// statistics and the chi-square gate; plan: innovation_plan's kernel for a (kf_plan.h), the VALU pixel_kernel
+// or one of the matrix-core kernels of kf_innovation_mfma.hip
+hipError_t dev_innovation(int np, const InnovationArgs& a, const KernelPlan& plan, hipStream_t s);
+hipError_t dev_innovation_mfma(const KernelPlan& plan, const InnovationArgs& a, int grid, hipStream_t s);
+void launch_table_innovation(std::vector<KernelPlan>& out);
 hipError_t dev_reduce(const double* partials, int n, double* out, hipStream_t s);
 hipError_t dev_gather(int elem_bytes, const void* src, const int64_t* idx, void* dst, int64_t n, int rows,
                       int64_t src_ld, int64_t dst_ld, hipStream_t s);

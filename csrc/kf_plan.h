@@ -27,6 +27,9 @@ enum PlanFamily : int {
   PLAN_GAIN_MFMA_MIXLO,
   PLAN_GAIN_MFMA_G,
   PLAN_GAIN_MFMA_G_MIXLO,
+  PLAN_INNOVATION,           // pixel_kernel<NP, OpInnovation<JOINT>>: any bands, thread per pixel, the VALU record loop
+  PLAN_INNOVATION_MFMA,      // innovation_mfma_kernel: GP bands on the matrix cores, tables in LDS
+  PLAN_INNOVATION_MFMA_G,    // innovation_mfma_g_kernel: tables in global memory
 };
 
 constexpr int PLAN_BLOCK = 256;   // kf_device.h BLOCK: every K1 / K1g kernel's workgroup
@@ -40,12 +43,13 @@ struct KernelPlan {
   int spec = 0;
   bool mixlo = false, pf = false;
   int rows = 0, out = 0;
+  bool joint = false;   // the innovation kernels' JOINT instantiation (d2 / logdet)
 };
 
 constexpr bool operator==(const KernelPlan& x, const KernelPlan& y) {
   return x.family == y.family && x.np == y.np && x.fd == y.fd && x.obs == y.obs && x.bs == y.bs &&
          x.minw == y.minw && x.layout == y.layout && x.il == y.il && x.spec == y.spec && x.mixlo == y.mixlo &&
-         x.pf == y.pf && x.rows == y.rows && x.out == y.out;
+         x.pf == y.pf && x.rows == y.rows && x.out == y.out && x.joint == y.joint;
 }
 
 // plan_<kernel>(template arguments in the kernel's own order): what KF_ROW
@@ -85,10 +89,22 @@ constexpr KernelPlan plan_gain_mfma_g_mixlo_kernel(int np, int d, int obs) {
   return plan_gain(PLAN_GAIN_MFMA_G_MIXLO, np, d, obs, true);
 }
 
+// the innovation check (kf_core.h pixel_innovation): runtime observation decoding (obs 0) throughout
+constexpr KernelPlan plan_innovation(int family, int np, int d, bool joint) {
+  return {family, np, d, 0, PLAN_BLOCK, 0, 0, false, 0, false, false, 0, 0, joint};
+}
+constexpr KernelPlan plan_innovation_mfma_kernel(int np, int d, bool joint) {
+  return plan_innovation(PLAN_INNOVATION_MFMA, np, d, joint);
+}
+constexpr KernelPlan plan_innovation_mfma_g_kernel(int np, int d, bool joint) {
+  return plan_innovation(PLAN_INNOVATION_MFMA_G, np, d, joint);
+}
+
 // Kernels with the bands' tables in dynamic LDS (a.gpm_frags fragments of 16 B).
 constexpr bool plan_lds_tables(const KernelPlan& p) {
   return p.family == PLAN_ANALYSIS_MFMA || p.family == PLAN_ANALYSIS_MFMA_MIXLO ||
-         p.family == PLAN_ANALYSIS_TIP_SL || p.family == PLAN_GAIN_MFMA || p.family == PLAN_GAIN_MFMA_MIXLO;
+         p.family == PLAN_ANALYSIS_TIP_SL || p.family == PLAN_GAIN_MFMA || p.family == PLAN_GAIN_MFMA_MIXLO ||
+         p.family == PLAN_INNOVATION_MFMA;
 }
 
 // The plan's template-id as a demangler prints it for the kernel's symbol
@@ -114,6 +130,10 @@ inline std::string plan_name(const KernelPlan& p) {
     case PLAN_GAIN_MFMA_MIXLO: return "gain_mfma_mixlo_kernel<" + head + ">";
     case PLAN_GAIN_MFMA_G: return "gain_mfma_g_kernel<" + head + ">";
     case PLAN_GAIN_MFMA_G_MIXLO: return "gain_mfma_g_mixlo_kernel<" + head + ">";
+    case PLAN_INNOVATION: return "pixel_kernel<" + i(p.np) + ", kf::OpInnovation<" + b(p.joint) + "> >";
+    case PLAN_INNOVATION_MFMA: return "innovation_mfma_kernel<" + i(p.np) + ", " + i(p.fd) + ", " + b(p.joint) + ">";
+    case PLAN_INNOVATION_MFMA_G:
+      return "innovation_mfma_g_kernel<" + i(p.np) + ", " + i(p.fd) + ", " + b(p.joint) + ">";
     default: return "NONE";
   }
 }
@@ -262,6 +282,37 @@ inline KernelPlan gain_plan(int np, const GainArgs& a) {
   }
   if (a.split_mixlo && !p.mixlo) return KernelPlan{};   // as AV_MIXLO_SPLIT in analysis_plan
   return p;
+}
+
+// The kernel of an innovation launch.  hb: a host-readable copy of the a.nb
+// descriptors a.bands points to (a.bands itself is device memory on a device
+// launch; null: nothing is known about the bands, the VALU kernel).  want_mfma
+// false: the thread-per-pixel kernel whatever the bands are, today's launch.
+// The matrix-core kernels serve the two shipped GP states and nothing else:
+//   np = 7: every band OP_GP of 4 inputs with split-f16 fragments, the tables
+//     staged in LDS (a.gpm_frags fragments, the zero fragment included);
+//   np = 10: every band a full-state OP_GP (10 inputs, identity map) with
+//     fragments, read from global memory whether or not they would fit in LDS;
+//     a.band_layout (BAND_LAYOUT_SHARED_X) is the kernel's, not the plan's.
+// Mixed operators, SAR / linear / precomputed bands, other state sizes and a
+// table built without fragments take the VALU kernel.
+inline KernelPlan innovation_plan(int np, const InnovationArgs& a, bool want_mfma, const BandDesc* hb = nullptr) {
+  if (!plan_np(np)) return KernelPlan{};
+  const bool joint = innovation_joint(a);
+  const KernelPlan valu = plan_innovation(PLAN_INNOVATION, np, 0, joint);
+  if (!want_mfma || !hb || a.nb < 1 || (np != 7 && np != 10)) return valu;
+  const int d = np == 7 ? 4 : 10;
+  for (int b = 0; b < a.nb; ++b) {
+    if (hb[b].op != OP_GP || hb[b].d != d || hb[b].gpm_nchunk <= 0 || !hb[b].gpm) return valu;
+    if (np == 10 && !hb[b].map_identity) return valu;
+  }
+  if (np == 10) return plan_innovation_mfma_g_kernel(np, d, joint);
+  int frags = 1;
+  for (int b = 0; b < a.nb; ++b) frags += hb[b].gpm_nchunk * gpm_frags_per_chunk(d);
+  // the LDS image the kernel stages must be the one the host sized
+  // ... and fit the 160 KiB of a gfx950 CU
+  if (a.gpm_frags <= 0 || a.gpm_frags != frags || (int64_t)frags * 16 > 160 * 1024) return valu;
+  return plan_innovation_mfma_kernel(np, d, joint);
 }
 
 }  // namespace kf

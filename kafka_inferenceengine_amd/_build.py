@@ -38,8 +38,11 @@ HEADERS = ["kf_core.h", "kf_plan.h", "kf_launch.h", "kf_stream.h", "kf_device.h"
            "kf_deflate.h", "kf_inflate.h"]
 # device translation units (compiled concurrently: the NP = 7 / 10 analysis
 # instantiations dominate the build)
-HIP_SOURCES = ["kf_kernels.hip", "kf_analysis7.hip", "kf_analysis10.hip", "kf_gain10.hip", "kf_reg_tiled.hip", "kf_deflate.hip",
-               "kf_inflate.hip"]
+HIP_SOURCES = ["kf_kernels.hip", "kf_analysis7.hip", "kf_analysis10.hip", "kf_gain10.hip", "kf_innovation_mfma.hip",
+               "kf_reg_tiled.hip", "kf_deflate.hip", "kf_inflate.hip"]
+# per-unit device flags: the innovation unit is built with the packed f32 VALU
+# operations (v_pk_add/mul/fma_f32) off, so its per-lane statistics stay scalar FMAs
+HIP_EXTRA_FLAGS = {"kf_innovation_mfma.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _pybind_includes() -> list[str]:
@@ -113,7 +116,7 @@ def build(force: bool = False, verbose: bool = False, checked: bool = False, pro
             # (kf_gp_mfma.h:gpm_exp_split) instead of conversions + v_pk_fma_f32; only the
             # rounding of a pair's residuals is packed (v_cvt_pk_f16_f32, written as a vector)
             jobs.append([hipcc, f"--offload-arch={ARCH}", *common, "-munsafe-fp-atomics", "-fno-slp-vectorize", "-mllvm",
-                         "-amdgpu-mfma-vgpr-form", "-c", str(src), "-o", str(obj)])
+                         "-amdgpu-mfma-vgpr-form", *HIP_EXTRA_FLAGS.get(name, []), "-c", str(src), "-o", str(obj)])
         objs.append(obj)
 
     # 2. host runner of the same per-pixel code (g++, OpenMP)

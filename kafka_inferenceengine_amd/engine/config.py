@@ -128,6 +128,13 @@ class EngineConfig:
     # marginal likelihood, the quantity to maximise over Q.  With a gate it costs
     # a second launch (a second operator evaluation) on the screened bands
     innovation_evidence: bool = False
+    # innovation_gp: how the check evaluates GP bands.  'valu': the thread-per-pixel
+    # record loop (any bands).  'mfma': on the matrix cores where the date's band
+    # table allows it (JRC-TIP, 10-parameter full-state GPs, on a device;
+    # ops.kernels.innovation_mfma_supported) and the VALU kernel otherwise -- a
+    # date with a SAR band, the host runner.  z differs from 'valu' by the rounding
+    # of the GP sums, so a decision within that of the gate may differ
+    innovation_gp: str = "valu"               # 'valu' | 'mfma'
     metrics_path: str | None = None           # JSONL metrics (per date / timestep)
     checkpoint_dir: str | None = None
     checkpoint_every: int = 0                 # timesteps between checkpoints (0: off)
@@ -160,6 +167,8 @@ class EngineConfig:
             raise ValueError("innovation_gate must be a finite number >= 0 (0: no gate)")
         if self.innovation_scope not in ("group", "band"):
             raise ValueError("innovation_scope must be 'group' or 'band'")
+        if self.innovation_gp not in ("valu", "mfma"):
+            raise ValueError("innovation_gp must be 'valu' or 'mfma'")
         if self.store_precision not in ("auto", "always"):
             raise ValueError("store_precision must be 'auto' or 'always'")
         if isinstance(self.convergence_chunk, str) and self.convergence_chunk.strip().lower() in ("", "0", "tile",

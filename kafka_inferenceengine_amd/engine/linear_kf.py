@@ -688,6 +688,12 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                              "(reference-protocol) observation operator has none before the analysis")
         return self._band_table(bands, specs, [d for _, d in bands])
 
+    def _innovation_gp(self, table) -> str:
+        """config.innovation_gp where the date's table and the device allow it, else the VALU kernel."""
+        if self.config.innovation_gp == "mfma" and K.innovation_mfma_supported(self.n_params, table, self.device):
+            return "mfma"
+        return "valu"
+
     def _screen_date(self, timestep, bands, forecast):
         """Innovation statistics of one date against the forecast its analysis
         starts from (config.innovation_gate / innovation_stats /
@@ -739,7 +745,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                 K.innovation(n, table, fc.x, fc.P, kind=fc.kind, N=N, chi2=buf["chi2"], nobs=buf["nobs"],
                              nrej=buf["nrej"], status=buf["status"], gate=cfg.innovation_gate,
                              scope=cfg.innovation_scope, groups=self._band_groups(timestep, len(specs)),
-                             screened=screened, **first)
+                             screened=screened, gp=self._innovation_gp(table), **first)
         self.last_innovation = {"chi2": buf["chi2"][:N], "nobs": buf["nobs"][:N], "nrej": buf["nrej"][:N],
                                 "status": buf["status"][:N]}
         if not gated:
@@ -753,8 +759,10 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         if joint:
             if N:
                 with self.timer.phase("innovation"):
-                    K.innovation(n, self._innovation_table(specs, run_bands), fc.x, fc.P, kind=fc.kind, N=N,
-                                 nobs=buf["nobs_kept"], status=buf["status_kept"], d2=buf["d2"], logdet=buf["logdet"])
+                    kept = self._innovation_table(specs, run_bands)
+                    K.innovation(n, kept, fc.x, fc.P, kind=fc.kind, N=N, nobs=buf["nobs_kept"],
+                                 status=buf["status_kept"], d2=buf["d2"], logdet=buf["logdet"],
+                                 gp=self._innovation_gp(kept))
             self._add_evidence(buf["d2"], buf["logdet"], buf["nobs_kept"])
         return fc, run_bands
 
@@ -843,7 +851,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             out.update({key: torch.zeros(max(N, 1), dtype=torch.float32, device=dev) for key in ("d2", "logdet")})
         if N:
             K.innovation(self.n_params, table, st.x, st.P, kind=st.kind, N=N, gate=gate, scope=scope,
-                         groups=self._band_groups(timestep, len(specs)), **out)
+                         groups=self._band_groups(timestep, len(specs)), gp=self._innovation_gp(table), **out)
         return {key: v[..., :N] for key, v in out.items()}
 
     def _health_metrics(self, wall_s: float) -> dict:

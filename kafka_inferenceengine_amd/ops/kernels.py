@@ -1689,8 +1689,58 @@ def _screened_dtype(obs):
     return torch.float32 if obs == OBS_F32 else torch.int16
 
 
+INNOVATION_GP = ("valu", "mfma")
+# the kernel the last innovation() launch on a device took (ext().innovation_plan: name, family, template arguments)
+LAST_INNOVATION_PLAN = None
+
+
+def _innovation_mfma_fields(n_params, bands: BandTable):
+    """(gpm_frags, band_layout) of a matrix-core launch of the check over ``bands``, from the
+    table as ``gain`` reads it: PER_BAND_OPERAND rebuilds the exponent operand per band."""
+    frags = 0
+    if n_params == 7 and bands.fast_d == 4:
+        frags = int(bands.gpm_frags)
+    layout = 0
+    if n_params == 10 and bands.fast_d == 10 and DEFAULT_VARIANT != Variant.PER_BAND_OPERAND:
+        # make_band_table's BAND_LAYOUT_SHARED_X test without its "too large for LDS": the check reads
+        # the tables from global memory whatever their size (once per table)
+        sx = getattr(bands, "_innov_sx", None)
+        if sx is None:
+            sx = bands._innov_sx = bool(bands.descs) and all(d.map_identity for d in bands.descs) and \
+                len({tuple(d.center[:10]) for d in bands.descs}) == 1
+        layout = BAND_LAYOUT_SHARED_X if sx else 0
+    return frags, layout
+
+
+def innovation_plan(n_params, bands: BandTable, joint=False, gp="mfma"):
+    """The kernel a device launch of :func:`innovation` over ``bands`` takes (kf_plan.h
+    ``innovation_plan``); no device needed.  ``Variant.VALU_ORACLE`` plans the VALU kernel."""
+    want = gp == "mfma" and DEFAULT_VARIANT != Variant.VALU_ORACLE and len(bands.descs) == bands.n
+    frags, layout = _innovation_mfma_fields(n_params, bands)
+    return ext().innovation_plan(int(n_params), list(bands.descs) if want else [], frags, layout, bool(joint), want)
+
+
+def innovation_mfma_unsupported(n_params, bands: BandTable, device):
+    """Why ``innovation(gp="mfma")`` cannot serve this table on this device, or None where it can."""
+    if torch.device(device).type != "cuda":
+        return "the matrix-core innovation kernels have no host twin (device tensors only)"
+    if n_params not in SUPPORTED_NP:
+        return f"n_params={n_params} has no compiled kernel"
+    if DEFAULT_VARIANT == Variant.VALU_ORACLE:
+        return None      # the oracle switch: the VALU kernel stands in, as for gain
+    if not innovation_plan(n_params, bands)["family"].startswith("innovation_mfma"):
+        return (f"no matrix-core innovation kernel for {bands.n} band(s) of a {n_params}-parameter state: it takes "
+                "7 parameters with 4-input GP bands whose tables fit in LDS, or 10 parameters with full-state GP "
+                "bands, every band with matrix-core fragments")
+    return None
+
+
+def innovation_mfma_supported(n_params, bands: BandTable, device) -> bool:
+    return innovation_mfma_unsupported(n_params, bands, device) is None
+
+
 def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=None, nobs=None, nrej=None, status,
-               gate=0.0, scope="group", groups=None, screened=None, d2=None, logdet=None):
+               gate=0.0, scope="group", groups=None, screened=None, d2=None, logdet=None, gp="valu"):
     """Innovation statistics and the chi-square gate, per pixel (csrc/kf_core.h
     ``pixel_innovation``).  ``x`` [n_p, ld] and ``p`` [ntri, ld] (packed rows of
     P^-1 for ``kind="precision"``, of P for ``"covariance"``) are the state the
@@ -1722,8 +1772,25 @@ def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=N
     ``gate`` k > 0 rejects band b where |z_b| > k (``scope="band"``) or every
     counted band of a group in which any band exceeds k (``scope="group"``,
     ``groups``: one id in 0..63 per band, None: one group).  gate = 0:
-    statistics only."""
+    statistics only.
+
+    ``gp="mfma"`` evaluates the GP bands on the matrix cores (kf_gp_mfma.h
+    ``pixel_innovation_mfma``) instead of the thread-per-pixel VALU record loop:
+    the JRC-TIP and the 10-parameter full-state GP tables on a device, and a
+    ValueError with the reason for anything else
+    (:func:`innovation_mfma_supported` asks without raising).  The statistics are
+    the same operations on the operator's value and Jacobian row, which differ
+    from the VALU loop's by the rounding of the GP sums.  ``Variant.VALU_ORACLE``
+    launches the VALU kernel, ``Variant.PER_BAND_OPERAND`` rebuilds the shared
+    exponent operand per band, as for :func:`gain`.  The kernel taken is
+    recorded in ``LAST_INNOVATION_PLAN``."""
     check_np(n_params)
+    if gp not in INNOVATION_GP:
+        raise ValueError("gp must be 'valu' or 'mfma'")
+    if gp == "mfma":
+        why = innovation_mfma_unsupported(n_params, bands, x.device)
+        if why is not None:
+            raise ValueError(f"innovation(gp='mfma'): {why}")
     if kind not in MARGINAL_KINDS:
         raise ValueError("kind must be 'precision' or 'covariance'")
     if scope not in INNOVATION_SCOPES:
@@ -1781,10 +1848,16 @@ def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=N
                 _SCREENED_PTRS.clear()
             ptrs = _SCREENED_PTRS[key] = small_h2d(torch.tensor(key[1:] or (0,), dtype=torch.int64), dev)
     e = ext()
+    global LAST_INNOVATION_PLAN
+    joint = d2 is not None or logdet is not None
+    want = gp == "mfma" and DEFAULT_VARIANT != Variant.VALU_ORACLE
+    frags, layout = _innovation_mfma_fields(n_params, bands) if want else (0, 0)
+    LAST_INNOVATION_PLAN = innovation_plan(n_params, bands, joint, gp) if _dev(x) else None
     e.innovation(n_params, _ptr(x), _ptr(p), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION,
                  bands.ptr, nb, _ptr(grp), gate, e.INNOV_SCOPE_BAND if scope == "band" else e.INNOV_SCOPE_GROUP,
                  _ptr(z), 0 if z is None else z.shape[1], _ptr(chi2), _ptr(nobs), _ptr(nrej), _ptr(status),
-                 _ptr(ptrs), N, ld, _dev(x), _stream(x), _ptr(d2), _ptr(logdet))
+                 _ptr(ptrs), N, ld, _dev(x), _stream(x), _ptr(d2), _ptr(logdet), want,
+                 list(bands.descs) if want else [], frags, layout)
 
 
 def reduce_partials(partials: torch.Tensor, out: torch.Tensor | None = None):

@@ -10,7 +10,8 @@ started on the device).  One JSON line per record, also appended to ``--record``
 ``innovation_kernel`` alone on the first date of ``bench.py``'s tip7 and
 prosail10 workloads (the sources, emulators and prior of the benchmark, the
 prior as the state): statistics only, and with a gate writing the screened
-planes.  The kernel evaluates the GP bands with the VALU record loop.
+planes.  Every variant is timed with the VALU kernel and then, where the table
+has one, with the matrix-core kernel (``gp="mfma"``; the record's ``gp`` / ``plan``).
 ``joint``: the joint instantiation (``innovation_joint_kernel``: the statistics
 plus d2 = r^T S^-1 r and log det S); ``joint_kept``: the second launch of a
 gated date under ``innovation_evidence`` (gate 0 on the screened bands, writing
@@ -18,9 +19,10 @@ status, nobs, d2 and logdet only).
 
     python scripts/bench_innovation.py kernels --configs tip7 prosail10 --size 10980
 
-``e2e``: ``bench.py --config C`` four ways -- default, ``--set
+``e2e``: ``bench.py --config C`` five ways (``--only`` picks some) -- default, ``--set
 fuse_propagation=false`` (the unfused path a screened date also takes), ``--set
-innovation_stats=true`` and ``--set innovation_gate=K`` -- ``--rounds`` times in
+innovation_stats=true``, ``--set innovation_gate=K`` and the latter with ``--set
+innovation_gp=mfma`` -- ``--rounds`` times in
 that order, with the ms/step of every run and the ratios of the means.
 
     python scripts/bench_innovation.py e2e --configs tip7 prosail10
@@ -38,7 +40,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 VARIANTS = (("default", []), ("unfused", ["--set", "fuse_propagation=false"]),
-            ("stats", ["--set", "innovation_stats=true"]), ("gated", None))
+            ("stats", ["--set", "innovation_stats=true"]), ("gated", None), ("gated_mfma", None))
 
 
 def emit(rec, record):
@@ -117,22 +119,28 @@ def one_kernel_config(config, size, reps, gate, device=None):
     # the screened bands of the gated launch: what the second launch of a gated date reads
     kept = [(s, dataclasses.replace(db, **{kf._nodata_plane(db): t})) for (s, db), t in zip(bands, screened)]
     out = []
-    for name, kw in (("stats", dict(gate=0.0)), ("gated", dict(gate=gate, screened=screened)),
-                     ("joint", dict(gate=0.0, d2=d2, logdet=logdet)), ("joint_kept", None)):
+    # every variant with the VALU kernel, then (where the table has one) with the matrix-core kernel
+    gps = ["valu"] + (["mfma"] if K.innovation_mfma_supported(n, table, dev) else [])
+    for name, kw, gp in ((nm, kw, gp) for nm, kw in (("stats", dict(gate=0.0)),
+                                                     ("gated", dict(gate=gate, screened=screened)),
+                                                     ("joint", dict(gate=0.0, d2=d2, logdet=logdet)),
+                                                     ("joint_kept", None)) for gp in gps):
         if kw is None:
             table2 = kf._innovation_table(specs, kept)
             kw = dict(gate=0.0)
             med, lo, hi = timed(lambda: K.innovation(n, table2, st.x, st.P, kind=st.kind, N=N, nobs=nobs,
-                                                     status=status, d2=d2, logdet=logdet))
+                                                     status=status, d2=d2, logdet=logdet, gp=gp))
         else:
             med, lo, hi = timed(lambda: K.innovation(n, table, st.x, st.P, kind=st.kind, N=N, chi2=chi2, nobs=nobs,
-                                                     nrej=nrej, status=status, groups=groups, **kw))
+                                                     nrej=nrej, status=status, groups=groups, gp=gp, **kw))
         seen = int(nobs.sum(dtype=torch.int64).item())
         fin = torch.isfinite(d2)
         joint = {} if name in ("stats", "gated") else {
             "d2_per_obs": round(float(torch.where(fin, d2, torch.zeros_like(d2)).sum(dtype=torch.float64).item())
                                 / max(seen, 1), 4), "joint_nan": int((~fin).sum().item())}
-        out.append({"bench": "kernel", "kernel": f"innovation_kernel/{name}", **joint, "config": config, "size": size,
+        plan = K.LAST_INNOVATION_PLAN["name"] if K.LAST_INNOVATION_PLAN else "host runner"
+        out.append({"bench": "kernel", "kernel": f"innovation_kernel/{name}", "gp": gp, "plan": plan, **joint,
+                    "config": config, "size": size,
                     "device": dev.type, "n_params": n, "n_bands": len(bands), "kind": st.kind, "gate": kw["gate"],
                     "ms_median": round(med, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4), "reps": reps,
                     "observed_bands": seen, "rejected_bands": int(nrej.sum(dtype=torch.int64).item()),
@@ -158,7 +166,11 @@ def e2e(a):
         runs = {name: [] for name, _ in VARIANTS}
         for _ in range(a.rounds):
             for name, extra in VARIANTS:
-                extra = ["--set", f"innovation_gate={a.gate}"] if extra is None else extra
+                if extra is None:      # gated, with the VALU check or (gated_mfma) the matrix-core one
+                    extra = ["--set", f"innovation_gate={a.gate}"] + \
+                        (["--set", "innovation_gp=mfma"] if name == "gated_mfma" else [])
+                if a.only and name not in a.only:
+                    continue
                 cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", config, "--steps",
                        str(a.steps), "--warmup", str(a.warmup), "--no-telemetry"] + extra
                 if a.size:
@@ -167,12 +179,13 @@ def e2e(a):
                 runs[name].append(rec["ms_per_step"])
                 if not rec["config"]["finite"]:
                     raise SystemExit(f"e2e {config} {name}: state not finite; stopping")
-        mean = {name: statistics.fmean(v) for name, v in runs.items()}
+        mean = {name: statistics.fmean(v) for name, v in runs.items() if v}
+        ratios = {f"{p}_over_{q}": round(mean[p] / mean[q], 3)
+                  for p, q in (("gated", "default"), ("gated", "unfused"), ("stats", "unfused"),
+                               ("gated_mfma", "default"), ("gated_mfma", "gated")) if p in mean and q in mean}
         emit({"bench": "e2e", "config": config, "size": a.size, "steps": a.steps, "warmup": a.warmup, "gate": a.gate,
-              "ms_per_step": runs, "mean_ms_per_step": {name: round(v, 3) for name, v in mean.items()},
-              "gated_over_default": round(mean["gated"] / mean["default"], 3),
-              "gated_over_unfused": round(mean["gated"] / mean["unfused"], 3),
-              "stats_over_unfused": round(mean["stats"] / mean["unfused"], 3)}, a.record)
+              "ms_per_step": runs, "mean_ms_per_step": {name: round(v, 3) for name, v in mean.items()}, **ratios},
+             a.record)
 
 
 def main():
@@ -185,6 +198,8 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=2, help="e2e: times the four runs are repeated")
+    ap.add_argument("--only", nargs="+", default=None, choices=[v[0] for v in VARIANTS],
+                    help="e2e: run these variants only (default: all five)")
     ap.add_argument("--limit", type=int, default=300, help="seconds each GPU step may take")
     ap.add_argument("--device", default=None, choices=["cpu"], help="kernels: dry run on the host runner")
     ap.add_argument("--record", default=None, help="append the JSON lines to this file")
