@@ -518,10 +518,16 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
                          double gate, int scope, uintptr_t z, int64_t ldz, uintptr_t chi2, uintptr_t nobs,
                          uintptr_t nrej, uintptr_t status, uintptr_t screened, int64_t N, int64_t ld, bool device,
                          uintptr_t stream, uintptr_t d2, uintptr_t logdet, bool want_mfma,
-                         const std::vector<BandDesc>& host_bands, int gpm_frags, int band_layout) {
+                         const std::vector<BandDesc>& host_bands, int gpm_frags, int band_layout, uintptr_t prop,
+                         uintptr_t line_tab, float line_t0, float line_inv_h, int line_n, int line_j) {
     // want_mfma with host_bands (host copies of the nb descriptors), gpm_frags and band_layout as the band
-    // table has them: the matrix-core kernel where innovation_plan has one (kf_plan.h), device launches only
+    // table has them: the matrix-core kernel where innovation_plan has one (kf_plan.h), device launches only.
+    // prop: the device copy of the PropArgs of a fused forecast (x / p: the previous analysis), with the
+    // line-table fields of that forecast (line_tab 0: none); a launch innovation_plan has no kernel for raises
     InnovationArgs a{};
+    a.prop = P<const PropArgs>(prop);
+    a.line_tab = P<const float>(line_tab);
+    a.line_t0 = line_t0, a.line_inv_h = line_inv_h, a.line_n = line_n, a.line_j = line_j;
     a.gpm_frags = gpm_frags;
     a.band_layout = band_layout;
     a.d2 = P<float>(d2);           // joint statistic [N] (either one selects the joint instantiation)
@@ -554,20 +560,33 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
   // the kernel a device launch of the innovation check takes (kf_plan.h innovation_plan); no device needed.
   // bands: host descriptors; joint: d2 or logdet asked for.  innovation_table: the matrix-core kernels' names
   m.def("innovation_plan", [](int np, const std::vector<BandDesc>& bands, int gpm_frags, int band_layout, bool joint,
-                              bool want_mfma) {
+                              bool want_mfma, bool prop, int kind) {
+    // prop: the launch carries a fused forecast (InnovationArgs.prop), with p of `kind`
     InnovationArgs a{};
     a.nb = (int)bands.size();
     a.gpm_frags = gpm_frags;
     a.band_layout = band_layout;
+    a.kind = kind;
     static float joint_out;
+    static const PropArgs prop_set{};
     if (joint) a.d2 = &joint_out;   // innovation_joint: either output asked for (never written here)
+    if (prop) a.prop = &prop_set;   // tested for null only
     py::dict d = plan_dict(innovation_plan(np, a, want_mfma, bands.data()));
-    d["band_layout"] = d["family"].cast<std::string>() == "innovation_mfma_g_kernel" ? band_layout : 0;
+    const std::string family = d["family"].cast<std::string>();
+    d["band_layout"] = family == "innovation_mfma_g_kernel" || family == "innovation_prop_g_kernel" ? band_layout : 0;
     return d;
-  });
+  }, py::arg("np"), py::arg("bands"), py::arg("gpm_frags"), py::arg("band_layout"), py::arg("joint"),
+     py::arg("want_mfma"), py::arg("prop") = false, py::arg("kind") = (int)MARG_PRECISION);
   m.def("innovation_table", []() {
     std::vector<KernelPlan> plans;
     launch_table_innovation(plans);
+    std::vector<std::string> names;
+    for (const KernelPlan& p : plans) names.push_back(plan_name(p));
+    return names;
+  });
+  m.def("innovation_prop_table", []() {
+    std::vector<KernelPlan> plans;
+    launch_table_innovation_prop(plans);
     std::vector<std::string> names;
     for (const KernelPlan& p : plans) names.push_back(plan_name(p));
     return names;

@@ -1661,11 +1661,19 @@ struct InnovationArgs {
   // the matrix-core kernels only (kf_gp_mfma.h pixel_innovation_mfma; both 0: the VALU launch)
   int32_t gpm_frags;       // LDS fragments of all bands' split-f16 tables + the shared zero fragment
   int32_t band_layout;     // BAND_LAYOUT_SHARED_X: one exponent operand per pixel group for every band
+  // the fused-forecast kernels only (kf_gp_mfma.h pixel_innovation_prop; prop null: every other launch).
+  // x / p are then the previous analysis (prop->x_a / p_a) and the check runs at the partial-reset
+  // forecast the kernel forms per pixel (forecast_partial), precision rows only
+  const PropArgs* prop;
+  const float* line_tab;   // the bands' line tables at that forecast (AnalysisArgs' fields; null: the GP sums)
+  float line_t0, line_inv_h;
+  int32_t line_n, line_j;
 };
 inline bool innovation_joint(const InnovationArgs& a) { return a.d2 || a.logdet; }
 inline bool innovation_args_ok(int np, const InnovationArgs& a) {
   if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return false;
   if (a.scope != INNOV_SCOPE_BAND && a.scope != INNOV_SCOPE_GROUP) return false;
+  if (a.prop && a.kind != MARG_PRECISION) return false;
   if (a.N < 0 || a.N > a.ld || np < 1 || np > MAX_D || a.nb < 0 || a.nb > INNOV_MAX_BANDS) return false;
   if (!(a.gate >= 0.f) || !finitef(a.gate) || (a.z && a.ldz < a.N) || (a.nb > 0 && !a.bands)) return false;
   return a.x && a.p && a.status;

@@ -476,6 +476,28 @@ __global__ __launch_bounds__(BLOCK, 2) void innovation_mfma_g_kernel(InnovationA
 #endif
 }
 
+// The check at the fused forecast (kf_gp_mfma.h pixel_innovation_prop): the two
+// kernels above with the forecast formed per lane from InnovationArgs.prop and
+// the bands' line tables where the launch carries them.  Same walk, same LDS
+// image and the same launch bounds: the body holds the factor and, JOINT, the
+// recursion's matrix across the band loop exactly as pixel_innovation_mfma does.
+template <int NP, int D, bool JOINT>
+__global__ __launch_bounds__(BLOCK, 3) void innovation_prop_kernel(InnovationArgs a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  extern __shared__ kf_h8 gpm_lds[];
+  stage_tables<BLOCK, D>(a, a.nb, gpm_lds);
+  innovation_tiles(a, [&](int64_t p, bool act) { pixel_innovation_prop<NP, D, false, JOINT>(a, p, act, gpm_lds); });
+#endif
+}
+
+template <int NP, int D, bool JOINT>
+__global__ __launch_bounds__(BLOCK, 2) void innovation_prop_g_kernel(InnovationArgs a) {
+  static_assert(BLOCK / 64 == GPM_G_WAVES, "per-wave LDS transpose buffers of gp_mfma_sums_g_xb");
+#if defined(__HIP_DEVICE_COMPILE__)
+  innovation_tiles(a, [&](int64_t p, bool act) { pixel_innovation_prop<NP, D, true, JOINT>(a, p, act, nullptr); });
+#endif
+}
+
 // ---------------------------------------------------------------------------
 // launchers
 inline int grid_for(int64_t N, int max_blocks) {
@@ -582,6 +604,12 @@ struct LaunchRow {
   KF_ROW(innovation_mfma_kernel, 7, 4, true)       \
   KF_ROW(innovation_mfma_g_kernel, 10, 10, false)  \
   KF_ROW(innovation_mfma_g_kernel, 10, 10, true)
+// ... at the fused forecast (InnovationArgs.prop): a second table of the same unit
+#define KF_INNOV_PROP_ROWS                         \
+  KF_ROW(innovation_prop_kernel, 7, 4, false)      \
+  KF_ROW(innovation_prop_kernel, 7, 4, true)       \
+  KF_ROW(innovation_prop_g_kernel, 10, 10, false)  \
+  KF_ROW(innovation_prop_g_kernel, 10, 10, true)
 
 // Launch of the table's kernel for a plan, hipErrorInvalidValue where it has
 // none (PLAN_NONE included), on the static grid-stride mapping: norm partials

@@ -1471,5 +1471,155 @@ __device__ __forceinline__ void pixel_innovation_mfma(const InnovationArgs& a, i
   }
   if (act) innovation_tail<JOINT>(a, p, ok, jok, counted, over, gbad, chi2, d2, logdet);
 }
+
+// The check at the fused forecast: pixel_innovation_mfma with the forecast
+// formed in registers from the previous analysis (InnovationArgs.prop:
+// forecast_partial, the rows pixel_analysis_mfma reads and no others, so the
+// forecast is never written to memory and the date's analysis keeps its fused
+// launch) and, where the launch carries line tables, every band's value and
+// input gradient from the cubics the analysis' first iteration reads at that
+// same point (line_pos / line_eval).  The choice is the wave's: the cubics
+// when every lane that uses the band lies inside the table, the matrix-core
+// sums of pixel_innovation_mfma otherwise, so a wave that falls back computes
+// that kernel's bits at the same forecast.
+//
+// Data movement: the forecast precision is PropArgs.reset_cinv (scalar loads,
+// one constant matrix per launch) with the propagated diagonals patched per
+// lane, factored once per pixel group and held across the band loop, as the
+// table interval (row pointer, s) is: it depends on the state alone.  The
+// launch-uniform line fields and the descriptor's epilogue fields are re-read
+// through opaque pointers so they hold no SGPRs across the chunk loop.  The
+// shared exponent operand of BAND_LAYOUT_SHARED_X is built by the first band
+// whose wave needs the sums: a wave served by the tables never forms it.
+// A lane whose forecast fails forecast_partial_spd or the class tests is
+// unscreenable as in pixel_innovation (status 1, NaN, nothing rejected).
+template <int NP, int D, bool GT, bool JOINT>
+__device__ __forceinline__ void pixel_innovation_prop(const InnovationArgs& a, int64_t p, bool act,
+                                                      const kf_h8* lds) {
+  constexpr int NT = ntri(NP);
+  KF_DCHECK(p >= 0 && p < a.N && a.N <= a.ld);
+  const float nan = __builtin_nanf("");
+  float x[NP], A[NT];
+  bool ok;
+  {
+    const KF_CONST_AS PropArgs* pa = opaque(cptr(a.prop));
+    forecast_partial<NP>(pa, p, x, A);
+    ok = forecast_partial_spd<NP>(pa, A);
+  }
+#pragma unroll
+  for (int j = 0; j < NP; ++j) ok = ok && finitef(x[j]);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) ok = ok && finitef(A[t]);
+  // the lane's table interval, the same for every band
+  const KF_CONST_AS InnovationArgs* ka =
+      opaque((const KF_CONST_AS InnovationArgs*)__builtin_amdgcn_kernarg_segment_ptr());
+  const bool line = ka->line_tab != nullptr;
+  LinePos lp{nullptr, 0.f, false};
+  // (a lane whose forecast is not ok may hold NaN here: line_pos clamps it to row 0 with in = false, and since
+  // such a lane never uses a band it evaluates that row's cubics below and discards them, as the analysis does)
+  if (line) lp = line_pos<NP>(ka, x, a.nb * (D + 1) * 4);
+  // pixel_innovation's factor of the precision, dense (the outputs' bits are the materialised check's)
+  ok = chol_packed<NP>(A) && ok;
+  const float k = a.gate;
+  uint64_t counted = 0, over = 0, gbad = 0;
+  float chi2 = 0.f;
+  float C[JOINT ? NT : 1], delta[JOINT ? NP : 1], d2 = 0.f, logdet = 0.f;
+  bool jok = true;
+  if constexpr (JOINT) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      delta[i] = 0.f;
+#pragma unroll
+      for (int j = i; j < NP; ++j) C[tri(NP, i, j)] = i == j ? 1.f : 0.f;
+    }
+  }
+  constexpr bool SXC = GT && D == NP && D % 2 == 0;
+  const bool sx = SXC && a.band_layout == BAND_LAYOUT_SHARED_X;
+  bool sx_built = false;   // wave-uniform
+  kf_h8 sxb[2][gpm_k_steps(D)];
+  int off = 0;
+  for (int b = 0; b < a.nb; ++b) {
+    const KF_CONST_AS BandDesc* bdp = cptr(a.bands) + b;
+    float y, w, zb = nan;
+    decode_obs<0>(*bdp, p, y, w);
+    const bool use = act && ok && w > 0.f;
+    const int nch = bdp->gpm_nchunk;
+    // wave-uniform: a wave under cloud branches over the band
+    if (__any(use)) {
+      float H0 = 0.f, h[NP];
+      bool fin;
+      if (line && __all(lp.in || !use)) {
+        float g[D];
+        line_eval<D>(lp.row + b * (D + 1) * 4, lp.s, H0, g);
+        fin = finitef(H0);
+#pragma unroll
+        for (int d = 0; d < D; ++d) fin = fin && finitef(g[d]);
+#pragma unroll
+        for (int j = 0; j < NP; ++j) h[j] = 0.f;
+        gpm_scatter<NP, D>(opaque(bdp), g, h);
+      } else {
+        // pixel_innovation_mfma's sums and epilogue, operation for operation
+        if constexpr (SXC) {
+          if (sx && !sx_built) {
+            const KF_CONST_AS BandDesc* b0 = cptr(a.bands);
+            float xi0[D], c0;
+#pragma unroll
+            for (int d = 0; d < D; ++d) xi0[d] = ok ? x[d] - b0->center[d] : 0.f;
+            gpm_operands<D>(xi0, 0.f, sxb, c0);
+            sx_built = true;
+          }
+        }
+        float xi[D], c = 0.f;
+        gpm_inputs<NP, D>(bdp, x, xi, c);
+        if (!(sx ? ok : use)) {
+          // the band's centre: finite operands whatever the lane's state holds
+#pragma unroll
+          for (int d = 0; d < D; ++d) xi[d] = 0.f;
+          c = 0.f;
+        }
+        c *= -0.5f * LOG2E;
+        float S[D + 1];
+        if constexpr (GT) {
+          if (sx) gp_mfma_sums_g_sx<D, false, true, false>(bdp, nch, sxb, c, S);
+          else gp_mfma_sums_g<D, false, true, false>(bdp->gpm, nch, xi, c, S);
+        } else {
+          gp_mfma_sums<D, false, false>(lds + off, lds + a.gpm_frags - 1, nch, xi, c, S);
+        }
+        const KF_CONST_AS BandDesc* q = opaque(bdp);   // epilogue fields: not live across the chunk loop
+        const float sc = q->gpm_scale;
+        float Sd[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) Sd[d] = S[1 + d] * sc;
+        gpm_epilogue<NP, D>(q, xi, S[0] * sc, Sd, H0, h);
+        fin = finitef(H0);
+#pragma unroll
+        for (int j = 0; j < NP; ++j) fin = fin && finitef(h[j]);
+      }
+      if (use && fin) {
+        // pixel_innovation's statistics, in its order (precision rows)
+        float s;
+        [[maybe_unused]] float v[JOINT ? NP : 1];
+        if constexpr (JOINT) s = chol_fwd_solve<NP>(A, h, v);
+        else s = chol_fwd_norm2<NP>(A, h);
+        const float zz = (y - H0) * kf_rsqrt(s + kf_rcp(w));
+        if (finitef(zz)) {
+          zb = zz;
+          counted |= 1ull << b;
+          chi2 = fmaf(zz, zz, chi2);
+          if constexpr (JOINT) {
+            if (jok) jok = joint_band_step<NP>(C, delta, v, y - H0, kf_rcp(w), d2, logdet);
+          }
+          if (k > 0.f && fabsf(zz) > k) {
+            over |= 1ull << b;
+            gbad |= 1ull << (a.grp ? (cptr(a.grp)[b] & 63) : 0);
+          }
+        }
+      }
+    }
+    off += nch * gpm_frags_per_chunk(D);
+    if (act && a.z) a.z[b * a.ldz + p] = zb;
+  }
+  if (act) innovation_tail<JOINT>(a, p, ok, jok, counted, over, gbad, chi2, d2, logdet);
+}
 #endif
 }  // namespace kf

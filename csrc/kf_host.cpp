@@ -377,7 +377,7 @@ int host_marginal(int np, const RasterArgs& a) {
 int host_product(int np, const ProductArgs& a) { return product_args_ok(np, a) ? host_pixels<OpProduct>(np, a) : -1; }
 int host_smooth(int np, const SmoothArgs& a) { return smooth_args_ok(np, a) ? host_pixels<OpSmooth>(np, a) : -1; }
 int host_innovation(int np, const InnovationArgs& a) {
-  if (!innovation_args_ok(np, a)) return -1;
+  if (!innovation_args_ok(np, a) || a.prop) return -1;   // the fused-forecast check is a device kernel only
   return innovation_joint(a) ? host_pixels<OpInnovation<true>>(np, a) : host_pixels<OpInnovation<false>>(np, a);
 }
 int host_obs_order(const BandDesc* bands, const int32_t* grp, int nb, int G, int64_t N, int32_t* order, bool local) {

@@ -649,8 +649,12 @@ hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s) {
 }
 hipError_t dev_innovation(int np, const InnovationArgs& a, const KernelPlan& plan, hipStream_t s) {
   if (!innovation_args_ok(np, a) || plan.np != np || plan.joint != innovation_joint(a)) return hipErrorInvalidValue;
+  // a.prop: x / p are the previous analysis, which only the fused-forecast kernels read as such
+  if (a.prop && plan.family != PLAN_INNOVATION_PROP && plan.family != PLAN_INNOVATION_PROP_G) return hipErrorInvalidValue;
   if (plan.family == PLAN_INNOVATION_MFMA || plan.family == PLAN_INNOVATION_MFMA_G)   // kf_innovation_mfma.hip
     return a.N > 0 ? dev_innovation_mfma(plan, a, dev_grid(a.N), s) : hipSuccess;
+  if (plan.family == PLAN_INNOVATION_PROP || plan.family == PLAN_INNOVATION_PROP_G)
+    return a.N > 0 ? dev_innovation_prop(plan, a, dev_grid(a.N), s) : hipSuccess;
   if (plan.family != PLAN_INNOVATION) return hipErrorInvalidValue;
   return innovation_joint(a) ? launch_pixels<OpInnovation<true>>(np, a, s) : launch_pixels<OpInnovation<false>>(np, a, s);
 }

@@ -58,6 +58,9 @@ hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s);         // on
 hipError_t dev_innovation(int np, const InnovationArgs& a, const KernelPlan& plan, hipStream_t s);
 hipError_t dev_innovation_mfma(const KernelPlan& plan, const InnovationArgs& a, int grid, hipStream_t s);
 void launch_table_innovation(std::vector<KernelPlan>& out);
+// ... at the fused forecast (a.prop set): the kernels of KF_INNOV_PROP_ROWS, a table of their own
+hipError_t dev_innovation_prop(const KernelPlan& plan, const InnovationArgs& a, int grid, hipStream_t s);
+void launch_table_innovation_prop(std::vector<KernelPlan>& out);
 hipError_t dev_reduce(const double* partials, int n, double* out, hipStream_t s);
 hipError_t dev_gather(int elem_bytes, const void* src, const int64_t* idx, void* dst, int64_t n, int rows,
                       int64_t src_ld, int64_t dst_ld, hipStream_t s);

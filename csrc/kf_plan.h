@@ -30,6 +30,8 @@ enum PlanFamily : int {
   PLAN_INNOVATION,           // pixel_kernel<NP, OpInnovation<JOINT>>: any bands, thread per pixel, the VALU record loop
   PLAN_INNOVATION_MFMA,      // innovation_mfma_kernel: GP bands on the matrix cores, tables in LDS
   PLAN_INNOVATION_MFMA_G,    // innovation_mfma_g_kernel: tables in global memory
+  PLAN_INNOVATION_PROP,      // innovation_prop_kernel: the check at the fused forecast (InnovationArgs.prop), tables in LDS
+  PLAN_INNOVATION_PROP_G,    // innovation_prop_g_kernel: tables in global memory
 };
 
 constexpr int PLAN_BLOCK = 256;   // kf_device.h BLOCK: every K1 / K1g kernel's workgroup
@@ -99,12 +101,18 @@ constexpr KernelPlan plan_innovation_mfma_kernel(int np, int d, bool joint) {
 constexpr KernelPlan plan_innovation_mfma_g_kernel(int np, int d, bool joint) {
   return plan_innovation(PLAN_INNOVATION_MFMA_G, np, d, joint);
 }
+constexpr KernelPlan plan_innovation_prop_kernel(int np, int d, bool joint) {
+  return plan_innovation(PLAN_INNOVATION_PROP, np, d, joint);
+}
+constexpr KernelPlan plan_innovation_prop_g_kernel(int np, int d, bool joint) {
+  return plan_innovation(PLAN_INNOVATION_PROP_G, np, d, joint);
+}
 
 // Kernels with the bands' tables in dynamic LDS (a.gpm_frags fragments of 16 B).
 constexpr bool plan_lds_tables(const KernelPlan& p) {
   return p.family == PLAN_ANALYSIS_MFMA || p.family == PLAN_ANALYSIS_MFMA_MIXLO ||
          p.family == PLAN_ANALYSIS_TIP_SL || p.family == PLAN_GAIN_MFMA || p.family == PLAN_GAIN_MFMA_MIXLO ||
-         p.family == PLAN_INNOVATION_MFMA;
+         p.family == PLAN_INNOVATION_MFMA || p.family == PLAN_INNOVATION_PROP;
 }
 
 // The plan's template-id as a demangler prints it for the kernel's symbol
@@ -134,6 +142,9 @@ inline std::string plan_name(const KernelPlan& p) {
     case PLAN_INNOVATION_MFMA: return "innovation_mfma_kernel<" + i(p.np) + ", " + i(p.fd) + ", " + b(p.joint) + ">";
     case PLAN_INNOVATION_MFMA_G:
       return "innovation_mfma_g_kernel<" + i(p.np) + ", " + i(p.fd) + ", " + b(p.joint) + ">";
+    case PLAN_INNOVATION_PROP: return "innovation_prop_kernel<" + i(p.np) + ", " + i(p.fd) + ", " + b(p.joint) + ">";
+    case PLAN_INNOVATION_PROP_G:
+      return "innovation_prop_g_kernel<" + i(p.np) + ", " + i(p.fd) + ", " + b(p.joint) + ">";
     default: return "NONE";
   }
 }
@@ -296,23 +307,29 @@ inline KernelPlan gain_plan(int np, const GainArgs& a) {
 //     a.band_layout (BAND_LAYOUT_SHARED_X) is the kernel's, not the plan's.
 // Mixed operators, SAR / linear / precomputed bands, other state sizes and a
 // table built without fragments take the VALU kernel.
+// a.prop set (x / p are the previous analysis, the kernel forms the forecast):
+// the fused-forecast twins of those two kernels under the same per-band and
+// LDS-size tests, precision rows only; a launch that does not qualify has no
+// kernel (PLAN_NONE: the caller decides beforehand, innovation_prop_unsupported).
 inline KernelPlan innovation_plan(int np, const InnovationArgs& a, bool want_mfma, const BandDesc* hb = nullptr) {
   if (!plan_np(np)) return KernelPlan{};
   const bool joint = innovation_joint(a);
-  const KernelPlan valu = plan_innovation(PLAN_INNOVATION, np, 0, joint);
+  const bool prop = a.prop != nullptr;
+  const KernelPlan valu = prop ? KernelPlan{} : plan_innovation(PLAN_INNOVATION, np, 0, joint);
+  if (prop && a.kind != MARG_PRECISION) return valu;
   if (!want_mfma || !hb || a.nb < 1 || (np != 7 && np != 10)) return valu;
   const int d = np == 7 ? 4 : 10;
   for (int b = 0; b < a.nb; ++b) {
     if (hb[b].op != OP_GP || hb[b].d != d || hb[b].gpm_nchunk <= 0 || !hb[b].gpm) return valu;
     if (np == 10 && !hb[b].map_identity) return valu;
   }
-  if (np == 10) return plan_innovation_mfma_g_kernel(np, d, joint);
+  if (np == 10) return prop ? plan_innovation_prop_g_kernel(np, d, joint) : plan_innovation_mfma_g_kernel(np, d, joint);
   int frags = 1;
   for (int b = 0; b < a.nb; ++b) frags += hb[b].gpm_nchunk * gpm_frags_per_chunk(d);
   // the LDS image the kernel stages must be the one the host sized
   // ... and fit the 160 KiB of a gfx950 CU
   if (a.gpm_frags <= 0 || a.gpm_frags != frags || (int64_t)frags * 16 > 160 * 1024) return valu;
-  return plan_innovation_mfma_kernel(np, d, joint);
+  return prop ? plan_innovation_prop_kernel(np, d, joint) : plan_innovation_mfma_kernel(np, d, joint);
 }
 
 }  // namespace kf

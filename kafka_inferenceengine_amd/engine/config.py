@@ -135,6 +135,18 @@ class EngineConfig:
     # date with a SAR band, the host runner.  z differs from 'valu' by the rounding
     # of the GP sums, so a decision within that of the gate may differ
     innovation_gp: str = "valu"               # 'valu' | 'mfma'
+    # innovation_forecast: where the check finds the forecast.  'materialised': the
+    # forecast is written to memory first and the date's analysis reads it (the
+    # unfused path).  'fused': where the date's forecast is a fused partial-reset
+    # forecast of precision kind and the band table is one the matrix-core check
+    # serves, the check kernel forms the forecast itself and the analysis keeps
+    # its fused launches, those of an unscreened date; every other date
+    # (gain form, prior blend, spatial prior, SAR / linear / mixed bands, other
+    # state sizes, the first date, the host runner) takes 'materialised'.  With
+    # the option 'fused' each date's 'innovation' metrics entry says which of the
+    # two it took ("forecast"); a default run's entry carries no such key
+    # (--innovation-forecast)
+    innovation_forecast: str = "materialised"  # 'materialised' | 'fused'
     metrics_path: str | None = None           # JSONL metrics (per date / timestep)
     checkpoint_dir: str | None = None
     checkpoint_every: int = 0                 # timesteps between checkpoints (0: off)
@@ -169,6 +181,8 @@ class EngineConfig:
             raise ValueError("innovation_scope must be 'group' or 'band'")
         if self.innovation_gp not in ("valu", "mfma"):
             raise ValueError("innovation_gp must be 'valu' or 'mfma'")
+        if self.innovation_forecast not in ("materialised", "fused"):
+            raise ValueError("innovation_forecast must be 'materialised' or 'fused'")
         if self.store_precision not in ("auto", "always"):
             raise ValueError("store_precision must be 'auto' or 'always'")
         if isinstance(self.convergence_chunk, str) and self.convergence_chunk.strip().lower() in ("", "0", "tile",

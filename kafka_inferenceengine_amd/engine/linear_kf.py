@@ -164,6 +164,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         self.ood_history = None           # config.domain_history: ST_OUT_OF_DOMAIN on any date so far
         self._qa_acc = None               # a QA output: the timestep's status / nobs / nrej folded over its dates
         self.last_innovation = None       # config.innovation_*: the last date's {"chi2", "nobs", "nrej"}
+        self._innov_forecast = None       # the last screened date's check: "fused" | "materialised"
         self.gate_history = None          # config.innovation_gate: dates with a rejection, per pixel (int32)
         self.evidence = None              # config.innovation_evidence: the run's per-pixel accumulators
         self._innov = None                # its buffers: statistics and the screened observation planes
@@ -610,6 +611,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                 rec.update(self._health_metrics(rec["wall_s"]))
                 if self._screening() and not self.config.band_sequential and self.last_innovation is not None:
                     rec["innovation"] = self._innovation_record()
+                    if self.config.innovation_forecast == "fused":   # what this date's check took (else: no key)
+                        rec["innovation"]["forecast"] = self._innov_forecast
             self.metrics.log(rec)
         return forecast, info
 
@@ -694,13 +697,28 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             return "mfma"
         return "valu"
 
+    def _fused_check(self, forecast, specs, table) -> bool:
+        """config.innovation_forecast = 'fused' on a date whose analysis takes the fused
+        propagation (do_all_bands_state's test) and whose band table the fused-forecast
+        check kernels serve; every other date checks the materialised forecast."""
+        cfg = self.config
+        return (cfg.innovation_forecast == "fused" and isinstance(forecast, LazyForecast)
+                and forecast.kind == PRECISION and self._analysis_kind() == PRECISION and bool(self.N)
+                and cfg.analysis_form != "gain" and cfg.spatial_gamma <= 0 and self.band_comm is None
+                and not any(t is not None for t in (forecast.blend_pix or ()))
+                and self._split_plan_kind(specs) is None
+                and K.innovation_prop_unsupported(self.n_params, table, self.device) is None)
+
     def _screen_date(self, timestep, bands, forecast):
         """Innovation statistics of one date against the forecast its analysis
         starts from (config.innovation_gate / innovation_stats /
-        innovation_evidence).  Returns the materialised forecast and the bands to
+        innovation_evidence).  Returns the forecast and the bands to
         assimilate: under a gate, copies whose nodata plane is an engine-owned
         buffer with the rejected observations set to nodata (the source's planes
-        are never written).
+        are never written).  The forecast is materialised for the check, or
+        (config.innovation_forecast = 'fused', :meth:`_fused_check`) stays the
+        :class:`LazyForecast` it was: the check kernel forms it per pixel from the
+        previous analysis and the date's analysis launches as on an unscreened date.
 
         With ``innovation_evidence`` the joint statistic d2 = r^T S^-1 r and
         log det S of the observations the analysis assimilates are written too
@@ -715,8 +733,15 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         specs = [s for s, _ in bands]
         dbs = [d for _, d in bands]
         table = self._innovation_table(specs, bands)
-        fc = self._as_kind(forecast, self._analysis_kind())
-        fc.require_full("the innovation check")
+        fused = self._fused_check(forecast, specs, table)
+        self._innov_forecast = "fused" if fused else "materialised"
+        if fused:
+            # x / p: the previous analysis (the rows the forecast reads), prop: its fused-forecast arguments
+            fc, at = forecast, dict(x=forecast.src.x, p=forecast.src.P, kind=PRECISION, prop=forecast.handle())
+        else:
+            fc = self._as_kind(forecast, self._analysis_kind())
+            fc.require_full("the innovation check")
+            at = dict(x=fc.x, p=fc.P, kind=fc.kind)
         gated = cfg.innovation_gate > 0
         buf = self._innov
         if buf is None:
@@ -742,10 +767,10 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                 screened.append(t[:src.numel()])
         if N:
             with self.timer.phase("innovation"):
-                K.innovation(n, table, fc.x, fc.P, kind=fc.kind, N=N, chi2=buf["chi2"], nobs=buf["nobs"],
+                K.innovation(n, table, N=N, chi2=buf["chi2"], nobs=buf["nobs"],
                              nrej=buf["nrej"], status=buf["status"], gate=cfg.innovation_gate,
                              scope=cfg.innovation_scope, groups=self._band_groups(timestep, len(specs)),
-                             screened=screened, gp=self._innovation_gp(table), **first)
+                             screened=screened, gp=self._innovation_gp(table), **at, **first)
         self.last_innovation = {"chi2": buf["chi2"][:N], "nobs": buf["nobs"][:N], "nrej": buf["nrej"][:N],
                                 "status": buf["status"][:N]}
         if not gated:
@@ -760,9 +785,9 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             if N:
                 with self.timer.phase("innovation"):
                     kept = self._innovation_table(specs, run_bands)
-                    K.innovation(n, kept, fc.x, fc.P, kind=fc.kind, N=N, nobs=buf["nobs_kept"],
+                    K.innovation(n, kept, N=N, nobs=buf["nobs_kept"],
                                  status=buf["status_kept"], d2=buf["d2"], logdet=buf["logdet"],
-                                 gp=self._innovation_gp(kept))
+                                 gp=self._innovation_gp(kept), **at)
             self._add_evidence(buf["d2"], buf["logdet"], buf["nobs_kept"])
         return fc, run_bands
 

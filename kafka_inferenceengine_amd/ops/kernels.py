@@ -1712,12 +1712,33 @@ def _innovation_mfma_fields(n_params, bands: BandTable):
     return frags, layout
 
 
-def innovation_plan(n_params, bands: BandTable, joint=False, gp="mfma"):
+def innovation_plan(n_params, bands: BandTable, joint=False, gp="mfma", prop=False, kind="precision"):
     """The kernel a device launch of :func:`innovation` over ``bands`` takes (kf_plan.h
-    ``innovation_plan``); no device needed.  ``Variant.VALU_ORACLE`` plans the VALU kernel."""
-    want = gp == "mfma" and DEFAULT_VARIANT != Variant.VALU_ORACLE and len(bands.descs) == bands.n
+    ``innovation_plan``); no device needed.  ``Variant.VALU_ORACLE`` plans the VALU kernel.
+    ``prop``: the launch carries a fused forecast (family ``NONE`` where no kernel serves it)."""
+    want = (gp == "mfma" or bool(prop)) and DEFAULT_VARIANT != Variant.VALU_ORACLE and len(bands.descs) == bands.n
     frags, layout = _innovation_mfma_fields(n_params, bands)
-    return ext().innovation_plan(int(n_params), list(bands.descs) if want else [], frags, layout, bool(joint), want)
+    e = ext()
+    return e.innovation_plan(int(n_params), list(bands.descs) if want else [], frags, layout, bool(joint), want,
+                             bool(prop), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION)
+
+
+def innovation_prop_unsupported(n_params, bands: BandTable, device, kind="precision"):
+    """Why ``innovation(prop=...)`` (the check at a fused forecast, kf_gp_mfma.h ``pixel_innovation_prop``)
+    cannot serve this table on this device, or None where it can."""
+    if torch.device(device).type != "cuda":
+        return "the fused-forecast innovation kernels have no host twin (device tensors only)"
+    if n_params not in SUPPORTED_NP:
+        return f"n_params={n_params} has no compiled kernel"
+    if kind != "precision":
+        return "the fused-forecast innovation kernels read precision rows only"
+    if DEFAULT_VARIANT == Variant.VALU_ORACLE:
+        return "Variant.VALU_ORACLE: the fused-forecast innovation kernels have no VALU twin"
+    if not innovation_plan(n_params, bands, prop=True, kind=kind)["family"].startswith("innovation_prop"):
+        return (f"no fused-forecast innovation kernel for {bands.n} band(s) of a {n_params}-parameter state: it takes "
+                "7 parameters with 4-input GP bands whose tables fit in LDS, or 10 parameters with full-state GP "
+                "bands, every band with matrix-core fragments")
+    return None
 
 
 def innovation_mfma_unsupported(n_params, bands: BandTable, device):
@@ -1740,7 +1761,8 @@ def innovation_mfma_supported(n_params, bands: BandTable, device) -> bool:
 
 
 def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=None, nobs=None, nrej=None, status,
-               gate=0.0, scope="group", groups=None, screened=None, d2=None, logdet=None, gp="valu"):
+               gate=0.0, scope="group", groups=None, screened=None, d2=None, logdet=None, gp="valu", prop=None,
+               line=None):
     """Innovation statistics and the chi-square gate, per pixel (csrc/kf_core.h
     ``pixel_innovation``).  ``x`` [n_p, ld] and ``p`` [ntri, ld] (packed rows of
     P^-1 for ``kind="precision"``, of P for ``"covariance"``) are the state the
@@ -1783,11 +1805,26 @@ def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=N
     from the VALU loop's by the rounding of the GP sums.  ``Variant.VALU_ORACLE``
     launches the VALU kernel, ``Variant.PER_BAND_OPERAND`` rebuilds the shared
     exponent operand per band, as for :func:`gain`.  The kernel taken is
-    recorded in ``LAST_INNOVATION_PLAN``."""
+    recorded in ``LAST_INNOVATION_PLAN``.
+
+    ``prop`` (a fused :class:`PropHandle`, ``prop_args(..., fused=True)``): the
+    check at the partial-reset forecast of ``x`` / ``p``, which are then the
+    previous analysis the handle was built on (precision rows; only the rows the
+    forecast reads need to be stored).  The kernel forms the forecast per pixel
+    (kf_gp_mfma.h ``pixel_innovation_prop``), so nothing is materialised; the
+    bands are evaluated on the matrix cores whatever ``gp`` says, or, with
+    ``line`` (None: ``LINE_TABLES``, False: off), from the line tables of
+    :func:`line_fields` wherever a whole wave lies inside them.  A table or
+    state no such kernel serves is a ValueError
+    (:func:`innovation_prop_unsupported` asks without raising)."""
     check_np(n_params)
     if gp not in INNOVATION_GP:
         raise ValueError("gp must be 'valu' or 'mfma'")
-    if gp == "mfma":
+    if prop is not None:
+        why = innovation_prop_unsupported(n_params, bands, x.device, kind)
+        if why is not None:
+            raise ValueError(f"innovation(prop=...): {why}")
+    elif gp == "mfma":
         why = innovation_mfma_unsupported(n_params, bands, x.device)
         if why is not None:
             raise ValueError(f"innovation(gp='mfma'): {why}")
@@ -1812,6 +1849,9 @@ def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=N
         raise ValueError("x and p must share their row stride")
     if bands.buf.device != dev:
         raise ValueError(f"band table on {bands.buf.device}, expected {dev}")
+    _check_prop(prop, N, ld, dev)
+    if prop is not None and (prop.args.x_a != _ptr(x) or prop.args.p_a != _ptr(p)):
+        raise ValueError("innovation(prop=...): x and p must be the analysis the handle was built on")
     if status is None:
         raise ValueError("status is required")
     _check_vec(status, N, "status", torch.uint8, dev)
@@ -1850,14 +1890,19 @@ def innovation(n_params, bands: BandTable, x, p, *, kind, N=None, z=None, chi2=N
     e = ext()
     global LAST_INNOVATION_PLAN
     joint = d2 is not None or logdet is not None
-    want = gp == "mfma" and DEFAULT_VARIANT != Variant.VALU_ORACLE
+    want = (gp == "mfma" or prop is not None) and DEFAULT_VARIANT != Variant.VALU_ORACLE
     frags, layout = _innovation_mfma_fields(n_params, bands) if want else (0, 0)
-    LAST_INNOVATION_PLAN = innovation_plan(n_params, bands, joint, gp) if _dev(x) else None
+    LAST_INNOVATION_PLAN = innovation_plan(n_params, bands, joint, gp, prop is not None, kind) if _dev(x) else None
+    lf = None
+    if prop is not None and (LINE_TABLES if line is None else line):
+        lf = line_fields(bands, prop, n_params, dev)
+    lf = (None, 0.0, 0.0, 0, 0) if lf is None else lf
     e.innovation(n_params, _ptr(x), _ptr(p), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION,
                  bands.ptr, nb, _ptr(grp), gate, e.INNOV_SCOPE_BAND if scope == "band" else e.INNOV_SCOPE_GROUP,
                  _ptr(z), 0 if z is None else z.shape[1], _ptr(chi2), _ptr(nobs), _ptr(nrej), _ptr(status),
                  _ptr(ptrs), N, ld, _dev(x), _stream(x), _ptr(d2), _ptr(logdet), want,
-                 list(bands.descs) if want else [], frags, layout)
+                 list(bands.descs) if want else [], frags, layout,
+                 0 if prop is None else _ptr(prop.device_copy()), _ptr(lf[0]), lf[1], lf[2], lf[3], lf[4])
 
 
 def reduce_partials(partials: torch.Tensor, out: torch.Tensor | None = None):

@@ -22,7 +22,7 @@ status, nobs, d2 and logdet only).
 ``e2e``: ``bench.py --config C`` five ways (``--only`` picks some) -- default, ``--set
 fuse_propagation=false`` (the unfused path a screened date also takes), ``--set
 innovation_stats=true``, ``--set innovation_gate=K`` and the latter with ``--set
-innovation_gp=mfma`` -- ``--rounds`` times in
+innovation_gp=mfma`` and that with ``--set innovation_forecast=fused`` -- ``--rounds`` times in
 that order, with the ms/step of every run and the ratios of the means.
 
     python scripts/bench_innovation.py e2e --configs tip7 prosail10
@@ -40,7 +40,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 VARIANTS = (("default", []), ("unfused", ["--set", "fuse_propagation=false"]),
-            ("stats", ["--set", "innovation_stats=true"]), ("gated", None), ("gated_mfma", None))
+            ("stats", ["--set", "innovation_stats=true"]), ("gated", None), ("gated_mfma", None),
+            ("gated_fused", None))
 
 
 def emit(rec, record):
@@ -121,6 +122,19 @@ def one_kernel_config(config, size, reps, gate, device=None):
     out = []
     # every variant with the VALU kernel, then (where the table has one) with the matrix-core kernel
     gps = ["valu"] + (["mfma"] if K.innovation_mfma_supported(n, table, dev) else [])
+    # ... and the check at the fused forecast of the same state (prop: line tables off, prop_line: on): the
+    # kernel forms the forecast st holds from the analysis the lazy forecast was built on
+    from kafka_inferenceengine_amd.engine.state import LazyForecast
+    lazy = kf.advance_state(kf._materialize(state), dates[0], lazy=True)
+    if isinstance(lazy, LazyForecast) and lazy.kind == "precision" and \
+            K.innovation_prop_unsupported(n, table, dev) is None:
+        st = lazy.materialize()
+        gps += ["prop", "prop_line"]
+
+    def at(gp):
+        if not gp.startswith("prop"):
+            return dict(x=st.x, p=st.P, kind=st.kind, gp=gp)
+        return dict(x=lazy.src.x, p=lazy.src.P, kind="precision", prop=lazy.handle(), line=gp == "prop_line")
     for name, kw, gp in ((nm, kw, gp) for nm, kw in (("stats", dict(gate=0.0)),
                                                      ("gated", dict(gate=gate, screened=screened)),
                                                      ("joint", dict(gate=0.0, d2=d2, logdet=logdet)),
@@ -128,11 +142,11 @@ def one_kernel_config(config, size, reps, gate, device=None):
         if kw is None:
             table2 = kf._innovation_table(specs, kept)
             kw = dict(gate=0.0)
-            med, lo, hi = timed(lambda: K.innovation(n, table2, st.x, st.P, kind=st.kind, N=N, nobs=nobs,
-                                                     status=status, d2=d2, logdet=logdet, gp=gp))
+            med, lo, hi = timed(lambda: K.innovation(n, table2, N=N, nobs=nobs, status=status, d2=d2,
+                                                     logdet=logdet, **at(gp)))
         else:
-            med, lo, hi = timed(lambda: K.innovation(n, table, st.x, st.P, kind=st.kind, N=N, chi2=chi2, nobs=nobs,
-                                                     nrej=nrej, status=status, groups=groups, gp=gp, **kw))
+            med, lo, hi = timed(lambda: K.innovation(n, table, N=N, chi2=chi2, nobs=nobs, nrej=nrej,
+                                                     status=status, groups=groups, **at(gp), **kw))
         seen = int(nobs.sum(dtype=torch.int64).item())
         fin = torch.isfinite(d2)
         joint = {} if name in ("stats", "gated") else {
@@ -168,7 +182,8 @@ def e2e(a):
             for name, extra in VARIANTS:
                 if extra is None:      # gated, with the VALU check or (gated_mfma) the matrix-core one
                     extra = ["--set", f"innovation_gate={a.gate}"] + \
-                        (["--set", "innovation_gp=mfma"] if name == "gated_mfma" else [])
+                        (["--set", "innovation_gp=mfma"] if name != "gated" else []) + \
+                        (["--set", "innovation_forecast=fused"] if name == "gated_fused" else [])
                 if a.only and name not in a.only:
                     continue
                 cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", config, "--steps",
@@ -182,7 +197,8 @@ def e2e(a):
         mean = {name: statistics.fmean(v) for name, v in runs.items() if v}
         ratios = {f"{p}_over_{q}": round(mean[p] / mean[q], 3)
                   for p, q in (("gated", "default"), ("gated", "unfused"), ("stats", "unfused"),
-                               ("gated_mfma", "default"), ("gated_mfma", "gated")) if p in mean and q in mean}
+                               ("gated_mfma", "default"), ("gated_mfma", "gated"), ("gated_fused", "default"),
+                               ("gated_fused", "gated_mfma")) if p in mean and q in mean}
         emit({"bench": "e2e", "config": config, "size": a.size, "steps": a.steps, "warmup": a.warmup, "gate": a.gate,
               "ms_per_step": runs, "mean_ms_per_step": {name: round(v, 3) for name, v in mean.items()}, **ratios},
              a.record)
