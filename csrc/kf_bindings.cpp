@@ -433,6 +433,53 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     if (device) check_hip(dev_hessian(np, a, (hipStream_t)stream), "hessian");
     else check_host(host_hessian(np, a), "hessian");
   });
+  // K6 on the matrix cores (kf_gp_mfma.h pixel_hessian_mfma).  bands: host copies of the descriptors; tabs /
+  // fmul / nchunk / scale: one entry per band, the Hessian table's device address (0: none), its per-field
+  // multipliers, chunk count and 2^sigma.  hessian_plan: the kernel such a launch takes (kf_plan.h), no device
+  // needed; hessian_mfma launches it and raises where the plan is the VALU kernel.
+  const auto hessian_args = [](const std::vector<BandDesc>& bands, const std::vector<uintptr_t>& tabs,
+                               const std::vector<uintptr_t>& fmul, const std::vector<int>& nchunk,
+                               const std::vector<float>& scale) {
+    HessianMfmaArgs a{};
+    const size_t nb = bands.size();
+    if (tabs.size() != nb || fmul.size() != nb || nchunk.size() != nb || scale.size() != nb)
+      throw std::invalid_argument("hessian: one table entry per band");
+    a.h.n_bands = (int)nb;
+    for (size_t b = 0; b < nb && b < (size_t)HESS_MAX_BANDS; ++b) {
+      a.tab[b] = P<const void>(tabs[b]);
+      a.fmul[b] = P<const float>(fmul[b]);
+      a.nchunk[b] = nchunk[b];
+      a.gpm_scale[b] = scale[b];
+    }
+    return a;
+  };
+  m.attr("HESS_MAX_BANDS") = HESS_MAX_BANDS;
+  m.def("hessian_plan", [hessian_args](int np, const std::vector<BandDesc>& bands, const std::vector<uintptr_t>& tabs,
+                                       const std::vector<uintptr_t>& fmul, const std::vector<int>& nchunk,
+                                       const std::vector<float>& scale, bool device) {
+    return plan_dict(hessian_plan(np, hessian_args(bands, tabs, fmul, nchunk, scale), device, bands.data()));
+  });
+  m.def("hessian_mfma", [hessian_args](int np, uintptr_t bands_dev, const std::vector<BandDesc>& bands,
+                                       const std::vector<uintptr_t>& tabs, const std::vector<uintptr_t>& fmul,
+                                       const std::vector<int>& nchunk, const std::vector<float>& scale, uintptr_t x,
+                                       uintptr_t a_rows, int64_t N, int64_t ld, uintptr_t stream) {
+    HessianMfmaArgs a = hessian_args(bands, tabs, fmul, nchunk, scale);
+    a.h.N = N;
+    a.h.ld = ld;
+    a.h.bands = P<const BandDesc>(bands_dev);
+    a.h.x = P<const float>(x);
+    a.h.a = P<float>(a_rows);
+    const KernelPlan plan = hessian_plan(np, a, true, bands.data());
+    if (plan.family != PLAN_HESSIAN_MFMA) throw std::invalid_argument("hessian_mfma: no matrix-core kernel for this launch");
+    check_hip(dev_hessian_mfma(plan, a, (hipStream_t)stream), "hessian_mfma");
+  });
+  m.def("hessian_table", []() {
+    std::vector<KernelPlan> plans;
+    launch_table_hessian(plans);
+    std::vector<std::string> names;
+    for (const KernelPlan& p : plans) names.push_back(plan_name(p));
+    return names;
+  });
   // unpack: mean and 1/sqrt(diag(P^-1)) onto the raster from the precision rows p
   m.def("unpack", [](int np, uintptr_t x, uintptr_t p, int64_t N, int64_t ld, uintptr_t idx, uintptr_t mean,
                      uintptr_t unc, int64_t plane, bool device, uintptr_t stream) {

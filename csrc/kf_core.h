@@ -3643,4 +3643,24 @@ constexpr int GPM_MAX_D = 10;
 // bands whose sums are held across the record loops (larger tables fall back to VALU)
 constexpr int GPM_MAX_BANDS = 4;
 
+// K6 on the matrix cores (kf_gp_mfma.h gp_hessian_sums, models/gp.py
+// mfma_hessian_tables): 1 + D + D(D+1)/2 fields per training point in groups of
+// 16 (one 32-row sums operand each: hi rows 0..15, lo rows 16..31).
+KF_HD constexpr int hess_fields(int D) { return 1 + D + D * (D + 1) / 2; }
+KF_HD constexpr int hess_groups(int D) { return (hess_fields(D) + 15) / 16; }
+KF_HD constexpr int hess_frags_per_chunk(int D) { return 64 * gpm_k_steps(D) + 128 * hess_groups(D); }
+constexpr int HESS_MAX_BANDS = 16;
+// The launch's per-band side arrays (BandDesc is unchanged): band b's Hessian
+// table (null: not an OP_GP band, skipped as pixel_hessian skips it), its chunk
+// count, the table's 2^sigma and its hess_fields(D) per-field multipliers
+// (device memory: 1 / field scale, times ln2 for the B_d and ln2^2 for the
+// B_u B_v fields).
+struct HessianMfmaArgs {
+  HessianArgs h;
+  const void* tab[HESS_MAX_BANDS];
+  const float* fmul[HESS_MAX_BANDS];
+  int32_t nchunk[HESS_MAX_BANDS];
+  float gpm_scale[HESS_MAX_BANDS];
+};
+
 }  // namespace kf

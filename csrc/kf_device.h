@@ -442,14 +442,18 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(const T* src, const int64
 // N - 1 with act = false (they take part in every MFMA, store and count nothing).
 #if defined(__HIP_DEVICE_COMPILE__)
 template <class F>
-__device__ __forceinline__ void innovation_tiles(const InnovationArgs& a, F&& f) {
+__device__ __forceinline__ void pixel_tiles(int64_t N, F&& f) {
   const int lane = threadIdx.x & 63;
   const int64_t stride = (int64_t)gridDim.x * BLOCK;
-  for (int64_t base = (int64_t)blockIdx.x * BLOCK + (threadIdx.x - lane); base < a.N; base += stride) {
+  for (int64_t base = (int64_t)blockIdx.x * BLOCK + (threadIdx.x - lane); base < N; base += stride) {
     const int64_t q = base + lane;
-    const bool act = q < a.N;
-    f(act ? q : a.N - 1, act);
+    const bool act = q < N;
+    f(act ? q : N - 1, act);
   }
+}
+template <class F>
+__device__ __forceinline__ void innovation_tiles(const InnovationArgs& a, F&& f) {
+  pixel_tiles(a.N, f);
 }
 #endif
 
@@ -495,6 +499,22 @@ __global__ __launch_bounds__(BLOCK, 2) void innovation_prop_g_kernel(InnovationA
   static_assert(BLOCK / 64 == GPM_G_WAVES, "per-wave LDS transpose buffers of gp_mfma_sums_g_xb");
 #if defined(__HIP_DEVICE_COMPILE__)
   innovation_tiles(a, [&](int64_t p, bool act) { pixel_innovation_prop<NP, D, true, JOINT>(a, p, act, nullptr); });
+#endif
+}
+
+// K6 with the GP sums on the matrix cores (kf_gp_mfma.h pixel_hessian_mfma),
+// opt-in beside pixel_kernel<NP, OpHessian>: the walk of the innovation kernels,
+// the Hessian tables read from global memory (HessianMfmaArgs.tab), one 4 KiB
+// extraction buffer per wave in LDS.  JRC-TIP holds both column blocks' sums (one
+// field group, 3 waves per SIMD); the 10-parameter state walks the blocks one
+// after the other (five groups: 80 accumulator registers instead of 160), which
+// keeps it at the 2 waves per SIMD of its launch bound without scratch.
+template <int NP, int D>
+__global__ __launch_bounds__(BLOCK, D <= 4 ? 3 : 2) void hessian_mfma_kernel(HessianMfmaArgs a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __shared__ float xbuf[(BLOCK / 64) * 2 * 32 * 16];
+  float* wbuf = xbuf + (threadIdx.x >> 6) * (2 * 32 * 16);
+  pixel_tiles(a.h.N, [&](int64_t p, bool act) { pixel_hessian_mfma<NP, D, (D <= 4 ? 2 : 1)>(p, act, wbuf); });
 #endif
 }
 
@@ -610,6 +630,11 @@ struct LaunchRow {
   KF_ROW(innovation_prop_kernel, 7, 4, true)       \
   KF_ROW(innovation_prop_g_kernel, 10, 10, false)  \
   KF_ROW(innovation_prop_g_kernel, 10, 10, true)
+
+// K6 on the matrix cores: a table of its own (kf_hessian_mfma.hip)
+#define KF_HESSIAN_ROWS               \
+  KF_ROW(hessian_mfma_kernel, 7, 4)   \
+  KF_ROW(hessian_mfma_kernel, 10, 10)
 
 // Launch of the table's kernel for a plan, hipErrorInvalidValue where it has
 // none (PLAN_NONE included), on the static grid-stride mapping: norm partials

@@ -1621,5 +1621,264 @@ __device__ __forceinline__ void pixel_innovation_prop(const InnovationArgs& a, i
   }
   if (act) innovation_tail<JOINT>(a, p, ok, jok, counted, over, gbad, chi2, d2, logdet);
 }
+
+// ---------------------------------------------------------------------------
+// K6, the Hessian correction (kf_core.h gp_hessian), on the matrix cores.  The
+// sums GEMM of the file header gets D(D+1)/2 more rows,
+//   A = [sgn_i; sgn_i B_id; sgn_i B_iu B_iv (u <= v)]  (F = hess_fields(D) rows),
+// cut into NG = hess_groups(D) operands of 16 fields: hi parts in rows 0..15,
+// lo parts in rows 16..31 (the LO = 16 layout of gpm_lo_row).  Per 32-point chunk
+// and 32-pixel column block the exponent MFMAs and gpm_exp_split run once and
+// every group takes [hi; lo] x mh and [hi; lo] x ml for both K halves: 4 NG sums
+// MFMAs on 2 exponent steps (JRC-TIP: 15 fields, one operand; PROSAIL: 66
+// fields, five operands, two rows in the last).
+//
+// Host table (models/gp.py mfma_hessian_tables), per chunk: the exponent A
+// fragments of mfma_tables (64 NK), then per group g and (q, h) the 32 rows'
+// fragments, so that a lane's fragment of (g, q) is 64 NK + 128 g + 64 q + lane.
+// The table is read from global memory through a raw buffer resource (lane
+// offset in a VGPR, chunk and group offset in soffset) into a register double
+// buffer that runs one group ahead: the next group's fragments -- after the last
+// group the next chunk's first -- are in flight under the current group's MFMAs,
+// and the next chunk's exponent fragments under the whole chunk.  The empty rows
+// of the last group read beyond num_records (zeros).
+//
+// NB: the column blocks held live.  NB = 2 keeps 2 NG accumulators (JRC-TIP:
+// 32 registers); NB = 1 walks the blocks one after the other, each with the
+// whole chunk loop and NG accumulators (PROSAIL: 80 registers instead of 160,
+// which with the 55-entry correction per lane is what keeps two waves per SIMD).
+template <int D, int NB>
+__device__ __forceinline__ void gp_hessian_sums(const void* tab_, int nchunk, const kf_h8 (&xb)[NB][gpm_k_steps(D)],
+                                                kf_f16v (&acc)[hess_groups(D)][NB]) {
+  constexpr int NK = gpm_k_steps(D), NG = hess_groups(D), FPC = hess_frags_per_chunk(D);
+  constexpr int NF_LAST = hess_fields(D) - 16 * (NG - 1);
+  const int lane = threadIdx.x & 63;
+  const int chunk_bytes = FPC * 16;
+  const __amdgpu_buffer_rsrc_t rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(tab_), (short)0, nchunk * chunk_bytes, 0x00020000);
+  constexpr int OOB = 0x40000000;
+  const int vo = lane * 16;
+  const int vo_last = (lane & 15) < NF_LAST ? vo : OOB;
+  const float neg1 = gpm_neg1();
+  const kf_f16v zero = {};
+  auto ld = [&](int voff, int soff) {
+    return __builtin_bit_cast(kf_h8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0));
+  };
+  auto ld_e = [&](int ch, kf_h8 (&ea)[NK]) {
+#pragma unroll
+    for (int kk = 0; kk < NK; ++kk) ea[kk] = ld(vo, ch * chunk_bytes + 1024 * kk);
+  };
+  auto ld_s = [&](int ch, int g, kf_h8 (&sa)[2]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) sa[q] = ld(g == NG - 1 ? vo_last : vo, ch * chunk_bytes + (64 * NK + 128 * g + 64 * q) * 16);
+  };
+  kf_h8 ea[NK], sa[2];
+  ld_e(0, ea);
+  ld_s(0, 0, sa);
+  // one chunk; the first is peeled onto the MFMA's zero operand (>= 1 chunk);
+  // the last chunk prefetches itself
+  auto step = [&](int ch, auto first) {
+    constexpr bool FIRST = decltype(first)::value;
+    const int nx = ch + 1 < nchunk ? ch + 1 : ch;
+    kf_h8 ean[NK];
+    ld_e(nx, ean);
+    kf_h8 mh[NB][2], ml[NB][2];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      kf_f16v e = __builtin_amdgcn_mfma_f32_32x32x16_f16(ea[0], xb[i][0], zero, 0, 0, 0);
+#pragma unroll
+      for (int kk = 1; kk < NK; ++kk) e = __builtin_amdgcn_mfma_f32_32x32x16_f16(ea[kk], xb[i][kk], e, 0, 0, 0);
+#pragma unroll
+      for (int q = 0; q < 2; ++q) gpm_exp_split<false>(e, 8 * q, neg1, mh[i][q], ml[i][q]);
+    }
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      kf_h8 san[2];
+      if (g + 1 < NG) ld_s(ch, g + 1, san);
+      else ld_s(nx, 0, san);
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        // the blocks alternate: no MFMA reads the accumulator the one before it wrote
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+          acc[g][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[q], mh[i][q], (FIRST && q == 0) ? zero : acc[g][i], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) acc[g][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa[q], ml[i][q], acc[g][i], 0, 0, 0);
+      }
+      sa[0] = san[0];
+      sa[1] = san[1];
+    }
+#pragma unroll
+    for (int kk = 0; kk < NK; ++kk) ea[kk] = ean[kk];
+  };
+  KF_DCHECK(nchunk >= 1);
+  step(0, std::true_type{});
+  for (int ch = 1; ch < nchunk; ++ch) step(ch, std::false_type{});
+}
+
+// One group's 16 fields of the lane's own pixel, through the wave's LDS buffer
+// [block][column][field] as gpm_extract_lds: each lane adds its hi and lo rows
+// (register r and r + 8) and stores its fields 8 g2 + 4 q + i of the NB blocks
+// it holds (NB = 1: block blk0), then reads its own pixel's 16 back.  NB = 1:
+// only the lanes of wave half blk0 read what this call stored.
+template <int NB>
+__device__ __forceinline__ void gph_extract(const kf_f16v (&acc)[NB], int blk0, float (&S)[16], float* wbuf) {
+  const int lane = threadIdx.x & 63, n = lane & 31, q = lane >> 5;
+  typedef float f4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int blk = NB == 2 ? i : blk0;
+#pragma unroll
+    for (int g2 = 0; g2 < 2; ++g2) {
+      f4 v;
+      v.x = acc[i][4 * g2 + 0] + acc[i][4 * g2 + 8];
+      v.y = acc[i][4 * g2 + 1] + acc[i][4 * g2 + 9];
+      v.z = acc[i][4 * g2 + 2] + acc[i][4 * g2 + 10];
+      v.w = acc[i][4 * g2 + 3] + acc[i][4 * g2 + 11];
+      *(f4*)(wbuf + (blk * 32 + n) * 16 + 8 * g2 + 4 * q) = v;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  const f4* src = (const f4*)(wbuf + (q * 32 + n) * 16);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const f4 v = src[k];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) S[4 * k + i] = v[i];
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// acc[tri(NP, ., .)] += s val for the second derivative (u, v) of a band's
+// inputs: directly for the identity map, through the compile-time JRC-TIP maps
+// (MK), else through the descriptor's map as gp_hessian scatters it (a map that
+// sends two inputs to one state entry doubles the term).
+template <int NP, int D, int MK>
+__device__ __forceinline__ void gph_scatter(const KF_CONST_AS BandDesc* q, bool ident, int u, int v, float sv,
+                                            float (&acc)[ntri(NP)]) {
+  if constexpr (MK == GPM_MAP_TIP_VIS || MK == GPM_MAP_TIP_NIR) {
+    constexpr GpmMap M = gpm_const_map(MK);
+    const int ju = M.m[u], jv = M.m[v];
+    acc[tri(NP, ju < jv ? ju : jv, ju < jv ? jv : ju)] += sv;
+  } else if (ident) {
+    acc[tri(NP, u < NP ? u : NP - 1, v < NP ? v : NP - 1)] += sv;
+  } else {
+    const int ju = q->map[u], jv = q->map[v];
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+#pragma unroll
+      for (int j = i; j < NP; ++j) {
+        const bool hit = (ju == i && jv == j) || (ju == j && jv == i);
+        const bool dup = (u != v) && (ju == jv) && (ju == i) && (i == j);
+        acc[tri(NP, i, j)] += hit ? (dup ? 2.f * sv : sv) : 0.f;
+      }
+  }
+}
+
+// pixel_hessian with lane = pixel and every GP band's sums evaluated by the wave
+// (all 64 lanes take part in every MFMA; act = false for the tail lanes past N,
+// which run on pixel N - 1 and store nothing).  A band no lane of the wave
+// observes is skipped; a lane that does not use the band feeds the band's centre
+// (xi = 0, c = 0).  A non-finite state reaches the matrix cores clamped
+// (gpm_operands) and poisons its own lane's sums through 2^cl only.  wbuf: the
+// wave's 4 KiB LDS buffer.
+template <int NP, int D, int NB>
+__device__ __forceinline__ void pixel_hessian_mfma(int64_t p, bool act, float* wbuf) {
+  constexpr int NT = ntri(NP), NK = gpm_k_steps(D), NG = hess_groups(D), F = hess_fields(D);
+  const KF_CONST_AS HessianMfmaArgs* ka = (const KF_CONST_AS HessianMfmaArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  const int64_t ld = ka->h.ld;
+  KF_DCHECK(p >= 0 && p < ka->h.N && ka->h.N <= ld);
+  float x[NP], acc[NT];
+#pragma unroll
+  for (int j = 0; j < NP; ++j) x[j] = ka->h.x[j * ld + p];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = 0.f;
+  bool touched = false;
+  const int half = (threadIdx.x >> 5) & 1;
+  for (int b = 0; b < ka->h.n_bands; ++b) {
+    const void* tab = ka->tab[b];
+    if (!tab) continue;   // not an OP_GP band (hessian_plan): pixel_hessian skips it too
+    const KF_CONST_AS BandDesc* bdp = cptr(ka->h.bands) + b;
+    float y, w;
+    decode_obs<0>(*bdp, p, y, w);
+    const bool use = act && (w > 0.f);
+    if (!__any(use)) continue;
+    constexpr bool TIPK = NP == 7 && D == 4;
+    const int mk = TIPK ? bdp->map_kind : GPM_MAP_RUNTIME;
+    float xi[D], c = 0.f;
+    if (TIPK && mk == GPM_MAP_TIP_VIS) gpm_inputs_const<NP, D, GPM_MAP_TIP_VIS>(bdp, x, xi, c);
+    else if (TIPK && mk == GPM_MAP_TIP_NIR) gpm_inputs_const<NP, D, GPM_MAP_TIP_NIR>(bdp, x, xi, c);
+    else gpm_inputs<NP, D>(bdp, x, xi, c);
+    if (!use) {
+#pragma unroll
+      for (int d = 0; d < D; ++d) xi[d] = 0.f;
+      c = 0.f;
+    }
+    c *= -0.5f * LOG2E;
+    kf_h8 xb[2][NK];
+    float cl;
+    gpm_operands<D>(xi, c, xb, cl);
+    const int nch = ka->nchunk[b];
+    // the per-lane part for the lanes whose pixel's sums are in S
+    auto finish = [&](const float (&S)[16 * NG], bool mine) __attribute__((always_inline)) {
+      const KF_CONST_AS BandDesc* q = bdp;
+      const KF_CONST_AS float* fm = cptr(ka->fmul[b]);
+      const float sc = ka->gpm_scale[b] * kexp2(cl);
+      const float S0 = S[0] * sc * fm[0];
+      const float s = w * (y - (q->offset + S0));
+      float au[D], G[D];
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        au[d] = q->coef[d] * xi[d];
+        G[d] = S[1 + d] * sc * fm[1 + d];
+      }
+      if (use && mine) {
+        touched = true;
+        const bool ident = q->map_identity;
+#pragma unroll
+        for (int u = 0; u < D; ++u)
+#pragma unroll
+          for (int v = u; v < D; ++v) {
+            const int f = 1 + D + tri(D, u, v);
+            float val = fmaf(au[u] * au[v], S0, S[f] * sc * fm[f]) - au[u] * G[v] - au[v] * G[u];
+            if (u == v) val -= q->coef[u] * S0;
+            if (TIPK && mk == GPM_MAP_TIP_VIS) gph_scatter<NP, D, GPM_MAP_TIP_VIS>(q, false, u, v, s * val, acc);
+            else if (TIPK && mk == GPM_MAP_TIP_NIR) gph_scatter<NP, D, GPM_MAP_TIP_NIR>(q, false, u, v, s * val, acc);
+            else gph_scatter<NP, D, GPM_MAP_RUNTIME>(q, ident, u, v, s * val, acc);
+          }
+      }
+    };
+    static_assert(F <= 16 * NG, "fields in groups of 16");
+    if constexpr (NB == 2) {
+      kf_f16v sums[NG][2];
+      gp_hessian_sums<D, 2>(tab, nch, xb, sums);
+      float S[16 * NG];
+#pragma unroll
+      for (int g = 0; g < NG; ++g) gph_extract<2>(sums[g], 0, *(float (*)[16])(S + 16 * g), wbuf);
+      finish(S, true);
+    } else {
+      auto block = [&](auto blk_) __attribute__((always_inline)) {
+        constexpr int blk = decltype(blk_)::value;
+        kf_h8 xb1[1][NK];
+#pragma unroll
+        for (int kk = 0; kk < NK; ++kk) xb1[0][kk] = xb[blk][kk];
+        kf_f16v sums[NG][1];
+        gp_hessian_sums<D, 1>(tab, nch, xb1, sums);
+        float S[16 * NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) gph_extract<1>(sums[g], blk, *(float (*)[16])(S + 16 * g), wbuf);
+        finish(S, half == blk);
+      };
+      block(std::integral_constant<int, 0>{});
+      block(std::integral_constant<int, 1>{});
+    }
+  }
+  // a pixel no band touched keeps its bits
+  if (touched) {
+    float* a = ka->h.a;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) a[t * ld + p] -= acc[t];
+  }
+}
 #endif
 }  // namespace kf

@@ -47,6 +47,9 @@ hipError_t dev_propagate(int np, const PropArgs& a, hipStream_t s);
 hipError_t dev_invert(int np, const InvertArgs& a, hipStream_t s);
 hipError_t dev_operator(int np, const OperatorArgs& a, hipStream_t s);
 hipError_t dev_hessian(int np, const HessianArgs& a, hipStream_t s);
+// K6 on the matrix cores (kf_hessian_mfma.hip): hessian_plan's PLAN_HESSIAN_MFMA kernel for a
+hipError_t dev_hessian_mfma(const KernelPlan& plan, const HessianMfmaArgs& a, hipStream_t s);
+void launch_table_hessian(std::vector<KernelPlan>& out);
 hipError_t dev_gp_operator(int np, int d, const GpOperatorArgs& a, hipStream_t s);
 bool gp_operator_supported(int np, int d);
 hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s);

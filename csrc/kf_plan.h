@@ -32,6 +32,8 @@ enum PlanFamily : int {
   PLAN_INNOVATION_MFMA_G,    // innovation_mfma_g_kernel: tables in global memory
   PLAN_INNOVATION_PROP,      // innovation_prop_kernel: the check at the fused forecast (InnovationArgs.prop), tables in LDS
   PLAN_INNOVATION_PROP_G,    // innovation_prop_g_kernel: tables in global memory
+  PLAN_HESSIAN,              // pixel_kernel<NP, OpHessian>: K6, thread per pixel, the VALU record loop
+  PLAN_HESSIAN_MFMA,         // hessian_mfma_kernel: K6 with the GP sums on the matrix cores, tables in global memory
 };
 
 constexpr int PLAN_BLOCK = 256;   // kf_device.h BLOCK: every K1 / K1g kernel's workgroup
@@ -108,6 +110,10 @@ constexpr KernelPlan plan_innovation_prop_g_kernel(int np, int d, bool joint) {
   return plan_innovation(PLAN_INNOVATION_PROP_G, np, d, joint);
 }
 
+// K6, the Hessian correction (kf_core.h pixel_hessian / kf_gp_mfma.h pixel_hessian_mfma)
+constexpr KernelPlan plan_hessian(int np) { return {PLAN_HESSIAN, np, 0, 0, PLAN_BLOCK}; }
+constexpr KernelPlan plan_hessian_mfma_kernel(int np, int d) { return {PLAN_HESSIAN_MFMA, np, d, 0, PLAN_BLOCK}; }
+
 // Kernels with the bands' tables in dynamic LDS (a.gpm_frags fragments of 16 B).
 constexpr bool plan_lds_tables(const KernelPlan& p) {
   return p.family == PLAN_ANALYSIS_MFMA || p.family == PLAN_ANALYSIS_MFMA_MIXLO ||
@@ -145,6 +151,8 @@ inline std::string plan_name(const KernelPlan& p) {
     case PLAN_INNOVATION_PROP: return "innovation_prop_kernel<" + i(p.np) + ", " + i(p.fd) + ", " + b(p.joint) + ">";
     case PLAN_INNOVATION_PROP_G:
       return "innovation_prop_g_kernel<" + i(p.np) + ", " + i(p.fd) + ", " + b(p.joint) + ">";
+    case PLAN_HESSIAN: return "pixel_kernel<" + i(p.np) + ", kf::OpHessian>";
+    case PLAN_HESSIAN_MFMA: return "hessian_mfma_kernel<" + i(p.np) + ", " + i(p.fd) + ">";
     default: return "NONE";
   }
 }
@@ -330,6 +338,32 @@ inline KernelPlan innovation_plan(int np, const InnovationArgs& a, bool want_mfm
   // ... and fit the 160 KiB of a gfx950 CU
   if (a.gpm_frags <= 0 || a.gpm_frags != frags || (int64_t)frags * 16 > 160 * 1024) return valu;
   return prop ? plan_innovation_prop_kernel(np, d, joint) : plan_innovation_mfma_kernel(np, d, joint);
+}
+
+// The kernel of a Hessian-correction launch.  hb: a host-readable copy of the
+// a.h.n_bands descriptors (null: nothing is known about the bands).  The
+// matrix-core kernel serves device launches of the two shipped GP states, 7
+// parameters with 4-input bands and 10 parameters with 10-input bands, when
+// every OP_GP band carries a Hessian table (HessianMfmaArgs.tab); bands of any
+// other kind are the ones pixel_hessian skips and carry none.  Anything else --
+// the host runner, another state size, a GP band of another input count or
+// without a table, more than HESS_MAX_BANDS bands -- takes the VALU kernel.
+inline KernelPlan hessian_plan(int np, const HessianMfmaArgs& a, bool device, const BandDesc* hb = nullptr) {
+  if (!plan_np(np)) return KernelPlan{};
+  const KernelPlan valu = plan_hessian(np);
+  const int nb = a.h.n_bands;
+  if (!device || !hb || nb < 1 || nb > HESS_MAX_BANDS || (np != 7 && np != 10)) return valu;
+  const int d = np == 7 ? 4 : 10;
+  bool any = false;
+  for (int b = 0; b < nb; ++b) {
+    if (hb[b].op != OP_GP) {
+      if (a.tab[b]) return valu;
+      continue;
+    }
+    if (hb[b].d != d || !a.tab[b] || !a.fmul[b] || a.nchunk[b] <= 0) return valu;
+    any = true;
+  }
+  return any ? plan_hessian_mfma_kernel(np, d) : valu;
 }
 
 }  // namespace kf

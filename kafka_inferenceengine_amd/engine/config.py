@@ -45,6 +45,11 @@ class EngineConfig:
     analysis_form: str = "information"        # 'information' (K1) | 'gain' (K1g)
     joseph: bool = False                      # Joseph-form covariance update (gain form)
     hessian_correction: bool = False          # K6 after convergence (off: linear_kf.py:313-319)
+    # hessian_gp: how K6 forms the GP sums.  'valu': the thread-per-pixel record
+    # loop (any bands).  'mfma': on the matrix cores where the date's band table
+    # allows it (JRC-TIP, 10-parameter GPs, on a device;
+    # ops.kernels.hessian_mfma_supported) and the VALU kernel otherwise
+    hessian_gp: str = "valu"                  # 'valu' | 'mfma'
     reference_quirks: bool = False            # swapped prior blend (kf_tools.py:90)
     band_sequential: bool = False             # legacy per-band assimilation (linear_kf.py:325-425)
     # spatial regulariser (new capability, off by default => reference results)
@@ -181,6 +186,8 @@ class EngineConfig:
             raise ValueError("innovation_scope must be 'group' or 'band'")
         if self.innovation_gp not in ("valu", "mfma"):
             raise ValueError("innovation_gp must be 'valu' or 'mfma'")
+        if self.hessian_gp not in ("valu", "mfma"):
+            raise ValueError("hessian_gp must be 'valu' or 'mfma'")
         if self.innovation_forecast not in ("materialised", "fused"):
             raise ValueError("innovation_forecast must be 'materialised' or 'fused'")
         if self.store_precision not in ("auto", "always"):

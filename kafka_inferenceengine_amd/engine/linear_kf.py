@@ -697,6 +697,12 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             return "mfma"
         return "valu"
 
+    def _hessian_gp(self, table) -> str:
+        """config.hessian_gp where the date's table and the device allow it, else the VALU kernel."""
+        if self.config.hessian_gp == "mfma" and K.hessian_mfma_supported(self.n_params, table, self.device):
+            return "mfma"
+        return "valu"
+
     def _fused_check(self, forecast, specs, table) -> bool:
         """config.innovation_forecast = 'fused' on a date whose analysis takes the fused
         propagation (do_all_bands_state's test) and whose band table the fused-forecast
@@ -1181,7 +1187,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         self._output_written = state if out_t is not None else None
         if cfg.hessian_correction and not gain and N:
             with self.timer.phase("hessian"):
-                K.hessian(n, run.table, state.x, state.P, N=N)
+                K.hessian(n, run.table, state.x, state.P, N=N, gp=self._hessian_gp(run.table))
         if bp:
             status = self._band_parallel_status(status)
         self.last_status = status
@@ -1445,7 +1451,7 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             self.config.convergence_tolerance = old_tol
         if self.config.hessian_correction is False and spec.kind != OP_PRECOMP and self.N:
             table = build_table([spec], [db], self.n_params, self._cache, self.device)
-            K.hessian(self.n_params, table, res.state.x, res.state.P, N=self.N)
+            K.hessian(self.n_params, table, res.state.x, res.state.P, N=self.N, gp=self._hessian_gp(table))
         return res
 
     def assimilate(self, locate_times, x_forecast, P_forecast, P_forecast_inverse, approx_diagonal=True,

@@ -371,6 +371,139 @@ def mfma_emulate(table, n_chunks: int, scale: float, D: int, xi, c):
 
 
 # --------------------------------------------------------------------------
+# Hessian tables (csrc/kf_gp_mfma.h gp_hessian_sums): the sums operand of the
+# matrix-core GP with D(D+1)/2 more rows, sgn B_u B_v.
+
+HESS_FIELD_LOG2 = 13     # every field's largest |entry| is scaled into [2^13, 2^14)
+
+
+def hess_fields(d: int) -> int:
+    """Weighted sums per training point: 1 + D + D(D+1)/2."""
+    return 1 + d + d * (d + 1) // 2
+
+
+def hess_groups(d: int) -> int:
+    """Sums operands of 16 fields (hi rows 0..15, lo rows 16..31)."""
+    return (hess_fields(d) + 15) // 16
+
+
+def hess_frags_per_chunk(d: int) -> int:
+    return 64 * gpm_k_steps(d) + 128 * hess_groups(d)
+
+
+def _hess_pairs(d: int):
+    """(u, v), u <= v, in the order of kf_core.h ``tri``."""
+    return [(u, v) for u in range(d) for v in range(u, d)]
+
+
+def mfma_hessian_tables(records, n_pos_pairs: int, lam):
+    """Operand fragments of the matrix-core Hessian correction (``csrc/kf_gp_mfma.h``
+    ``gp_hessian_sums``) from the packed VALU records.
+
+    Returns ``(table, n_chunks, scale, field_scale)``.  ``table`` is float16
+    ``[n_chunks, hess_frags_per_chunk, 8]``: per 32-point chunk the exponent A
+    fragments exactly as in :func:`mfma_tables`, then for each field group g and
+    each (K half q, lane half h) the sums A fragments of all 32 rows.  The fields
+    are ``[sgn, sgn B_d, sgn B_u B_v (u <= v, tri order)]``, each times
+    ``2^L'l`` and its own power of two ``field_scale[f]`` (exact; the kernel
+    divides it out after extraction), cut into groups of 16: a group's f16 hi
+    parts in rows 0..15, its lo parts in rows 16..31.  ``scale`` is
+    :func:`mfma_tables`' ``2^sigma``.  None when the exponent operand does not
+    fit f16 or a field has no float32 power-of-two scale."""
+    rec = np.asarray(records, dtype=np.float64)
+    if rec.ndim != 3 or rec.shape[2] != 2:
+        raise ValueError("records must be [T/2, D+1, 2]")
+    D = rec.shape[1] - 1
+    base = mfma_tables(records, n_pos_pairs, lam)
+    if base is None:
+        return None
+    etab, nch, scale = base
+    pts, sgn = mfma_point_order(rec, n_pos_pairs)
+    T = pts.shape[0]
+    L, B = pts[:, 0], pts[:, 1:]
+    Ls = L - np.log2(scale)
+    Ll = Ls - Ls.astype(np.float16).astype(np.float64)
+    F, NG, NK = hess_fields(D), hess_groups(D), gpm_k_steps(D)
+    A = np.zeros((16 * NG, 32 * nch))
+    A[0, :T] = sgn
+    A[1:1 + D, :T] = (sgn[:, None] * B).T
+    for t, (u, v) in enumerate(_hess_pairs(D)):
+        A[1 + D + t, :T] = sgn * B[:, u] * B[:, v]
+    A[:, :T] *= np.exp2(Ll)[None, :]
+    amax = np.abs(A).max(1)
+    if not np.isfinite(amax).all():
+        return None
+    with np.errstate(divide="ignore"):
+        sh = np.where(amax > 0, HESS_FIELD_LOG2 - np.floor(np.log2(np.where(amax > 0, amax, 1.0))), 0.0)
+    if np.abs(sh).max() > 120:
+        return None
+    A *= np.exp2(sh)[:, None]
+    Ah, Al = _split16(A)
+    sp = _sum_points()
+    out = np.zeros((nch, hess_frags_per_chunk(D), 8), dtype=np.float16)
+    out[:, :64 * NK] = etab[:, :64 * NK]
+    for ch in range(nch):
+        for g in range(NG):
+            for qq in range(2):
+                for hh in range(2):
+                    pt = ch * 32 + sp[qq, hh]
+                    o = 64 * NK + 128 * g + 64 * qq + 32 * hh
+                    out[ch, o:o + 16] = Ah[16 * g:16 * g + 16][:, pt]
+                    out[ch, o + 16:o + 32] = Al[16 * g:16 * g + 16][:, pt]
+    return out, nch, scale, np.exp2(sh)[:F]
+
+
+def mfma_hessian_emulate(table, n_chunks: int, scale: float, field_scale, D: int, xi, c):
+    """NumPy model of ``gp_hessian_sums`` read straight from the fragments:
+    ``S [n, F]`` = (S0, S^B_d, S^B_uv) in B units for centred inputs ``xi
+    [n, D]`` and exponent constants ``c [n]``: f16 operand splits, exact
+    products, float64 sums and exponentials."""
+    xi = np.asarray(xi, dtype=np.float64)
+    c = np.asarray(c, dtype=np.float64)
+    NK, NG, F = gpm_k_steps(D), hess_groups(D), hess_fields(D)
+    tab = np.asarray(table, dtype=np.float16).reshape(n_chunks, hess_frags_per_chunk(D), 8).astype(np.float64)
+    xh, xl = _split16(xi)
+    ch_ = np.maximum(c, -6.0e4).astype(np.float16).astype(np.float64)
+    xs = np.zeros((xi.shape[0], 16 * NK))
+    xs[:, 0:D], xs[:, D:2 * D], xs[:, 2 * D:3 * D] = xh, xh, xl
+    xs[:, 3 * D] = 1.0
+    xs[:, 3 * D + 1] = ch_
+    lane, j, sp = np.arange(64), np.arange(8), _sum_points()
+    S = np.zeros((xi.shape[0], 16 * NG))
+    for ch in range(n_chunks):
+        kexp = np.zeros((32, 16 * NK))
+        for kk in range(NK):
+            kexp[(lane & 31)[:, None], 16 * kk + 8 * (lane >> 5)[:, None] + j] = tab[ch, 64 * kk:64 * (kk + 1)]
+        m = np.exp2(xs @ kexp.T)                                # [n, 32 points]
+        mh = m.astype(np.float16).astype(np.float64)
+        ms = mh + (m - mh).astype(np.float16).astype(np.float64)
+        A = np.zeros((16 * NG, 32))
+        for g in range(NG):
+            for qq in range(2):
+                for hh in range(2):
+                    o = 64 * NK + 128 * g + 64 * qq + 32 * hh
+                    A[16 * g:16 * g + 16, sp[qq, hh]] = tab[ch, o:o + 16] + tab[ch, o + 16:o + 32]
+        S += ms @ A.T
+    return S[:, :F] * (scale * np.exp2(c - ch_))[:, None] / np.asarray(field_scale, dtype=np.float64)[None, :]
+
+
+def hessian_from_sums(S, lam, xi):
+    """``(f - offset, d2f/dx2 [n, D, D])`` from the sums in B units (the
+    kernel's per-lane assembly): with a_u = lambda_u xi_u, G_v = ln2 S_v and
+    G_uv = ln2^2 S_uv, H_uv = a_u a_v S0 - a_u G_v - a_v G_u + G_uv - delta_uv lambda_u S0."""
+    lam = np.asarray(lam, dtype=np.float64)
+    D = lam.size
+    ln2 = np.log(2.0)
+    S0, G = S[:, 0], ln2 * S[:, 1:1 + D]
+    a = lam[None, :] * xi
+    H = np.empty((S.shape[0], D, D))
+    for t, (u, v) in enumerate(_hess_pairs(D)):
+        H[:, u, v] = H[:, v, u] = a[:, u] * a[:, v] * S0 - a[:, u] * G[:, v] - a[:, v] * G[:, u] + \
+            ln2 * ln2 * S[:, 1 + D + t] - (lam[u] * S0 if u == v else 0.0)
+    return S0, H
+
+
+# --------------------------------------------------------------------------
 # line tables (csrc/kf_gp_mfma.h line_pos / line_eval)
 #
 # The first Gauss-Newton iteration of a date is linearised at the forecast

@@ -1293,12 +1293,103 @@ def operator_eval(n_params, bands: BandTable, band: int, x, h0, h=None, ok=None,
                         0 if h is None else h.shape[1], _ptr(ok), _dev(x), _stream(x))
 
 
-def hessian(n_params, bands: BandTable, x, a, N=None):
-    """K6: A -= sum_b w (y - f) d2f/dx2 over GP bands (in place)."""
+HESSIAN_GP = ("valu", "mfma")
+# the kernel the last hessian() launch on a device took (ext().hessian_plan: name, family, template arguments)
+LAST_HESSIAN_PLAN = None
+_HESSIAN_CACHE: dict = {}
+
+
+def hessian_fields(bands: BandTable, dev):
+    """Per-band side arrays of the matrix-core Hessian launch (kf_core.h HessianMfmaArgs): one ``(table,
+    multipliers, n_chunks, scale)`` per band, None for a band without a table (not a GP, no records, or values
+    outside f16: models/gp.py ``mfma_hessian_tables``).  Built once per band spec and device and kept there; the
+    multipliers undo the field scales and carry ln2 (B_d fields) and ln2^2 (B_u B_v fields)."""
+    out = []
+    specs = bands.specs if len(bands.specs) == bands.n else (None,) * bands.n
+    for sp in specs:
+        if sp is None or getattr(sp, "kind", None) != OP_GP or getattr(sp, "records", None) is None:
+            out.append(None)
+            continue
+        key = (id(sp), str(dev))
+        hit = _HESSIAN_CACHE.get(key)
+        if hit is None:
+            from ..models.gp import mfma_hessian_tables
+
+            r = mfma_hessian_tables(sp.records, sp.gp_pos_pairs, sp.coef)
+            val = None
+            if r is not None:
+                d = int(sp.d)
+                ln2 = np.log(2.0)
+                mul = np.concatenate([[1.0], np.full(d, ln2), np.full(d * (d + 1) // 2, ln2 * ln2)]) / r[3]
+                val = (torch.from_numpy(np.ascontiguousarray(r[0]).view(np.int16)).to(dev),
+                       torch.from_numpy(mul.astype(np.float32)).to(dev), int(r[1]), float(r[2]))
+            if len(_HESSIAN_CACHE) >= 64:
+                _HESSIAN_CACHE.clear()
+            hit = _HESSIAN_CACHE[key] = (sp, val)   # the spec is held so its id stays unique
+        out.append(hit[1])
+    return out
+
+
+def _hessian_side(fields):
+    return ([0 if f is None else _ptr(f[0]) for f in fields], [0 if f is None else _ptr(f[1]) for f in fields],
+            [0 if f is None else f[2] for f in fields], [0.0 if f is None else f[3] for f in fields])
+
+
+def hessian_plan(n_params, bands: BandTable, device, fields=None):
+    """The kernel ``hessian(gp="mfma")`` takes for ``bands`` on ``device`` (kf_plan.h ``hessian_plan``).  On a
+    CPU ``device`` the tables are not built: the host has no matrix-core kernel whatever they are."""
+    dev = torch.device(device)
+    on = dev.type == "cuda" and len(bands.descs) == bands.n
+    if fields is None:
+        fields = hessian_fields(bands, dev) if on else [None] * bands.n
+    return ext().hessian_plan(int(n_params), list(bands.descs) if on else [], *(_hessian_side(fields) if on else
+                                                                                 ([], [], [], [])), on)
+
+
+def hessian_mfma_unsupported(n_params, bands: BandTable, device):
+    """Why ``hessian(gp="mfma")`` cannot serve this table on this device, or None where it can."""
+    if torch.device(device).type != "cuda":
+        return "the matrix-core Hessian kernel has no host twin (device tensors only)"
+    if n_params not in SUPPORTED_NP:
+        return f"n_params={n_params} has no compiled kernel"
+    if hessian_plan(n_params, bands, device)["family"] != "hessian_mfma_kernel":
+        return (f"no matrix-core Hessian kernel for {bands.n} band(s) of a {n_params}-parameter state: it takes 7 "
+                "parameters with 4-input GP bands or 10 parameters with 10-input GP bands, every GP band with a "
+                "Hessian table")
+    return None
+
+
+def hessian_mfma_supported(n_params, bands: BandTable, device) -> bool:
+    return hessian_mfma_unsupported(n_params, bands, device) is None
+
+
+def hessian(n_params, bands: BandTable, x, a, N=None, gp="valu"):
+    """K6: A -= sum_b w (y - f) d2f/dx2 over GP bands (in place).
+
+    ``gp="mfma"`` forms the sums of every GP band on the matrix cores (kf_gp_mfma.h ``pixel_hessian_mfma``)
+    instead of the thread-per-pixel VALU record loop: the JRC-TIP and the 10-parameter GP tables on a device,
+    and a ValueError with the reason for anything else (:func:`hessian_mfma_supported` asks without raising).
+    The correction differs from the VALU loop's by the rounding of the sums.  The kernel taken is recorded in
+    ``LAST_HESSIAN_PLAN``."""
     check_np(n_params)
+    if gp not in HESSIAN_GP:
+        raise ValueError("gp must be 'valu' or 'mfma'")
     N = int(x.shape[1] if N is None else N)
     _check_soa(x, n_params, N, "x")
     _check_soa(a, ntri(n_params), N, "a", device=x.device)
+    global LAST_HESSIAN_PLAN
+    if gp == "mfma":
+        why = hessian_mfma_unsupported(n_params, bands, x.device)
+        if why is not None:
+            raise ValueError(f"hessian(gp='mfma'): {why}")
+        if a.shape[1] != x.shape[1]:
+            raise ValueError("x and a must share their row stride")
+        fields = hessian_fields(bands, x.device)
+        LAST_HESSIAN_PLAN = hessian_plan(n_params, bands, x.device, fields)
+        ext().hessian_mfma(n_params, bands.ptr, list(bands.descs), *_hessian_side(fields), _ptr(x), _ptr(a), N,
+                           x.shape[1], _stream(x))
+        return
+    LAST_HESSIAN_PLAN = ext().hessian_plan(int(n_params), [], [], [], [], [], False) if _dev(x) else None
     ext().hessian(n_params, bands.ptr, bands.n, _ptr(x), _ptr(a), N, x.shape[1], _dev(x), _stream(x))
 
 
