@@ -490,6 +490,7 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
   // marginal std rasters: sqrt(diag(P)) from the precision (MARG_PRECISION) or covariance rows
   m.attr("MARG_PRECISION") = MARG_PRECISION;
   m.attr("MARG_COVARIANCE") = MARG_COVARIANCE;
+  m.attr("MARG_VARIANCE") = MARG_VARIANCE;
   m.def("marginal", [](int np, uintptr_t x, uintptr_t p, int kind, int64_t N, int64_t ld, uintptr_t idx,
                        uintptr_t mean, uintptr_t unc, int64_t plane, bool device, uintptr_t stream) {
     const RasterArgs a = raster_args(x, p, kind, N, ld, idx, mean, unc, plane);
@@ -555,6 +556,34 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     }
     if (device) check_hip(dev_smooth(np, a, (hipStream_t)stream), "smooth");
     else check_host(host_smooth(np, a), "smooth");
+  });
+  // ... for one propagated parameter j (kf_core.h pixel_smooth_r1): the carried planes (cx, cv) instead of a
+  // smoothed state; cx_in = cv_in = 0: the last step; p_out (rows of `kind`) and var_out optional; q_pix: [np][ld]
+  m.def("smooth_r1", [](int np, uintptr_t x_a, uintptr_t p_a, int kind, int j, float mj, float qj, uintptr_t q_pix,
+                        uintptr_t cx_in, uintptr_t cv_in, uintptr_t x_out, uintptr_t cx_out, uintptr_t cv_out,
+                        uintptr_t status, uintptr_t p_out, uintptr_t var_out, int64_t N, int64_t ld, bool device,
+                        uintptr_t stream) {
+    if (np < 1 || np > MAX_D || j < 0 || j >= np) throw std::invalid_argument("smooth_r1: j outside the state");
+    SmoothR1Args a{};
+    a.N = N;
+    a.ld = ld;
+    a.kind = kind;
+    a.j = j;
+    a.m = mj;
+    a.q = qj;
+    a.x_a = P<const float>(x_a);
+    a.p_a = P<const float>(p_a);
+    a.q_pix = q_pix ? P<const float>(q_pix) + (int64_t)j * ld : nullptr;
+    a.cx_in = P<const float>(cx_in);
+    a.cv_in = P<const float>(cv_in);
+    a.x_out = P<float>(x_out);
+    a.cx_out = P<float>(cx_out);
+    a.cv_out = P<float>(cv_out);
+    a.status = P<uint8_t>(status);
+    a.p_out = P<float>(p_out);
+    a.var_out = P<float>(var_out);
+    if (device) check_hip(dev_smooth_r1(np, a, (hipStream_t)stream), "smooth_r1");
+    else check_host(host_smooth_r1(np, a), "smooth_r1");
   });
   // innovation statistics and the chi-square gate (kf_core.h pixel_innovation): z [nb][ldz], chi2 / nobs /
   // nrej / status [N]; screened: nb plane pointers (device memory on the device) or null

@@ -793,7 +793,8 @@ struct RasterArgs {
   int64_t N, ld;
   const float* x;        // [NP][ld]
   const float* p;        // [NT][ld] packed rows (unpack: P^-1; marginal: see kind)
-  int32_t kind;          // marginal only: MARG_PRECISION / MARG_COVARIANCE
+  int32_t kind;          // marginal only: MARG_PRECISION / MARG_COVARIANCE, or MARG_VARIANCE, under which
+                         // p is [NP][ld] rows of diag(P) and not packed rows; unpack refuses that kind
   const int64_t* idx;    // [N] raster cell of each pixel, or null
   float* mean;           // [NP][plane] or null
   float* unc;            // [NP][plane] or null
@@ -822,8 +823,11 @@ KF_PIXEL_OP(OpUnpack, RasterArgs, pixel_unpack);
 //     is not finite and positive, gets NaN in all NP planes.
 //   MARG_COVARIANCE: P itself (the gain form's state); only the diagonal rows
 //     are read, NaN where an entry is not finite and positive.
+//   MARG_VARIANCE (this pass only): NP rows [NP][ld] of diag(P), as pixel_smooth_r1
+//     writes them (var_out); the same rule per entry.
 constexpr int MARG_PRECISION = 0;
 constexpr int MARG_COVARIANCE = 1;
+constexpr int MARG_VARIANCE = 2;
 template <int NP>
 KF_HD void pixel_marginal(const RasterArgs& a, int64_t p) {
   constexpr int NT = ntri(NP);
@@ -841,7 +845,10 @@ KF_HD void pixel_marginal(const RasterArgs& a, int64_t p) {
   if (!unc) return;
   float d[NP];
   bool ok = true;
-  if (kind == MARG_COVARIANCE) {
+  if (kind == MARG_VARIANCE) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) d[j] = p_in[j * ld + p];
+  } else if (kind == MARG_COVARIANCE) {
 #pragma unroll
     for (int j = 0; j < NP; ++j) d[j] = p_in[tri(NP, j, j) * ld + p];
   } else {
@@ -1239,6 +1246,223 @@ KF_HD void pixel_smooth(const SmoothArgs& a, int64_t p) {
   a.status[p3] = ok ? 0 : 1;
 }
 KF_PIXEL_OP(OpSmooth, SmoothArgs, pixel_smooth);
+
+// float64 twin of chol_inv_diag (the smoother's marginal variances of a precision block)
+template <int NP>
+KF_HD void chol_inv_diag_f64(const double (&U)[ntri(NP)], float (&d)[NP]) {
+#pragma unroll
+  for (int c = 0; c < NP; ++c) {
+    double z[NP];
+    z[c] = U[tri(NP, c, c)];
+    double s = z[c] * z[c];
+#pragma unroll
+    for (int i = c + 1; i < NP; ++i) {
+      double t = 0.0;
+#pragma unroll
+      for (int k = c; k < i; ++k) t = fma(-U[tri(NP, k, i)], z[k], t);
+      z[i] = t * U[tri(NP, i, i)];
+      s = fma(z[i], z[i], s);
+    }
+    d[c] = (float)s;   // rounded once
+    smooth_row_done();
+  }
+}
+
+// The RTS step of pixel_smooth for a propagated set of one parameter, J = {j}
+// (the LAI propagator, a prior reset with one carried parameter): P_p is the
+// scalar s and the gain has one non-zero column, so with m = m_j, q = q_j and
+// (cx, cv) = the smoothed (x[j], P[j, j]) of step t + 1, the only things step
+// t + 1 hands back,
+//   v = P_a[:, j], pjj = v_j, s = m^2 pjj + q, g = v m / s, D = cv - s,
+//   x_s = x_a + g (cx - m x_a[j]),         P_s = P_a + D g g^T,
+//   cx' = x_s[j], cv' = pjj + D g_j^2      (handed to step t - 1),
+// and P_s^-1 = L_a - kappa e_j e_j^T, kappa = D m^2 / (s q + cv m^2 pjj): a
+// precision-kind state stays precision kind with one entry changed (Sherman-
+// Morrison; s^2 + D m^2 pjj = s q + cv m^2 pjj, a sum of positive terms).
+//   MARG_PRECISION: one float64 factorisation of the rows, one solve for e_j (v,
+//     rounded once), chol_inv_diag_f64 where var_out is asked for.  P_a is never
+//     formed; the float32 rows die into the float64 factor as they are loaded
+//     and are loaded again, one at a time, for p_out.
+//   MARG_COVARIANCE: the float32 factorisation is pixel_smooth's SPD test only;
+//     v is read from the rows of column j.
+// Both optional outputs null: x_s, the status and the two carried planes are all that is
+// written.  cx_in == cv_in == null: the last step of the run, x_s = x_a, the rows
+// unchanged, (cx', cv') = (x_a[j], pjj).
+// Fallback (status 1, else 0): an input that is not finite, a filtered block
+// that is not SPD, s <= 0, a kappa denominator that is not positive and finite
+// (this also covers cv' <= 0: cv' = pjj + D (m pjj / s)^2 = pjj den / s^2 with den = s q + cv m^2 pjj),
+// or a result that is not finite gives x_s = x_a, the rows unchanged
+// (NaN rows where the filtered block is not SPD), var_out = diag(P_a),
+// cx' = x_a[j] and cv' = pjj (NaN where the block is not SPD).
+struct SmoothR1Args {
+  int64_t N, ld;
+  int32_t kind;          // MARG_PRECISION / MARG_COVARIANCE: what p_a (and p_out) hold
+  int32_t j;             // the propagated parameter
+  float m, q;            // m_j, q_j
+  const float* x_a;      // [NP][ld]
+  const float* p_a;      // [NT][ld]
+  const float* q_pix;    // optional per-pixel q_j [N]
+  const float* cx_in;    // [N] smoothed x[j] of step t + 1, or null (with cv_in): the last step
+  const float* cv_in;    // [N] smoothed P[j, j] of step t + 1
+  float* x_out;          // [NP][ld]
+  float* cx_out;         // [N]
+  float* cv_out;         // [N]
+  uint8_t* status;       // [N]
+  float* p_out;          // [NT][ld] of `kind`, or null
+  float* var_out;        // [NP][ld] diag(P_s), or null
+};
+// a launch's arguments: every pointer but the optional ones set, the carried inputs both or neither,
+// N within the rows, j within the state, p_out not p_a (the covariance rows are stored as formed and
+// p_a is read again for a pixel that falls back)
+inline bool smooth_r1_args_ok(int np, const SmoothR1Args& a) {
+  if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return false;
+  if (a.N < 0 || a.N > a.ld || np < 1 || np > MAX_D || a.j < 0 || a.j >= np) return false;
+  if ((a.cx_in == nullptr) != (a.cv_in == nullptr)) return false;
+  if (a.p_out && a.p_out == a.p_a) return false;
+  return a.x_a && a.p_a && a.x_out && a.cx_out && a.cv_out && a.status;
+}
+
+template <int NP, bool VAR>
+KF_HD void pixel_smooth_r1(const SmoothR1Args& a, int64_t p) {
+  constexpr int NT = ntri(NP);
+  KF_DCHECK(p >= 0 && p < a.N && a.N <= a.ld && a.j >= 0 && a.j < NP);
+  const int64_t ld = a.ld;
+  const int j = a.j;
+  const int tjj = tri(NP, j, j);
+  const bool prec = a.kind == MARG_PRECISION, last = a.cx_in == nullptr;
+  const float nan = __builtin_nanf("");
+  // one opaque copy of p per phase (pixel_smooth): row addresses are formed where they are used
+  const int64_t p0 = opaque_lane(p);
+  // v = P_a[:, j] and the SPD test; pd = diag(P_a) of a precision block where var_out wants it
+  float v[NP], pd[NP], pjj;
+  bool fin = true, spd_a;
+  if (prec) {
+    double U[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const float r = a.p_a[t * ld + p0];
+      fin = fin && finitef(r);
+      U[t] = (double)r;
+    }
+    spd_a = chol_packed_f64<NP>(U);
+    double e[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) e[i] = (i == j) ? 1.0 : 0.0;
+    chol_solve_f64<NP>(U, e);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) v[i] = (float)e[i];
+    pjj = gather_state_u<NP>(v, j);
+    if (VAR) {
+      smooth_row_done();
+      chol_inv_diag_f64<NP>(U, pd);
+    }
+  } else {
+    float U[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      U[t] = a.p_a[t * ld + p0];
+      fin = fin && finitef(U[t]);
+    }
+    spd_a = chol_packed<NP>(U);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) v[i] = a.p_a[(i <= j ? tri(NP, i, j) : tri(NP, j, i)) * ld + p0];
+    pjj = a.p_a[tjj * ld + p0];
+  }
+  const bool have = fin && spd_a && pjj > 0.f && finitef(pjj);   // the filtered block and pjj are usable
+  // the scalars of the step, in float64 from the rounded pjj
+  const int64_t p1 = opaque_lane(p);
+  float xa[NP];
+  bool ok = have;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    xa[i] = a.x_a[i * ld + p1];
+    ok = ok && finitef(xa[i]);
+  }
+  const float xaj = a.x_a[j * ld + p1];
+  float gs = 0.f, D = 0.f, dx = 0.f, kap = 0.f;
+  if (!last) {
+    const float m = a.m, q = a.q_pix ? a.q_pix[p1] : a.q;
+    const float cx = a.cx_in[p1], cv = a.cv_in[p1];
+    ok = ok && finitef(m) && finitef(q) && finitef(cx) && finitef(cv);
+    const double mm = (double)m * (double)m, pj = (double)pjj;
+    const double s = fma(mm, pj, (double)q);
+    const double den = fma(s, (double)q, (double)cv * mm * pj);
+    ok = ok && (s > 0.0) && (den > 0.0) && __builtin_isfinite(den);
+    const double Dd = (double)cv - s;
+    gs = (float)((double)m / (ok ? s : 1.0));
+    D = (float)Dd;
+    kap = (float)(Dd * mm / (ok ? den : 1.0));
+    dx = fmaf(-m, xaj, cx);
+  }
+  float g[NP], xs[NP];
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    g[i] = v[i] * gs;
+    xs[i] = last ? xa[i] : fmaf(g[i], dx, xa[i]);
+    ok = ok && finitef(xs[i]);
+  }
+  const float gj = pjj * gs, xsj = last ? xaj : fmaf(gj, dx, xaj);
+  const float cvs = last ? pjj : fmaf(D * gj, gj, pjj);
+  ok = ok && finitef(cvs);
+  // diag(P_a) for var_out, and the one precision entry that changes
+  const int64_t p2 = opaque_lane(p);
+  float ljj = 0.f;
+  if (VAR) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      if (!prec) pd[i] = a.p_a[tri(NP, i, i) * ld + p2];
+      ok = ok && finitef(fmaf(D * g[i], g[i], pd[i]));
+    }
+  }
+  if (a.p_out && prec) {
+    ljj = a.p_a[tjj * ld + p2];
+    ok = ok && finitef(ljj - kap);
+  }
+  // the rows: each loaded immediately before its store.  Precision kind: a copy but for (j, j),
+  // final as stored; covariance kind: stored as formed, a pixel that falls back overwrites them below
+  const int64_t p3 = opaque_lane(p);
+  if (a.p_out) {
+    if (prec) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        float r = a.p_a[t * ld + p3];
+        if (t == tjj && ok && !last) r = ljj - kap;
+        a.p_out[t * ld + p3] = spd_a ? r : nan;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+#pragma unroll
+        for (int k = i; k < NP; ++k) {
+          const int t = tri(NP, i, k);
+          const float r = a.p_a[t * ld + p3];
+          const float w = last ? r : fmaf(D * g[i], g[k], r);
+          ok = ok && finitef(w);
+          a.p_out[t * ld + p3] = w;
+        }
+      if (!ok) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) a.p_out[t * ld + p3] = spd_a ? a.p_a[t * ld + p3] : nan;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    a.x_out[i * ld + p3] = ok ? xs[i] : xa[i];
+    if (VAR) a.var_out[i * ld + p3] = ok && !last ? fmaf(D * g[i], g[i], pd[i]) : (fin && spd_a ? pd[i] : nan);
+  }
+  a.cx_out[p3] = ok ? xsj : xaj;
+  a.cv_out[p3] = ok ? cvs : (have ? pjj : nan);
+  a.status[p3] = ok ? 0 : 1;
+}
+// VAR: the launch writes var_out.  Two kernels: with the choice made at run time in one kernel the
+// NP = 10 instantiation takes 214 VGPRs, as two it takes 184 each
+template <bool VAR>
+struct OpSmoothR1 {
+  using Args = SmoothR1Args;
+  template <int NP>
+  static KF_HD void px(const Args& a, int64_t p) { pixel_smooth_r1<NP, VAR>(a, p); }
+};
 
 KF_HD float bf16_to_f32(uint16_t b) {
   const uint32_t u = (uint32_t)b << 16;

@@ -369,13 +369,17 @@ int host_invert(int np, const InvertArgs& a) { return host_pixels<OpInvert>(np, 
 int host_operator(int np, const OperatorArgs& a) { return host_pixels<OpOperator>(np, a); }
 int host_gp_operator(int np, const GpOperatorArgs& a) { return host_pixels<OpGpOperatorHost>(np, a); }
 int host_hessian(int np, const HessianArgs& a) { return host_pixels<OpHessian>(np, a); }
-int host_unpack(int np, const RasterArgs& a) { return host_pixels<OpUnpack>(np, a); }
+int host_unpack(int np, const RasterArgs& a) { return a.kind == MARG_VARIANCE ? -1 : host_pixels<OpUnpack>(np, a); }
 int host_marginal(int np, const RasterArgs& a) {
-  if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return -1;
+  if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE && a.kind != MARG_VARIANCE) return -1;
   return host_pixels<OpMarginal>(np, a);
 }
 int host_product(int np, const ProductArgs& a) { return product_args_ok(np, a) ? host_pixels<OpProduct>(np, a) : -1; }
 int host_smooth(int np, const SmoothArgs& a) { return smooth_args_ok(np, a) ? host_pixels<OpSmooth>(np, a) : -1; }
+int host_smooth_r1(int np, const SmoothR1Args& a) {
+  if (!smooth_r1_args_ok(np, a)) return -1;
+  return a.var_out ? host_pixels<OpSmoothR1<true>>(np, a) : host_pixels<OpSmoothR1<false>>(np, a);
+}
 int host_innovation(int np, const InnovationArgs& a) {
   if (!innovation_args_ok(np, a) || a.prop) return -1;   // the fused-forecast check is a device kernel only
   return innovation_joint(a) ? host_pixels<OpInnovation<true>>(np, a) : host_pixels<OpInnovation<false>>(np, a);

@@ -636,9 +636,11 @@ hipError_t dev_propagate(int np, const PropArgs& a, hipStream_t s) { return laun
 hipError_t dev_invert(int np, const InvertArgs& a, hipStream_t s) { return launch_pixels<OpInvert>(np, a, s); }
 hipError_t dev_operator(int np, const OperatorArgs& a, hipStream_t s) { return launch_pixels<OpOperator>(np, a, s); }
 hipError_t dev_hessian(int np, const HessianArgs& a, hipStream_t s) { return launch_pixels<OpHessian>(np, a, s); }
-hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s) { return launch_pixels<OpUnpack>(np, a, s); }
+hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s) {
+  return a.kind == MARG_VARIANCE ? hipErrorInvalidValue : launch_pixels<OpUnpack>(np, a, s);
+}
 hipError_t dev_marginal(int np, const RasterArgs& a, hipStream_t s) {
-  if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE) return hipErrorInvalidValue;
+  if (a.kind != MARG_PRECISION && a.kind != MARG_COVARIANCE && a.kind != MARG_VARIANCE) return hipErrorInvalidValue;
   return launch_pixels<OpMarginal>(np, a, s);
 }
 hipError_t dev_product(int np, const ProductArgs& a, hipStream_t s) {
@@ -646,6 +648,10 @@ hipError_t dev_product(int np, const ProductArgs& a, hipStream_t s) {
 }
 hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s) {
   return smooth_args_ok(np, a) ? launch_pixels<OpSmooth>(np, a, s) : hipErrorInvalidValue;
+}
+hipError_t dev_smooth_r1(int np, const SmoothR1Args& a, hipStream_t s) {
+  if (!smooth_r1_args_ok(np, a)) return hipErrorInvalidValue;
+  return a.var_out ? launch_pixels<OpSmoothR1<true>>(np, a, s) : launch_pixels<OpSmoothR1<false>>(np, a, s);
 }
 hipError_t dev_innovation(int np, const InnovationArgs& a, const KernelPlan& plan, hipStream_t s) {
   if (!innovation_args_ok(np, a) || plan.np != np || plan.joint != innovation_joint(a)) return hipErrorInvalidValue;

@@ -56,6 +56,7 @@ hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s);
 hipError_t dev_marginal(int np, const RasterArgs& a, hipStream_t s);       // a.kind: MARG_*
 hipError_t dev_product(int np, const ProductArgs& a, hipStream_t s);       // physical-unit planes, interval, QA byte
 hipError_t dev_smooth(int np, const SmoothArgs& a, hipStream_t s);         // one backward step of the RTS smoother
+hipError_t dev_smooth_r1(int np, const SmoothR1Args& a, hipStream_t s);    // ... for one propagated parameter
 // statistics and the chi-square gate; plan: innovation_plan's kernel for a (kf_plan.h), the VALU pixel_kernel
 // or one of the matrix-core kernels of kf_innovation_mfma.hip
 hipError_t dev_innovation(int np, const InnovationArgs& a, const KernelPlan& plan, hipStream_t s);
@@ -103,6 +104,7 @@ int host_unpack(int np, const RasterArgs& a);
 int host_marginal(int np, const RasterArgs& a);
 int host_product(int np, const ProductArgs& a);
 int host_smooth(int np, const SmoothArgs& a);
+int host_smooth_r1(int np, const SmoothR1Args& a);
 int host_innovation(int np, const InnovationArgs& a);
 // obs_order chunk: pixels per scatter workgroup; local = 1 partitions each
 // chunk on its own (no count / scan passes, chunk-aligned, see kf_kernels.hip)

@@ -152,6 +152,11 @@ class EngineConfig:
     # two it took ("forecast"); a default run's entry carries no such key
     # (--innovation-forecast)
     innovation_forecast: str = "materialised"  # 'materialised' | 'fused'
+    # LinearKalman.smooth: 'dense' takes pixel_smooth for every propagator; 'rank_one' takes the
+    # rank-one kernel (pixel_smooth_r1: two carried planes, the smoothed state in the filtered
+    # state's own kind) where the propagator carries exactly one parameter (the LAI propagator, a
+    # prior reset with one carried parameter) and the dense kernel for every other link
+    smoother_form: str = "dense"              # 'dense' | 'rank_one'
     metrics_path: str | None = None           # JSONL metrics (per date / timestep)
     checkpoint_dir: str | None = None
     checkpoint_every: int = 0                 # timesteps between checkpoints (0: off)
@@ -190,6 +195,8 @@ class EngineConfig:
             raise ValueError("hessian_gp must be 'valu' or 'mfma'")
         if self.innovation_forecast not in ("materialised", "fused"):
             raise ValueError("innovation_forecast must be 'materialised' or 'fused'")
+        if self.smoother_form not in ("dense", "rank_one"):
+            raise ValueError("smoother_form must be 'dense' or 'rank_one'")
         if self.store_precision not in ("auto", "always"):
             raise ValueError("store_precision must be 'auto' or 'always'")
         if isinstance(self.convergence_chunk, str) and self.convergence_chunk.strip().lower() in ("", "0", "tile",

@@ -108,11 +108,14 @@ class SmootherMixin:
             raise FileNotFoundError(f"smooth(): no committed checkpoint under {root}")
         return [(t, (lambda p=p: CheckpointManager.load(p, self)[0])) for t, p in found]
 
-    def _smooth_dump(self, output, timestep, state: KFState):
+    def _smooth_dump(self, output, timestep, state: KFState, var=None):
         if output is None:
             return
         if hasattr(output, "dump_state"):
-            output.dump_state(timestep, state, self)
+            if var is not None:
+                output.dump_state(timestep, state, self, marginal_var=var)
+            else:
+                output.dump_state(timestep, state, self)
             return
         x, P = state.to_reference()
         if state.kind == COVARIANCE:
@@ -129,12 +132,17 @@ class SmootherMixin:
         checkpoint_keep=0``) or an explicit list ``states`` of
         ``(timestep, KFState)``.  The steps are walked backward with the running
         smoothed state on the device; each step's smoothed state, a ``KFState``
-        of kind covariance, is written to ``output`` (any output class; every
+        of kind covariance (under ``smoother_form='rank_one'`` with one
+        propagated parameter: of the filtered state's own kind, only the two
+        planes of that parameter carried between the steps; a step between the
+        first and the last without an ``output`` then keeps the filtered rows),
+        is written to ``output`` (any output class; every
         option of it applies as in a forward run).  Each rank smooths its own
         strip; no collective is involved.
 
         Returns ``(state, records)``: the earliest step's smoothed state and one
         record per step in time order, ``{"timestep", "fallback_pixels",
+        "kernel" ('dense', 'rank_one' or 'none': the step launched nothing),
         "load_s", "kernel_s", "output_s"}`` (wall times, the device
         synchronised between them; from checkpoints also ``read_s`` and
         ``h2d_s``, the parts of ``load_s``); ``fallback_pixels`` counts this
@@ -146,8 +154,17 @@ class SmootherMixin:
         ``spatial_gamma > 0`` and for a propagator without a ``device_spec``;
         ``FileNotFoundError`` when a step of the run has no committed checkpoint."""
         mask, m, q = self._smoother_link()
+        # one propagated parameter under smoother_form='rank_one': pixel_smooth_r1, two carried planes
+        r1 = self.config.smoother_form == "rank_one" and bin(mask).count("1") == 1
         if output is not None and getattr(output, "uncertainty", "conditional") not in ("conditional", "marginal"):
             raise ValueError("output.uncertainty must be 'conditional' or 'marginal'")
+        if r1:
+            j = mask.bit_length() - 1
+            carried = None
+            # the project's device outputs take diag(P_s) from the kernel for their marginal std rasters
+            # (any other output class is handed the state and inverts as after the dense kernel)
+            from ..input_output.output import DeviceOutput, KafkaOutput
+            want_var = isinstance(output, (DeviceOutput, KafkaOutput)) and output.uncertainty == "marginal"
         source = self._smoother_source(checkpoint_dir, states)
         n = self.n_params
         sync = (lambda: torch.cuda.synchronize(self.device)) if self.device.type == "cuda" else (lambda: None)
@@ -164,8 +181,31 @@ class SmootherMixin:
             sync()
             t1 = time.perf_counter()
             n_fb = 0
+            var = None
+            kernel = "none"
             if mask == 0:
                 cur = filt
+            elif r1 and self.N > 0:
+                # every step, the last one included (carried None): the smoothed state in the filtered
+                # state's own kind; its rows only where something reads them
+                ld = filt.x.shape[1]
+                q_pix = self._q_pix
+                if q_pix is not None and q_pix.shape[1] != ld:
+                    q_pix = _pad_rows(q_pix, ld)
+                rows = output is not None or i == 0
+                cur = KFState.empty(n, self.N, self.device, filt.kind, ld=ld) if rows else \
+                    KFState(torch.empty_like(filt.x), filt.P, filt.kind, self.N)
+                var = torch.empty_like(filt.x) if want_var else None
+                out = (torch.empty(self.N, dtype=torch.float32, device=self.device),
+                       torch.empty(self.N, dtype=torch.float32, device=self.device))
+                status = torch.empty(self.N, dtype=torch.uint8, device=self.device)
+                K.smooth_r1(n, filt.x, filt.P, cur.x, out[0], out[1], status, kind=filt.kind, j=j, m=m[j], q=q[j],
+                            q_pix=q_pix, cx_in=None if carried is None else carried[0],
+                            cv_in=None if carried is None else carried[1], p_out=cur.P if rows else None,
+                            var_out=var, N=self.N)
+                carried = out
+                n_fb = int(status.count_nonzero().item())
+                kernel = "rank_one"
             elif nxt is None or self.N == 0:
                 cur = self._as_kind(filt, COVARIANCE)
             else:
@@ -180,12 +220,13 @@ class SmootherMixin:
                 K.smooth(n, filt.x, filt.P, nxt.x, nxt.P, cur.x, cur.P, status, kind=filt.kind, prop_mask=mask,
                          m=m, q=q, q_pix=q_pix, N=self.N)
                 n_fb = int(status.count_nonzero().item())
+                kernel = "dense"
             sync()
             t2 = time.perf_counter()
-            self._smooth_dump(output, timestep, cur)
+            self._smooth_dump(output, timestep, cur, var)
             sync()
             t3 = time.perf_counter()
-            rec = {"event": "smooth", "timestep": timestep.isoformat(), "fallback_pixels": n_fb,
+            rec = {"event": "smooth", "timestep": timestep.isoformat(), "fallback_pixels": n_fb, "kernel": kernel,
                    "load_s": t1 - t0, "kernel_s": t2 - t1, "output_s": t3 - t2}
             if states is None:
                 rec.update({k: v for k, v in getattr(self, "last_checkpoint_load", {}).items() if k != "bytes"})

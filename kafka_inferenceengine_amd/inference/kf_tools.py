@@ -292,6 +292,53 @@ def rts_smooth_blocks(x_a, blocks_a, x_next, P_next, mask, m, q, kind="precision
     return x_s, 0.5 * (P_s + P_s.transpose(0, 2, 1))
 
 
+def rts_smooth_rank_one_blocks(x_a, blocks_a, cx, cv, j, m, q, kind="precision"):
+    """The backward step for a single propagated parameter ``j``, in float64,
+    from its scalar formulas (``csrc/kf_core.h pixel_smooth_r1``; nothing is
+    shared with ``rts_smooth_blocks``, which must give the same numbers).
+
+    ``x_a`` [N, n], ``blocks_a`` [N, n, n] of ``kind``; ``cx`` / ``cv`` [N]: the
+    smoothed x[j] and P[j, j] of step t + 1 (both None: the last step);
+    ``m`` / ``q``: scalars m_j and q_j, ``q`` also [N].  With v = P_a[:, j],
+    pjj = v_j::
+
+        s = m^2 pjj + q      g = v m / s      D = cv - s
+        x_s = x_a + g (cx - m x_a[j])         P_s = P_a + D g g^T
+        L_s = L_a - kappa e_j e_j^T,  kappa = D m^2 / (s q + cv m^2 pjj)
+
+    Returns a dict: ``x`` [N, n]; ``blocks`` [N, n, n] of ``kind`` (P_s, or the
+    precision L_s); ``var`` [N, n] = diag(P_s); ``cx`` = x_s[:, j] and ``cv`` =
+    P_s[:, j, j] for step t - 1."""
+    if kind not in ("precision", "covariance"):
+        raise ValueError("kind must be 'precision' or 'covariance'")
+    x_a = np.asarray(x_a, dtype=np.float64)
+    N, n = x_a.shape
+    A = np.asarray(blocks_a, dtype=np.float64).reshape(N, n, n)
+    e = np.zeros(n)
+    e[j] = 1.0
+    if kind == "precision":
+        v = np.linalg.solve(A, np.broadcast_to(e, (N, n))[:, :, None])[:, :, 0]
+        var = np.diagonal(np.linalg.inv(A), axis1=1, axis2=2).copy()
+    else:
+        v = A[:, :, j].copy()
+        var = np.diagonal(A, axis1=1, axis2=2).copy()
+    pjj = v[:, j]
+    if cx is None and cv is None:
+        return dict(x=x_a.copy(), blocks=A.copy(), var=var, cx=x_a[:, j].copy(), cv=pjj.copy())
+    cx, cv = np.asarray(cx, dtype=np.float64), np.asarray(cv, dtype=np.float64)
+    m, q = float(m), np.broadcast_to(np.asarray(q, dtype=np.float64), (N,))
+    s = m * m * pjj + q
+    g = v * (m / s)[:, None]
+    D = cv - s
+    x_s = x_a + g * (cx - m * x_a[:, j])[:, None]
+    out = A.copy()
+    if kind == "precision":
+        out[:, j, j] -= D * m * m / (s * q + cv * m * m * pjj)
+    else:
+        out += D[:, None, None] * g[:, :, None] * g[:, None, :]
+    return dict(x=x_s, blocks=out, var=var + D[:, None] * g * g, cx=x_s[:, j].copy(), cv=pjj + D * g[:, j] ** 2)
+
+
 # ------------------------------------------------------- Hessian correction
 def hessian_correction_pixel(gp, x0, C_obs_inv, innovation, band, nparams):
     selecta = band_selecta(band)

@@ -485,8 +485,8 @@ class KafkaOutput:
         self._dev.mark_written(timestep, state, engine)
         self._ship(timestep, engine)
 
-    def dump_state(self, timestep, state, engine, qa_inputs=None):
-        self._device_output().dump_state(timestep, state, engine, qa_inputs=qa_inputs)
+    def dump_state(self, timestep, state, engine, qa_inputs=None, marginal_var=None):
+        self._device_output().dump_state(timestep, state, engine, qa_inputs=qa_inputs, marginal_var=marginal_var)
         self._ship(timestep, engine)
 
     def _device_encode(self, cuda: bool) -> bool:
@@ -960,9 +960,12 @@ class DeviceOutput:
         if self.keep_history:
             self.history[timestep] = (self.mean.clone(), self.unc.clone())
 
-    def dump_state(self, timestep, state, engine, qa_inputs=None):
+    def dump_state(self, timestep, state, engine, qa_inputs=None, marginal_var=None):
         """``qa_inputs``: the timestep's (status, nobs, nrej), each uint8 [>= N] on
-        the state's device or None -- the inputs of the QA bits 0-3."""
+        the state's device or None -- the inputs of the QA bits 0-3.
+        ``marginal_var``: diag(P) of the state as [n_p, ld] rows where the caller
+        has it already (the rank-one smoother); ``uncertainty="marginal"`` then
+        takes its square root and factorises nothing."""
         n = engine.n_params
         self._ensure(engine, state.x.device)
         marginal = self.uncertainty == "marginal"
@@ -971,7 +974,9 @@ class DeviceOutput:
         unc = self._next_unc(state.x.device)
         mean = self._own_mean()
         idx = None if self._identity else self._idx
-        if state.N and marginal:
+        if state.N and marginal and marginal_var is not None:
+            K.marginal(n, st.x, marginal_var, mean, unc, idx=idx, N=state.N, kind="diagonal")
+        elif state.N and marginal:
             K.marginal(n, st.x, st.P, mean, unc, idx=idx, N=state.N, kind=st.kind)
         elif state.N:
             K.unpack(n, st.x, st.P, mean, unc, idx=idx, N=state.N)

@@ -1625,15 +1625,15 @@ class TileDecoder:
         return out, status[:n]
 
 
-def _check_rasters(n_params, x, p, mean, unc, idx, N, pname) -> tuple[int, int]:
+def _check_rasters(n_params, x, p, mean, unc, idx, N, pname, prows=None) -> tuple[int, int]:
     """The raster scatter of unpack() and marginal(): x [n_p, ld], the packed
-    rows ``p`` [ntri, ld] (read only for ``unc``), planes mean / unc [n_p, plane]
+    rows ``p`` [ntri, ld] (``prows`` rows where given; read only for ``unc``), planes mean / unc [n_p, plane]
     and the optional index map -> (N, plane)."""
     check_np(n_params)
     N = int(x.shape[1] if N is None else N)
     _check_soa(x, n_params, N, "x")
     if unc is not None:
-        _check_soa(p, ntri(n_params), N, pname, device=x.device)
+        _check_soa(p, ntri(n_params) if prows is None else prows, N, pname, device=x.device)
         if p.shape[1] != x.shape[1]:
             raise ValueError(f"x and {pname} must share their row stride")
     plane = (mean if mean is not None else unc).shape[1]
@@ -1663,13 +1663,16 @@ def marginal(n_params, x, p, mean=None, unc=None, idx=None, N=None, kind="precis
     """Scatter mean and the marginal std sqrt(diag(P)) onto raster planes
     [n_p, H*W].  ``p`` holds the packed rows of P^-1 (``kind="precision"``:
     factorised per pixel; a block that is not SPD gives NaN in all its planes)
-    or of P itself (``kind="covariance"``: the diagonal rows are read)."""
-    if kind not in MARGINAL_KINDS:
-        raise ValueError("kind must be 'precision' or 'covariance'")
-    N, plane = _check_rasters(n_params, x, p, mean, unc, idx, N, "p")
+    or of P itself (``kind="covariance"``: the diagonal rows are read), or
+    (``kind="diagonal"``) the [n_p, ld] rows of diag(P) that ``smooth_r1``
+    writes as ``var_out``."""
+    if kind not in MARGINAL_KINDS + ("diagonal",):
+        raise ValueError("kind must be 'precision', 'covariance' or 'diagonal'")
+    N, plane = _check_rasters(n_params, x, p, mean, unc, idx, N, "p", prows=n_params if kind == "diagonal" else None)
     e = ext()
-    e.marginal(n_params, _ptr(x), _ptr(p), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION, N,
-               x.shape[1], _ptr(idx), _ptr(mean), _ptr(unc), plane, _dev(x), _stream(x))
+    code = {"precision": e.MARG_PRECISION, "covariance": e.MARG_COVARIANCE, "diagonal": e.MARG_VARIANCE}[kind]
+    e.marginal(n_params, _ptr(x), _ptr(p), code, N, x.shape[1], _ptr(idx), _ptr(mean), _ptr(unc), plane, _dev(x),
+               _stream(x))
 
 
 def product(n_params, x, p, transforms, z, phys=None, qa=None, idx=None, N=None, kind="precision", status=None,
@@ -1769,6 +1772,51 @@ def smooth(n_params, x_a, p_a, x_next, p_next, x_out, p_out, status, *, kind, pr
     e.smooth(n_params, _ptr(x_a), _ptr(p_a), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION,
              _ptr(x_next), _ptr(p_next), _ptr(x_out), _ptr(p_out), _ptr(status), N, x_a.shape[1], prop_mask, mv, qv,
              _ptr(q_pix), _dev(x_a), _stream(x_a))
+
+
+def smooth_r1(n_params, x_a, p_a, x_out, cx_out, cv_out, status, *, kind, j, m, q, q_pix=None, cx_in=None, cv_in=None,
+              p_out=None, var_out=None, N=None):
+    """One backward step of the RTS smoother where the propagator carries the
+    single parameter ``j`` (csrc/kf_core.h ``pixel_smooth_r1``): a rank-one
+    update of the filtered state.  ``x_a`` / ``p_a`` as ``smooth``; ``m`` / ``q``:
+    the scalars m_j and q_j, ``q_pix`` [n_p, ld] a per-pixel model error (row
+    ``j`` is read).  ``cx_in`` / ``cv_in`` [>= N]: the smoothed x[j] and P[j, j]
+    of step t + 1, all the step needs of it; both None: the last step of the run
+    (x_s = x_a, rows unchanged).  Writes ``x_out``, the carried planes
+    ``cx_out`` / ``cv_out`` [>= N] for step t - 1, ``status`` (1 where the pixel
+    kept its filtered state) and, where given, ``p_out`` -- packed rows of the
+    same ``kind`` as ``p_a``: the covariance with its rank-one update, or the
+    precision with entry (j, j) changed -- and ``var_out`` [n_p, ld], the
+    marginal variances diag(P_s).  ``p_out`` must not be ``p_a``."""
+    check_np(n_params)
+    if kind not in MARGINAL_KINDS:
+        raise ValueError("kind must be 'precision' or 'covariance'")
+    j = int(j)
+    if not 0 <= j < n_params:
+        raise ValueError(f"j={j} outside the state of {n_params} parameters")
+    if (cx_in is None) != (cv_in is None):
+        raise ValueError("cx_in and cv_in go together (both None: the last step)")
+    N = int(x_a.shape[1] if N is None else N)
+    dev = x_a.device
+    _check_soa(x_a, n_params, N, "x_a")
+    for t, rows, name in ((p_a, ntri(n_params), "p_a"), (x_out, n_params, "x_out"), (q_pix, n_params, "q_pix"),
+                          (p_out, ntri(n_params), "p_out"), (var_out, n_params, "var_out")):
+        if t is None and name in ("p_a", "x_out"):
+            raise ValueError(f"{name} is required")
+        _check_soa(t, rows, N, name, device=dev)
+        if t is not None and t.shape[1] != x_a.shape[1]:
+            raise ValueError(f"x_a and {name} must share their row stride")
+    if p_out is not None and p_out.data_ptr() == p_a.data_ptr():
+        raise ValueError("p_out must not be p_a")
+    for t, name, dt in ((cx_in, "cx_in", torch.float32), (cv_in, "cv_in", torch.float32),
+                        (cx_out, "cx_out", torch.float32), (cv_out, "cv_out", torch.float32), (status, "status", torch.uint8)):
+        if t is None and name not in ("cx_in", "cv_in"):
+            raise ValueError(f"{name} is required")
+        _check_vec(t, N, name, dt, dev)
+    e = ext()
+    e.smooth_r1(n_params, _ptr(x_a), _ptr(p_a), e.MARG_COVARIANCE if kind == "covariance" else e.MARG_PRECISION, j,
+                float(m), float(q), _ptr(q_pix), _ptr(cx_in), _ptr(cv_in), _ptr(x_out), _ptr(cx_out), _ptr(cv_out),
+                _ptr(status), _ptr(p_out), _ptr(var_out), N, x_a.shape[1], _dev(x_a), _stream(x_a))
 
 
 INNOVATION_SCOPES = ("band", "group")

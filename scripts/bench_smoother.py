@@ -9,7 +9,11 @@ started on the device).  One JSON line per record, also appended to ``--record``
 ``smooth_kernel`` for n = 7 with mask {6} (the LAI propagator) and n = 10 with
 the full mask, both kinds of the filtered rows, with the bytes per pixel it
 moves (reads 2 (n + ntri) floats, writes n + ntri floats and the status byte)
-and the effective bandwidth.  As the yardsticks on the same box: a plain device
+and the effective bandwidth; ``smooth_r1_kernel`` (mask {6} at both sizes, both
+kinds, every output written: reads n + ntri + 2 floats, writes 2 n + ntri + 2
+floats and the status byte) and, for n = 10, the dense kernel on mask {6} too.
+The dense and rank-one launches are timed interleaved, one call of each per
+round.  As the yardsticks on the same box: a plain device
 copy of the same byte volume (half of it read, half written), and
 ``marginal_kernel`` (precision kind, with the mean) on the same N.
 
@@ -36,7 +40,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CASES = {7: 1 << 6, 10: (1 << 10) - 1}     # n -> prop_mask
+CASES = {7: 1 << 6, 10: (1 << 10) - 1}     # n -> prop_mask of the dense kernel's lines
+R1_J = 6                                   # the rank-one kernel's propagated parameter (mask {6}), n = 7 and 10
 
 
 def emit(rec, record):
@@ -111,14 +116,46 @@ def one_kernel_config(size, n, reps):
                     "ms_min": round(lo, 4), "ms_max": round(hi, 4), "reps": reps, "read_B_per_px": rd,
                     "write_B_per_px": wr, "GB_per_s": round((rd + wr) * N / (med * 1e-3) / 1e9, 1), **kw})
 
+    def interleaved(fns):
+        """One call of each per round, the rounds repeated: [(median, min, max)] per function."""
+        for _ in range(2):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        ms = [[] for _ in fns]
+        for _ in range(reps):
+            for i, fn in enumerate(fns):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                ms[i].append(e0.elapsed_time(e1))
+        return [(statistics.median(v), min(v), max(v)) for v in ms]
+
+    cx, cv = x_next[R1_J].contiguous(), p_next[sorted(diag)[R1_J]].contiguous()
+    cxo, cvo, var = torch.empty_like(cx), torch.empty_like(cv), torch.empty_like(x_a)
     for kind in ("precision", "covariance"):
-        med, lo, hi = timed(lambda: K.smooth(n, x_a, p_a, x_next, p_next, x_out, p_out, status, kind=kind,
-                                             prop_mask=CASES[n], m=m, q=q))
+        masks = sorted({CASES[n], 1 << R1_J})
+        fns = [lambda mk=mk: K.smooth(n, x_a, p_a, x_next, p_next, x_out, p_out, status, kind=kind, prop_mask=mk,
+                                      m=m, q=q) for mk in masks]
+        fns.append(lambda: K.smooth_r1(n, x_a, p_a, x_out, cxo, cvo, status, kind=kind, j=R1_J, m=1.0, q=0.04,
+                                       cx_in=cx, cv_in=cv, p_out=p_out, var_out=var))
+        fns.append(lambda: K.smooth_r1(n, x_a, p_a, x_out, cxo, cvo, status, kind=kind, j=R1_J, m=1.0, q=0.04,
+                                       cx_in=cx, cv_in=cv))
+        times = interleaved(fns)
         fb = int(status.count_nonzero().item())
         assert fb == 0 and bool(torch.isfinite(p_out[:, ::4097]).all())
-        rec(f"smooth_kernel/{kind}", med, lo, hi, rd, wr, prop_mask=CASES[n], fallback_pixels=fb)
+        for mk, (med, lo, hi) in zip(masks, times):
+            rec(f"smooth_kernel/{kind}", med, lo, hi, rd, wr, prop_mask=mk, fallback_pixels=fb)
+        med, lo, hi = times[-2]
+        rec(f"smooth_r1_kernel/{kind}", med, lo, hi, 4 * (n + nt + 2), 4 * (2 * n + nt + 2) + 1, prop_mask=1 << R1_J,
+            outputs="rows+var", fallback_pixels=fb)
+        med, lo, hi = times[-1]
+        rec(f"smooth_r1_kernel/{kind}", med, lo, hi, 4 * (n + nt + 2), 4 * (n + 2) + 1, prop_mask=1 << R1_J,
+            outputs="none", fallback_pixels=fb)
     # a plain device copy of the same byte volume: 1.5 (n + nt) floats per pixel read and as many written
-    del x_next, p_next, x_out, p_out
+    del x_next, p_next, x_out, p_out, var
     half = (3 * (n + nt) * N) // 2
     src = torch.rand(half, device=dev, generator=g)
     dst = torch.empty_like(src)
