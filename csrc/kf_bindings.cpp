@@ -480,6 +480,42 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     for (const KernelPlan& p : plans) names.push_back(plan_name(p));
     return names;
   });
+  // GP predictive variance of one emulator at the states x (kf_launch.h GpVarArgs).  device: etab / wtab the
+  // fragment tables of models/gp.py mfma_variance_tables (nchunk chunks), grid <= 0 for one workgroup per
+  // compute unit; host: etab the centred float32 training inputs [T][d], wtab the float32 W^ [T][T].
+  m.def("gp_variance", [](int np, const std::vector<int>& map, const std::vector<float>& center,
+                          const std::vector<float>& lam, float signal, float inv_scale2, uintptr_t etab,
+                          uintptr_t wtab, int nchunk, int T, uintptr_t x, uintptr_t out, int64_t N, int64_t ld,
+                          int grid, bool device, uintptr_t stream) {
+    GpVarArgs a{};
+    const size_t d = map.size();
+    if (d < 1 || d > (size_t)GPM_MAX_D || center.size() != d || lam.size() != d)
+      throw std::invalid_argument("gp_variance: map, center and lam need one entry per GP input (at most 10)");
+    for (size_t i = 0; i < d; ++i) {
+      if (map[i] < 0 || map[i] >= np) throw std::invalid_argument("gp_variance: state map outside the state");
+      a.map[i] = map[i];
+      a.center[i] = center[i];
+      a.lam[i] = lam[i];
+    }
+    a.d = (int)d;
+    a.x = P<const float>(x);
+    a.out = P<float>(out);
+    a.N = N;
+    a.ld = ld;
+    a.etab = P<const void>(etab);
+    a.wtab = P<const void>(wtab);
+    a.nchunk = nchunk;
+    a.signal = signal;
+    a.inv_scale2 = inv_scale2;
+    if (device) check_hip(dev_gp_variance(a, grid, (hipStream_t)stream), "gp_variance");
+    else check_host(host_gp_variance(a, P<const float>(etab), P<const float>(wtab), T), "gp_variance");
+  });
+  m.attr("GPV_MAX_CHUNKS") = GPV_MAX_CHUNKS;
+  m.def("gp_variance_table", []() {
+    std::vector<std::string> names;
+    for (const char* n : gp_variance_table()) names.push_back(n);
+    return names;
+  });
   // unpack: mean and 1/sqrt(diag(P^-1)) onto the raster from the precision rows p
   m.def("unpack", [](int np, uintptr_t x, uintptr_t p, int64_t N, int64_t ld, uintptr_t idx, uintptr_t mean,
                      uintptr_t unc, int64_t plane, bool device, uintptr_t stream) {

@@ -384,6 +384,46 @@ int host_innovation(int np, const InnovationArgs& a) {
   if (!innovation_args_ok(np, a) || a.prop) return -1;   // the fused-forecast check is a device kernel only
   return innovation_joint(a) ? host_pixels<OpInnovation<true>>(np, a) : host_pixels<OpInnovation<false>>(np, a);
 }
+// The predictive variance of kf_gp_variance.hip as a plain float32 loop: k^ from the squared
+// distances, u = W^ k^ over the lower triangle, var = s max(0, 1 - sum u^2).
+int host_gp_variance(const GpVarArgs& a, const float* t, const float* w, int T) {
+  const int D = a.d;
+  if (D < 1 || D > GPM_MAX_D || T < 1 || a.N > a.ld || !a.x || !a.out || !t || !w) return -1;
+#pragma omp parallel
+  {
+    std::vector<float> kh((size_t)T);
+#pragma omp for schedule(static)
+    for (int64_t p = 0; p < a.N; ++p) {
+      float xi[GPM_MAX_D];
+      bool fin = true;
+      for (int d = 0; d < D; ++d) {
+        xi[d] = a.x[(int64_t)a.map[d] * a.ld + p] - a.center[d];
+        fin = fin && finitef(xi[d]);
+      }
+      if (!fin) {
+        a.out[p] = nanf("");
+        continue;
+      }
+      for (int i = 0; i < T; ++i) {
+        float q = 0.f;
+        for (int d = 0; d < D; ++d) {
+          const float dx = xi[d] - t[(size_t)i * D + d];
+          q += a.lam[d] * dx * dx;
+        }
+        kh[i] = expf(-0.5f * q);
+      }
+      float su = 0.f;
+      for (int r = 0; r < T; ++r) {
+        const float* wr = w + (size_t)r * T;
+        float u = 0.f;
+        for (int i = 0; i <= r; ++i) u += wr[i] * kh[i];
+        su += u * u;
+      }
+      a.out[p] = a.signal * fmaxf(1.f - su, 0.f);
+    }
+  }
+  return 0;
+}
 int host_obs_order(const BandDesc* bands, const int32_t* grp, int nb, int G, int64_t N, int32_t* order, bool local) {
   if (G < 1 || G > 3) return -1;
   std::vector<uint8_t> cls((size_t)N);

@@ -50,6 +50,28 @@ hipError_t dev_hessian(int np, const HessianArgs& a, hipStream_t s);
 // K6 on the matrix cores (kf_hessian_mfma.hip): hessian_plan's PLAN_HESSIAN_MFMA kernel for a
 hipError_t dev_hessian_mfma(const KernelPlan& plan, const HessianMfmaArgs& a, hipStream_t s);
 void launch_table_hessian(std::vector<KernelPlan>& out);
+// GP predictive variance on the matrix cores (kf_gp_variance.hip): out[p] = s (1 - |W^ k^(x_p)|^2) for one
+// emulator, with K + nugget = L L^T, k^ = k / s and W^ = sqrt(s) L^-1 (tables: models/gp.py
+// mfma_variance_tables).  The GP input d of pixel p is x[map[d] * ld + p] - center[d].
+constexpr int GPV_MAX_CHUNKS = 16;   // 32-point chunks: k^ of a 64-pixel tile in LDS, 8 KiB per chunk
+struct GpVarArgs {
+  const float* x;     // SoA state rows [n_params][ld] (read only)
+  float* out;         // [N]
+  int64_t N, ld;
+  const void* etab;   // exponent A fragments, nchunk x gpm_k_steps(d) x 64 x 16 B
+  const void* wtab;   // W^ hi / lo A fragments, nchunk (nchunk + 1) / 2 blocks x 4 KiB
+  int32_t nchunk, d;
+  float signal;       // s
+  float inv_scale2;   // 1 / w_scale^2: undoes the power-of-two scale of W^ on sum u^2
+  int32_t map[GPM_MAX_D];
+  float center[GPM_MAX_D];
+  float lam[GPM_MAX_D];
+};
+// grid <= 0: one workgroup per compute unit (the kernel keeps a CU's LDS to itself)
+hipError_t dev_gp_variance(const GpVarArgs& a, int grid, hipStream_t s);
+std::vector<const char*> gp_variance_table();
+// the same whitened form as a float32 loop: t [T][d] centred training inputs, w [T][T] the unsplit W^
+int host_gp_variance(const GpVarArgs& a, const float* t, const float* w, int T);
 hipError_t dev_gp_operator(int np, int d, const GpOperatorArgs& a, hipStream_t s);
 bool gp_operator_supported(int np, int d);
 hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s);

@@ -157,6 +157,11 @@ class EngineConfig:
     # state's own kind) where the propagator carries exactly one parameter (the LAI propagator, a
     # prior reset with one carried parameter) and the dense kernel for every other link
     smoother_form: str = "dense"              # 'dense' | 'rank_one'
+    # emulator_uncertainty: 'report' evaluates the predictive std of every GP band's emulator at
+    # each date's analysis (ops.kernels.gp_variance; LinearKalman.last_emulator_std) and adds its
+    # max and mean over the finite pixels to the date's metrics record ("emulator").  The analysis
+    # itself does not read it.  'off': nothing launches (--emulator-uncertainty)
+    emulator_uncertainty: str = "off"         # 'off' | 'report'
     metrics_path: str | None = None           # JSONL metrics (per date / timestep)
     checkpoint_dir: str | None = None
     checkpoint_every: int = 0                 # timesteps between checkpoints (0: off)
@@ -197,6 +202,8 @@ class EngineConfig:
             raise ValueError("innovation_forecast must be 'materialised' or 'fused'")
         if self.smoother_form not in ("dense", "rank_one"):
             raise ValueError("smoother_form must be 'dense' or 'rank_one'")
+        if self.emulator_uncertainty not in ("off", "report"):
+            raise ValueError("emulator_uncertainty must be 'off' or 'report'")
         if self.store_precision not in ("auto", "always"):
             raise ValueError("store_precision must be 'auto' or 'always'")
         if isinstance(self.convergence_chunk, str) and self.convergence_chunk.strip().lower() in ("", "0", "tile",

@@ -165,6 +165,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         self._qa_acc = None               # a QA output: the timestep's status / nobs / nrej folded over its dates
         self.last_innovation = None       # config.innovation_*: the last date's {"chi2", "nobs", "nrej"}
         self._innov_forecast = None       # the last screened date's check: "fused" | "materialised"
+        self.last_emulator_std = None     # config.emulator_uncertainty: the last date's [n_gp_bands, N] std
+        self._last_date = None            # (date, band specs, analysis state) of the last date assimilated
         self.gate_history = None          # config.innovation_gate: dates with a rejection, per pixel (int32)
         self.evidence = None              # config.innovation_evidence: the run's per-pixel accumulators
         self._innov = None                # its buffers: statistics and the screened observation planes
@@ -592,6 +594,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                 if self._qa_output():
                     self._qa_accumulate()
             forecast = res.state
+            if not self.config.band_sequential:
+                self._last_date = (step, [sp for sp, _ in bands], res.state)
             if self.config.domain_history and getattr(self, "last_status", None) is not None and self.N:
                 # pixels whose GP inputs left an emulator's domain on any date of the run
                 ood = self.last_status[:self.N] & K.ST_OUT_OF_DOMAIN
@@ -607,6 +611,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                 info.setdefault("chunk_iters", []).append(self.last_chunk_iters)
             if self._reg_log:
                 rec["spatial"] = self._spatial_record()
+            if self.config.emulator_uncertainty == "report":
+                rec["emulator"] = self._emulator_report()
             if self.metrics.enabled:
                 rec.update(self._health_metrics(rec["wall_s"]))
                 if self._screening() and not self.config.band_sequential and self.last_innovation is not None:
@@ -696,6 +702,45 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         if self.config.innovation_gp == "mfma" and K.innovation_mfma_supported(self.n_params, table, self.device):
             return "mfma"
         return "valu"
+
+    # ------------------------------------------- emulator predictive uncertainty
+    def emulator_variance(self, state=None, timestep=None):
+        """Predictive std of the emulator of every GP band of ``timestep`` (default: the last
+        date assimilated) at ``state`` (a KFState or an ``[n_params, ld]`` float32 tensor;
+        default: that date's analysis): ``[n_gp_bands, N]`` float32 on the engine's device,
+        sqrt(s - k^T (K + nugget)^-1 k) by ops.kernels.gp_variance.  Bands that are no GP are
+        skipped; a GP band the kernel cannot serve (no nugget on its emulator, no table)
+        raises with the reason."""
+        last = self._last_date
+        if last is None and (state is None or timestep is None):
+            raise ValueError("emulator_variance: no date assimilated yet (pass state and timestep)")
+        if timestep is None or (last is not None and last[0] == timestep):
+            specs = last[1]
+        else:
+            specs = [sp for sp, _ in self._device_bands(timestep)]
+        x = last[2].x if state is None else getattr(state, "x", state)
+        gp = [(b, sp) for b, sp in enumerate(specs) if sp.kind == OP_GP]
+        out = torch.empty((len(gp), self.N), dtype=torch.float32, device=self.device)
+        for i, (b, sp) in enumerate(gp):
+            ok, why = K.gp_variance_supported(sp, self.device)
+            if not ok:
+                raise ValueError(f"emulator_variance: band {b}: {why}")
+            K.gp_variance(self.n_params, sp, x, out[i], N=self.N)
+        return out.sqrt_()
+
+    def _emulator_report(self):
+        """config.emulator_uncertainty = 'report': the date's std planes (``last_emulator_std``)
+        and, per GP band, their max and mean over the finite pixels (one read-back)."""
+        if self.config.band_sequential:
+            raise ValueError("emulator_uncertainty='report' does not run with band_sequential")
+        std = self.last_emulator_std = self.emulator_variance()
+        names = [getattr(sp.emulator, "name", "gp") for sp in self._last_date[1] if sp.kind == OP_GP]
+        if not std.numel():
+            return [{"band": n, "max": None, "mean": None} for n in names]
+        fin = torch.isfinite(std)
+        s0 = torch.where(fin, std, torch.zeros_like(std))
+        stats = torch.stack([s0.max(1).values, s0.sum(1) / fin.sum(1).clamp(min=1)]).cpu().numpy()
+        return [{"band": n, "max": float(stats[0, i]), "mean": float(stats[1, i])} for i, n in enumerate(names)]
 
     def _hessian_gp(self, table) -> str:
         """config.hessian_gp where the date's table and the device allow it, else the VALU kernel."""

@@ -42,6 +42,8 @@ WRONG_VALUE = -999.0
 # ------------------------------------------------------------- emulators
 def save_emulator(path, em: GaussianProcessEmulator, **extra):
     """Emulator -> .npz (plain arrays only; loadable without pickle)."""
+    if em.noise is not None:      # the nugget, for the predictive variance (models/gp.py variance)
+        extra = dict(extra, noise=np.array(em.noise))
     np.savez(path, inputs=em.inputs, alpha=em.alpha, lam=em.lam, signal=np.array(em.signal),
              mean=np.array(em.mean), name=np.array(em.name), **extra)
 
@@ -49,7 +51,7 @@ def save_emulator(path, em: GaussianProcessEmulator, **extra):
 def load_emulator(path) -> GaussianProcessEmulator:
     with np.load(path, allow_pickle=False) as z:
         return GaussianProcessEmulator(z["inputs"], z["alpha"], z["lam"], float(z["signal"]), float(z["mean"]),
-                                       name=str(z["name"]))
+                                       name=str(z["name"]), noise=float(z["noise"]) if "noise" in z.files else None)
 
 
 def load_emulator_set(path) -> dict:
@@ -59,7 +61,8 @@ def load_emulator_set(path) -> dict:
         bands = sorted({k.split("__")[0] for k in z.files if "__" in k})
         for b in bands:
             out[b] = GaussianProcessEmulator(z[f"{b}__inputs"], z[f"{b}__alpha"], z[f"{b}__lam"],
-                                             float(z[f"{b}__signal"]), float(z[f"{b}__mean"]), name=b)
+                                             float(z[f"{b}__signal"]), float(z[f"{b}__mean"]), name=b,
+                                             noise=float(z[f"{b}__noise"]) if f"{b}__noise" in z.files else None)
     return out
 
 
@@ -68,6 +71,8 @@ def save_emulator_set(path, ems: dict):
     for b, em in ems.items():
         arrs.update({f"{b}__inputs": em.inputs, f"{b}__alpha": em.alpha, f"{b}__lam": em.lam,
                      f"{b}__signal": np.array(em.signal), f"{b}__mean": np.array(em.mean)})
+        if em.noise is not None:
+            arrs[f"{b}__noise"] = np.array(em.noise)
     np.savez(path, **arrs)
 
 

@@ -22,13 +22,17 @@ LOG2E = 1.4426950408889634
 class GaussianProcessEmulator:
     """RBF (ARD) GP emulator with analytic gradient and Hessian."""
 
-    def __init__(self, inputs, alpha, lam, signal: float = 1.0, mean: float = 0.0, name: str = "gp"):
+    def __init__(self, inputs, alpha, lam, signal: float = 1.0, mean: float = 0.0, name: str = "gp", noise=None):
         self.inputs = np.asarray(inputs, dtype=np.float64)      # [T, D]
         self.alpha = np.asarray(alpha, dtype=np.float64)        # [T]
         self.lam = np.asarray(lam, dtype=np.float64)            # [D]  (1/lengthscale^2)
         self.signal = float(signal)
         self.mean = float(mean)
         self.name = name
+        # the nugget as a fraction of ``signal`` (``fit`` adds noise * s + 1e-10 to the
+        # diagonal); None: fitted elsewhere, no predictive variance
+        self.noise = None if noise is None else float(noise)
+        self._chol = None
         if self.inputs.ndim != 2 or self.inputs.shape[0] != self.alpha.shape[0]:
             raise ValueError("inputs must be [T, D] and alpha [T]")
         if self.lam.shape != (self.inputs.shape[1],):
@@ -63,8 +67,34 @@ class GaussianProcessEmulator:
             H[s:s + chunk] = self.mean + ak.sum(1)
             dH[s:s + chunk] = -self.lam[None, :] * np.einsum("nt,ntd->nd", ak, diff)
         if do_unc:
-            return H, np.zeros_like(H), dH
+            return H, (np.zeros_like(H) if self.noise is None else self.variance(X, chunk)), dH
         return H, dH
+
+    def cholesky(self) -> np.ndarray:
+        """Lower Cholesky factor of ``K + nugget`` over the training points (float64, kept)."""
+        if self.noise is None:
+            raise ValueError(f"emulator {self.name!r} has no noise (nugget): it was built from alpha alone, and the "
+                             "predictive variance needs K + nugget")
+        if self._chol is None:
+            diff = self.inputs[:, None, :] - self.inputs[None, :, :]
+            Kt = self.signal * np.exp(-0.5 * np.einsum("ijd,d->ij", diff * diff, self.lam))
+            Kt[np.diag_indices_from(Kt)] += self.noise * self.signal + 1e-10
+            self._chol = np.linalg.cholesky(Kt)
+        return self._chol
+
+    def variance(self, X, chunk: int = 65536):
+        """Predictive variance ``s - k(x)^T (K + nugget)^-1 k(x)`` as float64
+        ``s - |L^-1 k|^2``, clamped at 0 (what gp_emulator's ``do_unc`` returns)."""
+        from scipy.linalg import solve_triangular
+
+        L = self.cholesky()
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        var = np.empty(X.shape[0])
+        for s in range(0, X.shape[0], chunk):
+            _, _, k = self._kernel(X[s:s + chunk])
+            v = solve_triangular(L, k.T, lower=True)
+            var[s:s + chunk] = np.maximum(self.signal - (v * v).sum(0), 0.0)
+        return var
 
     def hessian(self, X):
         """d2f/dx2, [n, D, D]."""
@@ -146,7 +176,7 @@ class GaussianProcessEmulator:
         K = s * np.exp(-0.5 * np.einsum("ijd,d->ij", diff * diff, lam))
         K[np.diag_indices_from(K)] += noise * s + 1e-10
         alpha = np.linalg.solve(K, y - mu)
-        return cls(X, alpha, lam, s, mu, name=name)
+        return cls(X, alpha, lam, s, mu, name=name, noise=noise)
 
     @classmethod
     def synthetic(cls, target, lo, hi, n_train: int = 500, seed: int = 0, length_frac: float = 0.35,
@@ -170,13 +200,14 @@ class GaussianProcessEmulator:
 
 def pack_emulator_set(ems: dict):
     """{key: emulator} -> (header, float64 buffer): header = [(key, T, D, name)],
-    buffer = per emulator [signal, mean, inputs (T x D), alpha (T), lam (D), center (D)]."""
+    buffer = per emulator [signal, mean, inputs (T x D), alpha (T), lam (D), center (D), noise (NaN: none)]."""
     header, parts = [], []
     for key, em in ems.items():
         T, D = em.inputs.shape
         header.append((str(key), int(T), int(D), str(em.name)))
         parts += [np.array([em.signal, em.mean]), em.inputs.ravel(), em.alpha.ravel(), em.lam.ravel(),
-                  np.asarray(em.center(), dtype=np.float64).ravel()]
+                  np.asarray(em.center(), dtype=np.float64).ravel(),
+                  np.array([np.nan if em.noise is None else em.noise])]
     return header, (np.concatenate(parts) if parts else np.zeros(0))
 
 
@@ -193,7 +224,10 @@ def unpack_emulator_set(header, buf) -> dict:
         o += D
         center = buf[o:o + D]
         o += D
-        em = GaussianProcessEmulator(inputs.copy(), alpha.copy(), lam.copy(), float(sig), float(mu), name=name)
+        noise = None if np.isnan(buf[o]) else float(buf[o])
+        o += 1
+        em = GaussianProcessEmulator(inputs.copy(), alpha.copy(), lam.copy(), float(sig), float(mu), name=name,
+                                     noise=noise)
         out[key] = em.set_center(center) if not np.array_equal(center, em.center()) else em
     return out
 
@@ -501,6 +535,143 @@ def hessian_from_sums(S, lam, xi):
         H[:, u, v] = H[:, v, u] = a[:, u] * a[:, v] * S0 - a[:, u] * G[:, v] - a[:, v] * G[:, u] + \
             ln2 * ln2 * S[:, 1 + D + t] - (lam[u] * S0 if u == v else 0.0)
     return S0, H
+
+
+# --------------------------------------------------------------------------
+# predictive-variance tables (csrc/kf_gp_variance.hip)
+#
+# With K + nugget = L L^T, k^ = k / s in (0, 1] and W^ = sqrt(s) L^-1 (lower
+# triangular) the variance is s (1 - |W^ k^|^2).  k^ comes from the exponent
+# GEMM of the matrix-core GP (no weights: L = -1/2 log2e sum lambda t^2) and is
+# kept as k^ 2^GPV_K_LOG2 (multiplied after the exponential: inside the exponent
+# it costs the near points their last bits) so its f16 halves stay normal; W^ k^ is a triangular GEMM of 32 x 32 blocks with split-f16
+# operands.  The low part of L is folded into W^'s columns (exact in float64
+# before the split), as mfma_tables folds it into its sums operand.
+
+GPV_MAX_T = 512          # 16 chunks: k^ of a 64-pixel tile fills 128 KiB of LDS
+GPV_K_LOG2 = 14          # k^ 2^14 <= 2^14 (f16 max 65504)
+GPV_W_LOG2 = 13          # W^'s largest |entry| is scaled into [2^13, 2^14)
+GPV_PAD_L = -65504.0     # exponent constant of a padding point (-1e30 within f16): k^ = 0
+
+
+def mfma_variance_tables(em):
+    """Operand fragments of the predictive-variance kernel (``csrc/kf_gp_variance.hip``)
+    for emulator ``em`` (with ``noise``), all T points in their natural order.
+
+    Returns ``(etab, wtab, n_chunks, w_scale)``.  ``etab`` float16 ``[n_chunks,
+    64 NK, 8]``: the exponent A fragments in :func:`mfma_tables`' layout (rows
+    ``[Bh | Bl | Bh | Lh | 1]``).  ``wtab`` float16 ``[n_blocks, 2, 2, 64, 8]``:
+    the 32 x 32 blocks (R, C <= R) of ``W^ diag(2^Ll) 2^-GPV_K_LOG2 w_scale`` at
+    R (R + 1) / 2 + C, per K half q the hi then the lo A fragments of all 64
+    lanes (row 32 R + (lane & 31), K slot 8 h + j = point 32 C + _sum_points()[q,
+    h, j]: the order in which the exponent MFMA leaves k^).  T is padded to 32
+    n_chunks with k^ = 0 points and zero rows and columns.  None when D > 10 or
+    a value leaves the f16 range."""
+    from scipy.linalg import solve_triangular
+
+    D, T = em.n_inputs, em.n_train
+    if not 1 <= D <= GPM_MAX_D or T < 1:
+        return None
+    chol = em.cholesky()
+    t = em.inputs - em.center()[None, :]
+    L = -0.5 * LOG2E * (t * t * em.lam[None, :]).sum(1)
+    B = LOG2E * em.lam[None, :] * t
+    if np.abs(B).max() > _F16_SAFE or np.abs(L).max() > _F16_SAFE:
+        return None
+    nch = -(-T // 32)
+    Tpad, NK = 32 * nch, gpm_k_steps(D)
+    Bh, Bl = _split16(B)
+    Lh = L.astype(np.float16)
+    Ll = L - Lh.astype(np.float64)
+    kexp = np.zeros((Tpad, 16 * NK), dtype=np.float16)
+    kexp[:T, 0:D], kexp[:T, D:2 * D], kexp[:T, 2 * D:3 * D] = Bh, Bl, Bh
+    kexp[:T, 3 * D] = Lh
+    kexp[T:, 3 * D] = GPV_PAD_L
+    kexp[:, 3 * D + 1] = 1.0
+    W = np.zeros((Tpad, Tpad))
+    W[:T, :T] = np.sqrt(em.signal) * solve_triangular(chol, np.eye(T), lower=True)
+    W[:, :T] *= np.exp2(Ll - GPV_K_LOG2)[None, :]
+    amax = np.abs(W).max()
+    if not np.isfinite(amax) or amax <= 0:
+        return None
+    sh = GPV_W_LOG2 - np.floor(np.log2(amax))
+    if abs(sh) > 60:          # the kernel undoes 2^(2 sh) in float32
+        return None
+    Wh, Wl = _split16(np.tril(W) * np.exp2(sh))
+    lane, j, sp = np.arange(64), np.arange(8), _sum_points()
+    etab = np.zeros((nch, 64 * NK, 8), dtype=np.float16)
+    for kk in range(NK):
+        etab[:, 64 * kk:64 * (kk + 1)] = kexp.reshape(nch, 32, 16 * NK)[:, (lane & 31)[:, None],
+                                                                        16 * kk + 8 * (lane >> 5)[:, None] + j]
+    wtab = np.zeros((nch * (nch + 1) // 2, 2, 2, 64, 8), dtype=np.float16)
+    for R in range(nch):
+        rows = (32 * R + (lane & 31))[:, None]
+        for C in range(R + 1):
+            for q in range(2):
+                cols = 32 * C + sp[q][lane >> 5]                # [64, 8]
+                wtab[R * (R + 1) // 2 + C, q, 0] = Wh[rows, cols]
+                wtab[R * (R + 1) // 2 + C, q, 1] = Wl[rows, cols]
+    return etab, wtab, nch, float(2.0 ** sh)
+
+
+def _f16_toward_zero(m):
+    """f16 of float32 ``m`` rounded toward zero (v_cvt_pkrtz_f16_f32)."""
+    h = m.astype(np.float16)
+    over = np.abs(h.astype(np.float32)) > np.abs(m)
+    return np.where(over, np.nextafter(h, np.float16(0)), h)
+
+
+def mfma_variance_emulate(tables, D: int, xi, lam):
+    """NumPy model of ``gp_variance_kernel`` read straight from the fragments:
+    ``var / s [n]`` (float32) for centred float32 inputs ``xi [n, D]``: f16
+    operand splits, exact products, and float32 accumulators rounded after every
+    MFMA in the kernel's order (row group, chunk, K half; hi hi, hi lo, lo hi).
+    The exponent constant c = -1/2 log2e sum lambda x^2 is formed in float64 from
+    the split inputs xh + xl, the values the exponent MFMA multiplies: every k^
+    of a pixel carries 2^c, so a float32 c (or one of the unsplit inputs) would
+    put its rounding, times |c| ~ 10, on the whole of sum u^2."""
+    etab, wtab, nch, w_scale = tables
+    xi = np.asarray(xi, dtype=np.float32).astype(np.float64)
+    NK = gpm_k_steps(D)
+    xh, xl = _split16(np.clip(xi, -6.0e4, 6.0e4))
+    xs_ = xh.astype(np.float64) + xl.astype(np.float64)
+    cd = -0.5 * LOG2E * (xs_ * xs_ * np.asarray(lam, dtype=np.float32).astype(np.float64)[None, :D]).sum(1)
+    c = cd.astype(np.float32)
+    ch_ = np.maximum(c, np.float32(-6.0e4)).astype(np.float16)
+    cl_ = (cd - ch_.astype(np.float64)).astype(np.float32)
+    xs = np.zeros((xi.shape[0], 16 * NK))
+    xs[:, 0:D], xs[:, D:2 * D], xs[:, 2 * D:3 * D] = xh, xh, xl
+    xs[:, 3 * D] = 1.0
+    xs[:, 3 * D + 1] = ch_
+    lane, j, sp = np.arange(64), np.arange(8), _sum_points()
+    et = np.asarray(etab, dtype=np.float64)
+    kh = np.zeros((xi.shape[0], 32 * nch))
+    kl = np.zeros_like(kh)
+    for ch in range(nch):
+        kexp = np.zeros((32, 16 * NK))
+        for kk in range(NK):
+            kexp[(lane & 31)[:, None], 16 * kk + 8 * (lane >> 5)[:, None] + j] = et[ch, 64 * kk:64 * (kk + 1)]
+        with np.errstate(under="ignore"):
+            m = np.exp2((xs @ kexp.T).astype(np.float32)) * np.float32(2.0 ** GPV_K_LOG2)
+        h = _f16_toward_zero(m)
+        kh[:, 32 * ch:32 * ch + 32] = h
+        kl[:, 32 * ch:32 * ch + 32] = (m - h.astype(np.float32)).astype(np.float16)
+    wt = np.asarray(wtab, dtype=np.float64)
+    su = np.zeros(xi.shape[0], dtype=np.float32)
+    for R in range(nch):
+        acc = np.zeros((xi.shape[0], 32), dtype=np.float32)
+        for C in range(R + 1):
+            for q in range(2):
+                A = np.zeros((2, 32, 16))
+                A[:, (lane & 31)[:, None], 8 * (lane >> 5)[:, None] + j] = wt[R * (R + 1) // 2 + C, q]
+                pts = 32 * C + sp[q].reshape(16)                # point of K slot 8 h + j
+                for a_, k_ in ((A[0], kh), (A[0], kl), (A[1], kh)):
+                    acc = (acc + k_[:, pts] @ a_.T).astype(np.float32)
+        su += (acc * acc).sum(1, dtype=np.float32)
+    inv2 = np.float32(1.0 / (w_scale * w_scale))
+    with np.errstate(under="ignore", over="ignore"):
+        su = np.where(c > np.float32(-6.0e4), (su * inv2) * np.exp2(2.0 * cl_, dtype=np.float32), np.float32(0))
+    return np.maximum(np.float32(1) - su, np.float32(0)).astype(np.float32)
 
 
 # --------------------------------------------------------------------------

@@ -1393,6 +1393,94 @@ def hessian(n_params, bands: BandTable, x, a, N=None, gp="valu"):
     ext().hessian(n_params, bands.ptr, bands.n, _ptr(x), _ptr(a), N, x.shape[1], _dev(x), _stream(x))
 
 
+# ------------------------------------------------------ GP predictive variance
+# (csrc/kf_gp_variance.hip).  The tables are built once per (emulator, centre, device) and kept here, as
+# engine/bands.py RecordCache.get_mfma keeps the analysis tables: device = the split-f16 fragments of
+# models/gp.py mfma_variance_tables, CPU = the float32 training inputs and W^ of the host runner.
+GPV_D = (4, 10)            # GP input counts with a compiled kernel
+_GPV_CACHE: dict = {}
+
+
+def _gpv_emulator(spec_or_emulator):
+    """(emulator, state map) of a GP band's OperatorSpec, or of a bare emulator (identity map)."""
+    em = getattr(spec_or_emulator, "emulator", None)
+    if em is not None or hasattr(spec_or_emulator, "state_map"):
+        return em, [int(i) for i in spec_or_emulator.state_map]
+    return spec_or_emulator, list(range(int(getattr(spec_or_emulator, "n_inputs", 0))))
+
+
+def _gpv_fields(em, dev):
+    key = (id(em), tuple(map(float, em.center())), str(dev))
+    hit = _GPV_CACHE.get(key)
+    if hit is None:
+        from scipy.linalg import solve_triangular
+
+        from ..models.gp import mfma_variance_tables
+
+        if dev.type == "cuda":
+            r = mfma_variance_tables(em)
+            val = None if r is None else (torch.from_numpy(np.ascontiguousarray(r[0]).view(np.int16)).to(dev),
+                                          torch.from_numpy(np.ascontiguousarray(r[1]).view(np.int16)).to(dev),
+                                          int(r[2]), float(1.0 / (r[3] * r[3])))
+        else:
+            w = np.sqrt(em.signal) * solve_triangular(em.cholesky(), np.eye(em.n_train), lower=True)
+            val = (torch.from_numpy(np.ascontiguousarray(em.inputs - em.center()[None, :], dtype=np.float32)),
+                   torch.from_numpy(np.ascontiguousarray(np.tril(w), dtype=np.float32)), 0, 1.0)
+        if len(_GPV_CACHE) >= 64:
+            _GPV_CACHE.clear()
+        hit = _GPV_CACHE[key] = (em, val)   # the emulator is held so its id stays unique
+    return hit[1]
+
+
+def gp_variance_supported(spec_or_emulator, device="cuda"):
+    """``(ok, reason)``: whether :func:`gp_variance` serves this GP band (or bare emulator) on ``device``."""
+    from ..models.gp import GPV_MAX_T
+
+    dev = torch.device(device)
+    em, _ = _gpv_emulator(spec_or_emulator)
+    if em is None or not all(hasattr(em, k) for k in ("inputs", "lam", "signal", "noise", "cholesky")):
+        return False, "not a GP band with its emulator (the variance needs the training inputs and the nugget)"
+    if em.noise is None:
+        return False, (f"emulator {getattr(em, 'name', '?')!r} has no noise (nugget): K + nugget cannot be rebuilt "
+                       "from alpha alone")
+    if dev.type == "cuda":
+        if em.n_inputs not in GPV_D:
+            return False, f"no predictive-variance kernel for {em.n_inputs} GP inputs (compiled: {GPV_D})"
+        tpad = 32 * -(-em.n_train // 32)
+        if tpad > GPV_MAX_T:
+            return False, (f"{em.n_train} training points pad to {tpad} > {GPV_MAX_T}: k^ of a 64-pixel tile no "
+                           "longer fits the 160 KiB of LDS")
+        if _gpv_fields(em, dev) is None:
+            return False, "the emulator's exponent operand or W^ leaves the f16 range (no matrix-core table)"
+    return True, ""
+
+
+def gp_variance(n_params, spec_or_emulator, x, out, N=None, stream=None, grid=None):
+    """Predictive variance of one GP band's emulator at the states ``x`` ``[n_params, ld]``, written to the
+    float32 plane ``out`` ``[>= N]``: ``s - k(x)^T (K + nugget)^-1 k(x)`` with the GP inputs gathered through
+    the band's state map.  On a device the triangular GEMM runs on the matrix cores
+    (csrc/kf_gp_variance.hip); CPU tensors take the float32 host loop.  A pixel with a non-finite input
+    reads NaN.  Raises ValueError with :func:`gp_variance_supported`'s reason where there is no kernel.
+    ``stream``: a raw stream handle (default: the current one); ``grid``: workgroups (default: one per
+    compute unit)."""
+    N = int(x.shape[1] if N is None else N)
+    _check_soa(x, int(n_params), N, "x")
+    _check_vec(out, N, "out", torch.float32, x.device)
+    ok, why = gp_variance_supported(spec_or_emulator, x.device)
+    if not ok:
+        raise ValueError(f"gp_variance: {why}")
+    em, smap = _gpv_emulator(spec_or_emulator)
+    if len(smap) != em.n_inputs or any(j < 0 or j >= int(n_params) for j in smap):
+        raise ValueError(f"gp_variance: state map {smap} does not fit {em.n_inputs} GP inputs of a "
+                         f"{n_params}-parameter state")
+    if N <= 0:
+        return
+    f = _gpv_fields(em, x.device)
+    ext().gp_variance(int(n_params), smap, [float(v) for v in em.center()], [float(v) for v in em.lam],
+                      float(em.signal), f[3], _ptr(f[0]), _ptr(f[1]), f[2], int(em.n_train), _ptr(x), _ptr(out), N,
+                      x.shape[1], int(grid or 0), _dev(x), _stream(x) if stream is None else int(stream))
+
+
 class TileEncoder:
     """GeoTIFF tiles encoded on the device (csrc/kf_deflate.h): each 256 x 256
     tile of each float32 plane becomes one zlib stream (TIFF predictor 3,
