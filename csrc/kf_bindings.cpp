@@ -421,6 +421,59 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     if (device) check_hip(dev_gp_operator(np, d, a, (hipStream_t)stream), "gp_operator");
     else check_host(host_gp_operator(np, a), "gp_operator");
   });
+  // K2 on the matrix cores (kf_gp_operator_mfma.hip).  bands: host copies of the descriptors, whose gpm /
+  // gpm_nchunk / gpm_scale / d fill the launch's side arrays.  gp_operator_plan: the kernels such a launch takes
+  // (kf_plan.h; family "NONE": none is planned), one name per distinct input count, and per band whether its
+  // table stays resident in LDS; no device needed.  gp_operator_mfma launches them, GPO_MAX_BANDS bands at a
+  // time, and raises where no kernel is planned.
+  m.def("gp_operator_plan", [](int np, const std::vector<BandDesc>& bands, bool device) {
+    const std::vector<KernelPlan> plans = gp_operator_plan(np, device, bands.data(), (int)bands.size());
+    py::dict d = plan_dict(plans.empty() ? KernelPlan{} : plans[0]);
+    py::list names, ds, resident;
+    for (const KernelPlan& p : plans) {
+      names.append(plan_name(p));
+      ds.append(p.fd);
+    }
+    if (!plans.empty())
+      for (const BandDesc& q : bands) resident.append(gp_operator_resident(q));
+    d["names"] = names, d["d"] = ds, d["resident"] = resident;
+    return d;
+  });
+  m.def("gp_operator_resident_chunks", [](int d) { return gpo_resident_chunks(d); });
+  m.def("gp_operator_mfma", [](int np, uintptr_t bands_dev, const std::vector<BandDesc>& bands, uintptr_t x, int64_t N,
+                               int64_t ld, uintptr_t h0, uintptr_t h, int64_t ldh, uintptr_t stream) {
+    const int nb = (int)bands.size();
+    if (gp_operator_plan(np, true, bands.data(), nb).empty())
+      throw std::invalid_argument("gp_operator_mfma: no matrix-core kernel for this launch");
+    for (int b0 = 0; b0 < nb; b0 += GPO_MAX_BANDS) {
+      GpOperatorMfmaArgs a{};
+      a.g.N = N;
+      a.g.ld = ld;
+      a.g.bands = P<const BandDesc>(bands_dev) + b0;
+      a.g.nb = std::min(GPO_MAX_BANDS, nb - b0);
+      a.g.x = P<const float>(x);
+      a.g.h0 = P<float>(h0) + (int64_t)b0 * ldh;
+      a.g.h = P<float>(h) + (int64_t)b0 * np * ldh;
+      a.g.ldh = ldh;
+      a.np = np;
+      for (int b = 0; b < a.g.nb; ++b) {
+        const BandDesc& q = bands[b0 + b];
+        a.tab[b] = q.gpm;
+        a.n_chunks[b] = q.gpm_nchunk;
+        a.scale[b] = q.gpm_scale;
+        a.d[b] = q.d;
+      }
+      check_hip(dev_gp_operator_mfma(gp_operator_plan(np, true, bands.data() + b0, a.g.nb), a, (hipStream_t)stream),
+                "gp_operator_mfma");
+    }
+  });
+  m.def("gp_operator_table", []() {
+    std::vector<KernelPlan> plans;
+    launch_table_gp_operator(plans);
+    std::vector<std::string> names;
+    for (const KernelPlan& p : plans) names.push_back(plan_name(p));
+    return names;
+  });
   m.def("hessian", [](int np, uintptr_t bands, int nb, uintptr_t x, uintptr_t a_rows, int64_t N, int64_t ld,
                       bool device, uintptr_t stream) {
     HessianArgs a{};

@@ -3887,4 +3887,28 @@ struct HessianMfmaArgs {
   float gpm_scale[HESS_MAX_BANDS];
 };
 
+// K2 on the matrix cores (kf_gp_operator_mfma.hip gp_operator_mfma_kernel<D>):
+// a workgroup serves one band and shares that band's table (models/gp.py
+// mfma_tables fragments) among its waves through LDS.  A table of at most
+// GPO_LDS_FRAGS fragments stays resident while the workgroup walks its pixels;
+// a larger one streams through two halves of GPO_RING_FRAGS fragments each.
+// 36 KiB + the zero fragment per workgroup: four workgroups per compute unit.
+constexpr int GPO_MAX_BANDS = 16;      // bands per launch (the host slices longer tables)
+constexpr int GPO_LDS_FRAGS = 2304;
+constexpr int GPO_RING_FRAGS = 1024;   // 4 cooperative 16-byte loads per thread and half
+KF_HD constexpr int gpo_resident_chunks(int D) { return GPO_LDS_FRAGS / gpm_frags_per_chunk(D); }
+KF_HD constexpr int gpo_ring_chunks(int D) { return GPO_RING_FRAGS / gpm_frags_per_chunk(D); }
+KF_HD constexpr bool gpo_d(int d) { return d == 2 || d == 3 || d == 4 || d == 7 || d == 10; }
+// The launch's per-band side arrays (BandDesc is unchanged): band b's fragment
+// table, its 32-point chunk count, the table's 2^sigma and its input count (the
+// workgroups of blockIdx.y = b run in the launch of the kernel compiled for it).
+struct GpOperatorMfmaArgs {
+  GpOperatorArgs g;
+  int32_t np;                          // state size: rows of g.x and per band of g.h
+  const void* tab[GPO_MAX_BANDS];
+  int32_t n_chunks[GPO_MAX_BANDS];
+  float scale[GPO_MAX_BANDS];
+  int32_t d[GPO_MAX_BANDS];
+};
+
 }  // namespace kf

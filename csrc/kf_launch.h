@@ -74,6 +74,10 @@ std::vector<const char*> gp_variance_table();
 int host_gp_variance(const GpVarArgs& a, const float* t, const float* w, int T);
 hipError_t dev_gp_operator(int np, int d, const GpOperatorArgs& a, hipStream_t s);
 bool gp_operator_supported(int np, int d);
+// K2 on the matrix cores (kf_gp_operator_mfma.hip): one grid per plan of gp_operator_plan (a distinct input
+// count each) over a's bands, a.g.nb <= GPO_MAX_BANDS; max_blocks caps the workgroups of a launch
+hipError_t dev_gp_operator_mfma(const std::vector<KernelPlan>& plans, const GpOperatorMfmaArgs& a, hipStream_t s);
+void launch_table_gp_operator(std::vector<KernelPlan>& out);
 hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s);
 hipError_t dev_marginal(int np, const RasterArgs& a, hipStream_t s);       // a.kind: MARG_*
 hipError_t dev_product(int np, const ProductArgs& a, hipStream_t s);       // physical-unit planes, interval, QA byte

@@ -7,6 +7,7 @@
 #pragma once
 #include <string>
 #include <type_traits>
+#include <vector>
 #include "kf_core.h"
 
 namespace kf {
@@ -34,6 +35,7 @@ enum PlanFamily : int {
   PLAN_INNOVATION_PROP_G,    // innovation_prop_g_kernel: tables in global memory
   PLAN_HESSIAN,              // pixel_kernel<NP, OpHessian>: K6, thread per pixel, the VALU record loop
   PLAN_HESSIAN_MFMA,         // hessian_mfma_kernel: K6 with the GP sums on the matrix cores, tables in global memory
+  PLAN_GP_OPERATOR_MFMA,     // gp_operator_mfma_kernel: K2 on the matrix cores, one band's table per workgroup in LDS
 };
 
 constexpr int PLAN_BLOCK = 256;   // kf_device.h BLOCK: every K1 / K1g kernel's workgroup
@@ -114,6 +116,9 @@ constexpr KernelPlan plan_innovation_prop_g_kernel(int np, int d, bool joint) {
 constexpr KernelPlan plan_hessian(int np) { return {PLAN_HESSIAN, np, 0, 0, PLAN_BLOCK}; }
 constexpr KernelPlan plan_hessian_mfma_kernel(int np, int d) { return {PLAN_HESSIAN_MFMA, np, d, 0, PLAN_BLOCK}; }
 
+// K2 on the matrix cores (kf_gp_operator_mfma.hip): 4 workgroups per compute unit by the launch bound
+constexpr KernelPlan plan_gp_operator_mfma_kernel(int d) { return {PLAN_GP_OPERATOR_MFMA, 0, d, 0, PLAN_BLOCK, 4}; }
+
 // Kernels with the bands' tables in dynamic LDS (a.gpm_frags fragments of 16 B).
 constexpr bool plan_lds_tables(const KernelPlan& p) {
   return p.family == PLAN_ANALYSIS_MFMA || p.family == PLAN_ANALYSIS_MFMA_MIXLO ||
@@ -153,6 +158,7 @@ inline std::string plan_name(const KernelPlan& p) {
       return "innovation_prop_g_kernel<" + i(p.np) + ", " + i(p.fd) + ", " + b(p.joint) + ">";
     case PLAN_HESSIAN: return "pixel_kernel<" + i(p.np) + ", kf::OpHessian>";
     case PLAN_HESSIAN_MFMA: return "hessian_mfma_kernel<" + i(p.np) + ", " + i(p.fd) + ">";
+    case PLAN_GP_OPERATOR_MFMA: return "gp_operator_mfma_kernel<" + i(p.fd) + ">";
     default: return "NONE";
   }
 }
@@ -365,5 +371,30 @@ inline KernelPlan hessian_plan(int np, const HessianMfmaArgs& a, bool device, co
   }
   return any ? plan_hessian_mfma_kernel(np, d) : valu;
 }
+
+// The kernels of a K2 launch on the matrix cores: one plan per distinct input
+// count d of the table, ascending (a workgroup's band is uniform, so bands of
+// different d share a call and each d gets a grid of its own).  hb: host copies
+// of the nb descriptors.  The family is taken when the tensors are on a device
+// and every band is an OP_GP with a fragment table, d in {2, 3, 4, 7, 10},
+// d <= np and its state map inside the state; otherwise no kernel is planned
+// (empty: the caller keeps the VALU kernel or raises).
+inline std::vector<KernelPlan> gp_operator_plan(int np, bool device, const BandDesc* hb, int nb) {
+  std::vector<KernelPlan> out;
+  if (!plan_np(np) || !device || !hb || nb < 1) return out;
+  bool has[GPM_MAX_D + 1] = {};
+  for (int b = 0; b < nb; ++b) {
+    const BandDesc& q = hb[b];
+    if (q.op != OP_GP || !gpo_d(q.d) || q.d > np || q.gpm_nchunk <= 0 || !q.gpm) return out;
+    for (int k = 0; k < q.d; ++k)
+      if (q.map[k] < 0 || q.map[k] >= np) return out;
+    has[q.d] = true;
+  }
+  for (int d = 0; d <= GPM_MAX_D; ++d)
+    if (has[d]) out.push_back(plan_gp_operator_mfma_kernel(d));
+  return out;
+}
+// band b's table stays in LDS for the workgroup's whole walk (else: the two-half ring)
+inline bool gp_operator_resident(const BandDesc& q) { return q.gpm_nchunk <= gpo_resident_chunks(q.d); }
 
 }  // namespace kf

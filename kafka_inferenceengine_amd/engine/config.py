@@ -94,6 +94,12 @@ class EngineConfig:
     # x D=10 fused 300 ms vs split 306 ms/step; 34 bands split (one chunk) 133 vs fused 142 ms.
     # On a GPU, full-state GP bands with matrix-core tables (D = n_params in 7, 10) stay fused
     # under 'auto' at any band count (global-table kernel: 34 bands 631 vs 1064 ms/step split).
+    # split_gp: how the split path's operator pass (K2) forms the GP sums.  'valu': the
+    # thread-per-pixel record loop.  'mfma': on the matrix cores where the chunk's band
+    # table allows it (ops.kernels.gp_operator_mfma_supported: device, every band a GP of
+    # 2, 3, 4, 7 or 10 inputs with a fragment table -- bands of different input counts and
+    # (n, d) pairs without a VALU kernel included) and the VALU kernel otherwise
+    split_gp: str = "valu"                    # 'valu' | 'mfma'
     gp_split_min_d: int = 99
     gp_split_min_bands: int = 13
     band_chunk: int = 0                       # bands per split chunk; 0 = as many as fit in half the free HBM
@@ -198,6 +204,8 @@ class EngineConfig:
             raise ValueError("innovation_gp must be 'valu' or 'mfma'")
         if self.hessian_gp not in ("valu", "mfma"):
             raise ValueError("hessian_gp must be 'valu' or 'mfma'")
+        if self.split_gp not in ("valu", "mfma"):
+            raise ValueError("split_gp must be 'valu' or 'mfma'")
         if self.innovation_forecast not in ("materialised", "fused"):
             raise ValueError("innovation_forecast must be 'materialised' or 'fused'")
         if self.smoother_form not in ("dense", "rank_one"):

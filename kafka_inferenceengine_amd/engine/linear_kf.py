@@ -1317,15 +1317,20 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         if cfg.gp_split == "never" or not specs or any(s.kind != OP_GP for s in specs):
             return None
         ds = {s.d for s in specs}
-        if len(ds) != 1:
-            return None
-        d = ds.pop()
         on_dev = self.device.type == "cuda"
-        if on_dev and not K.gp_operator_supported(self.n_params, d):
+        # split_gp = 'mfma': every band has a gp_operator_mfma_kernel and a fragment table, so any chunk of
+        # them does -- bands of different input counts and (n, d) pairs without a VALU kernel included
+        mfma = (cfg.split_gp == "mfma" and on_dev and self.n_params in K.SUPPORTED_NP
+                and all(s.d in K.GP_OPERATOR_MFMA_D and s.d <= self.n_params
+                        and self._cache.get_mfma(s, self.device) is not None for s in specs))
+        if len(ds) != 1 and not mfma:
+            return None
+        d = max(ds)
+        if on_dev and not mfma and not K.gp_operator_supported(self.n_params, d):
             return None
         if cfg.gp_split == "auto" and d < cfg.gp_split_min_d and len(specs) < cfg.gp_split_min_bands:
             return None
-        if (cfg.gp_split == "auto" and on_dev and d == self.n_params and d in K.GPM_GLOBAL_D
+        if (cfg.gp_split == "auto" and on_dev and len(ds) == 1 and d == self.n_params and d in K.GPM_GLOBAL_D
                 and K.DEFAULT_VARIANT != K.Variant.VALU_ORACLE and all(self._cache.get_mfma(s, self.device) is not None for s in specs)):
             # many full-state GP bands: the fused matrix-core kernel with the
             # tables in global memory beats the split path (34 bands: 631 vs
@@ -1381,7 +1386,10 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         chunks = plan["chunks"]
         prev = None
         for ci, (op_tab, an_tab, nb) in enumerate(chunks):
-            K.gp_operator(n, op_tab, x_prev, plan["h0"][:nb], plan["h"][:nb * n], N=N, d=plan["d"])
+            if self.config.split_gp == "mfma" and K.gp_operator_mfma_supported(n, op_tab, self.device):
+                K.gp_operator(n, op_tab, x_prev, plan["h0"][:nb], plan["h"][:nb * n], N=N, gp="mfma")
+            else:
+                K.gp_operator(n, op_tab, x_prev, plan["h0"][:nb], plan["h"][:nb * n], N=N, d=plan["d"])
             last = ci == len(chunks) - 1
             a_in, b_in = prev if prev is not None else (None, None)
             if last:

@@ -414,16 +414,78 @@ def tip_structure(n_params, bands: BandTable, prop, variant=None) -> int:
 
 
 # ------------------------------------------------------------------ ops
-def gp_operator(n_params, bands: BandTable, x, h0, h, N=None, d=None):
+GP_OPERATOR_GP = ("valu", "mfma")
+GP_OPERATOR_MFMA_D = (2, 3, 4, 7, 10)   # kf_core.h gpo_d: input counts with a gp_operator_mfma_kernel
+GP_OPERATOR_MFMA_KERNEL = "gp_operator_mfma_kernel"
+# the kernels the last gp_operator(gp="mfma") launch took (ext().gp_operator_plan: family, one name per distinct
+# input count, per band whether its table stays resident in LDS); None after a VALU launch
+LAST_GP_OPERATOR_PLAN = None
+
+
+def gp_operator_plan(n_params, bands: BandTable, device):
+    """The kernels ``gp_operator(gp="mfma")`` takes for ``bands`` on ``device`` (kf_plan.h ``gp_operator_plan``).
+    The fragment tables are the descriptors' own (engine/bands.py ``RecordCache.get_mfma``, per band spec and
+    device)."""
+    on = torch.device(device).type == "cuda" and len(bands.descs) == bands.n
+    return ext().gp_operator_plan(int(n_params), list(bands.descs) if on else [], on)
+
+
+def gp_operator_mfma_unsupported(n_params, bands: BandTable, device):
+    """Why ``gp_operator(gp="mfma")`` cannot serve this table on this device, or None where it can."""
+    if torch.device(device).type != "cuda":
+        return "the matrix-core operator kernel has no host twin (device tensors only)"
+    if n_params not in SUPPORTED_NP:
+        return f"n_params={n_params} has no compiled kernel"
+    if len(bands.descs) != bands.n or bands.n < 1:
+        return "the table carries no host copies of its descriptors"
+    for b, q in enumerate(bands.descs):
+        if q.op != OP_GP:
+            return f"band {b} is not a GP emulator (operator kind {q.op})"
+        if q.d not in GP_OPERATOR_MFMA_D or q.d > n_params:
+            return f"band {b} has {q.d} inputs: the kernels take {GP_OPERATOR_MFMA_D}, at most n_params"
+        if q.gpm_nchunk <= 0 or not q.gpm:
+            return f"band {b} has no split-f16 fragment table (models/gp.py mfma_tables)"
+    if gp_operator_plan(n_params, bands, device)["family"] != GP_OPERATOR_MFMA_KERNEL:
+        return "no matrix-core operator kernel is planned for this table"
+    return None
+
+
+def gp_operator_mfma_supported(n_params, bands: BandTable, device) -> bool:
+    return gp_operator_mfma_unsupported(n_params, bands, device) is None
+
+
+def gp_operator(n_params, bands: BandTable, x, h0, h, N=None, d=None, gp="valu"):
     """K2 split path: GP value/Jacobian of every band of ``bands`` at x into
-    h0 [nb, ldh] and h [nb*n_params, ldh] (masked pixels: zeros)."""
+    h0 [nb, ldh] and h [nb*n_params, ldh] (masked pixels: zeros).
+
+    ``gp="mfma"`` forms the sums on the matrix cores (csrc/kf_gp_operator_mfma.hip) instead of the
+    thread-per-pixel VALU record loop: a workgroup per band and pixel group with the band's fragment table
+    shared through LDS.  Bands of different input counts may share the call (``d`` is ignored); a table the
+    kernels cannot serve raises ValueError with the reason (:func:`gp_operator_mfma_supported` asks without
+    raising).  The values differ from the VALU loop's by the rounding of the sums.  The kernels taken are
+    recorded in ``LAST_GP_OPERATOR_PLAN``."""
     check_np(n_params)
+    if gp not in GP_OPERATOR_GP:
+        raise ValueError("gp must be 'valu' or 'mfma'")
     N = int(x.shape[1] if N is None else N)
     _check_soa(x, n_params, N, "x")
     nb = bands.n
-    d = bands.fast_d if d is None else d
     if h0.shape[0] != nb or h.shape[0] != nb * n_params or h0.shape[1] != h.shape[1] or h0.shape[1] < N:
         raise ValueError("h0 must be [nb, ldh] and h [nb*n_params, ldh]")
+    global LAST_GP_OPERATOR_PLAN
+    if gp == "mfma":
+        why = gp_operator_mfma_unsupported(n_params, bands, x.device)
+        if why is not None:
+            raise ValueError(f"gp_operator(gp='mfma'): {why}")
+        for t, name in ((h0, "h0"), (h, "h")):
+            if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 tensor on {x.device}")
+        LAST_GP_OPERATOR_PLAN = gp_operator_plan(n_params, bands, x.device)
+        ext().gp_operator_mfma(int(n_params), bands.ptr, list(bands.descs), _ptr(x), N, x.shape[1], _ptr(h0), _ptr(h),
+                               h0.shape[1], _stream(x))
+        return
+    LAST_GP_OPERATOR_PLAN = None
+    d = bands.fast_d if d is None else d
     if _dev(x) and not ext().gp_operator_supported(n_params, int(d)):
         raise ValueError(f"no gp_operator kernel for n_params={n_params}, d={d}")
     ext().gp_operator(n_params, int(d), bands.ptr, nb, _ptr(x), N, x.shape[1], _ptr(h0), _ptr(h), h0.shape[1],
