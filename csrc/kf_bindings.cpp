@@ -474,6 +474,64 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     for (const KernelPlan& p : plans) names.push_back(plan_name(p));
     return names;
   });
+  // K2 in float64 on the FP64 matrix cores (kf_gp_operator_f64.hip).  groups[b]: the 16-point groups of band b's
+  // float64 table (0: none); tabs[b] / doubles[b]: its device address and length.  gp_operator_f64_plan: the
+  // kernels such a launch takes (family "NONE": none is planned), one name per distinct K-step count "nk"; no
+  // device needed.  gp_operator_f64 launches them, GPO_MAX_BANDS bands at a time, and raises where no kernel is
+  // planned or a table is shorter than its groups.
+  m.def("gp_operator_f64_plan", [](int np, const std::vector<BandDesc>& bands, const std::vector<int32_t>& groups,
+                                   bool device) {
+    std::vector<KernelPlan> plans;
+    if (groups.size() == bands.size())
+      plans = gp_operator_f64_plan(np, device, bands.data(), groups.data(), (int)bands.size());
+    py::dict d = plan_dict(plans.empty() ? KernelPlan{} : plans[0]);
+    py::list names, nks;
+    for (const KernelPlan& p : plans) {
+      names.append(plan_name(p));
+      nks.append(p.fd);
+    }
+    d["names"] = names, d["nk"] = nks;
+    return d;
+  });
+  m.def("gp_operator_f64", [](int np, uintptr_t bands_dev, const std::vector<BandDesc>& bands,
+                              const std::vector<uintptr_t>& tabs, const std::vector<int32_t>& groups,
+                              const std::vector<int64_t>& doubles, uintptr_t x, int64_t N, int64_t ld, uintptr_t h0,
+                              uintptr_t h, int64_t ldh, uintptr_t stream) {
+    const int nb = (int)bands.size();
+    if ((int)tabs.size() != nb || (int)groups.size() != nb || (int)doubles.size() != nb ||
+        gp_operator_f64_plan(np, true, bands.data(), groups.data(), nb).empty())
+      throw std::invalid_argument("gp_operator_f64: no float64 kernel for this launch");
+    for (int b = 0; b < nb; ++b)
+      if (!tabs[b] || doubles[b] < GPF_HEADER + (int64_t)groups[b] * gpf_group_doubles(gpf_k_steps(bands[b].d)))
+        throw std::invalid_argument("gp_operator_f64: a band's table is shorter than its groups");
+    for (int b0 = 0; b0 < nb; b0 += GPO_MAX_BANDS) {
+      GpOperatorF64Args a{};
+      a.g.N = N;
+      a.g.ld = ld;
+      a.g.bands = P<const BandDesc>(bands_dev) + b0;
+      a.g.nb = std::min(GPO_MAX_BANDS, nb - b0);
+      a.g.x = P<const float>(x);
+      a.g.h0 = P<float>(h0) + (int64_t)b0 * ldh;
+      a.g.h = P<float>(h) + (int64_t)b0 * np * ldh;
+      a.g.ldh = ldh;
+      a.np = np;
+      for (int b = 0; b < a.g.nb; ++b) {
+        a.tab[b] = P<const double>(tabs[b0 + b]);
+        a.n_groups[b] = groups[b0 + b];
+        a.d[b] = bands[b0 + b].d;
+      }
+      check_hip(dev_gp_operator_f64(gp_operator_f64_plan(np, true, bands.data() + b0, groups.data() + b0, a.g.nb), a,
+                                    (hipStream_t)stream),
+                "gp_operator_f64");
+    }
+  });
+  m.def("gp_operator_f64_table", []() {
+    std::vector<KernelPlan> plans;
+    launch_table_gp_operator_f64(plans);
+    std::vector<std::string> names;
+    for (const KernelPlan& p : plans) names.push_back(plan_name(p));
+    return names;
+  });
   m.def("hessian", [](int np, uintptr_t bands, int nb, uintptr_t x, uintptr_t a_rows, int64_t N, int64_t ld,
                       bool device, uintptr_t stream) {
     HessianArgs a{};

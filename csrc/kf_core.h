@@ -3911,4 +3911,52 @@ struct GpOperatorMfmaArgs {
   int32_t d[GPO_MAX_BANDS];
 };
 
+// K2 in float64 on the FP64 matrix cores (kf_gp_operator_f64.hip
+// gp_operator_f64_kernel<NK>): a band's table (models/gp.py f64_tables) is
+// GPF_HEADER doubles -- scale, offset, then the centre and lambda of GPF_MAX_D
+// input slots (slots past d zero) -- followed per group of 16 training points by
+// gpf_group_doubles(NK) doubles in lane order: NK x 64 exponent A operands, the
+// 16 row constants, 4 x 64 sums A operands.  NK = gpf_k_steps(d) K steps of 4
+// inputs.
+constexpr int GPF_MAX_D = 12;          // input slots of the header: 4 x the largest NK
+constexpr int GPF_HEADER = 32;         // 2 + 2 GPF_MAX_D, padded to 256 B
+constexpr int GPF_CENTER = 2, GPF_LAM = 2 + GPF_MAX_D;
+KF_HD constexpr int gpf_k_steps(int d) { return (d + 3) / 4; }
+KF_HD constexpr int gpf_group_doubles(int nk) { return 64 * nk + 16 + 256; }
+KF_HD constexpr bool gpf_d(int d) { return d >= 1 && d <= GPM_MAX_D; }
+// The launch's per-band side arrays (BandDesc is unchanged): band b's table, its
+// 16-point groups and its input count.
+struct GpOperatorF64Args {
+  GpOperatorArgs g;
+  int32_t np;                          // state size: rows of g.x and per band of g.h
+  const double* tab[GPO_MAX_BANDS];
+  int32_t n_groups[GPO_MAX_BANDS];
+  int32_t d[GPO_MAX_BANDS];
+};
+
+// 2^x in float64 for the GP exponent (x <= 0 up to rounding): x = n + f with
+// n = rint(x), |f| <= 1/2; 2^f = sum_k (ln 2)^k / k! f^k through k = 12 (the
+// remainder is below 2^-52 of the value), scaled by ldexp.  Zero below the
+// double range, +inf above it, NaN kept (the comparisons do not replace it).
+// Relative error below 2^-50: the Horner steps' roundings.
+KF_HD double kexp2_f64(double x) {
+  x = x < -1100.0 ? -1100.0 : x;
+  x = x > 1100.0 ? 1100.0 : x;
+  const double n = __builtin_rint(x), f = x - n;
+  double p = 2.5678435993488206e-11;
+  p = __builtin_fma(p, f, 4.4455382718708116e-10);
+  p = __builtin_fma(p, f, 7.054911620801123e-09);
+  p = __builtin_fma(p, f, 1.01780860092397e-07);
+  p = __builtin_fma(p, f, 1.321548679014431e-06);
+  p = __builtin_fma(p, f, 1.5252733804059841e-05);
+  p = __builtin_fma(p, f, 0.0001540353039338161);
+  p = __builtin_fma(p, f, 0.0013333558146428443);
+  p = __builtin_fma(p, f, 0.009618129107628477);
+  p = __builtin_fma(p, f, 0.05550410866482158);
+  p = __builtin_fma(p, f, 0.24022650695910072);
+  p = __builtin_fma(p, f, 0.6931471805599453);
+  p = __builtin_fma(p, f, 1.0);
+  return __builtin_ldexp(p, (int)n);
+}
+
 }  // namespace kf

@@ -78,6 +78,9 @@ bool gp_operator_supported(int np, int d);
 // count each) over a's bands, a.g.nb <= GPO_MAX_BANDS; max_blocks caps the workgroups of a launch
 hipError_t dev_gp_operator_mfma(const std::vector<KernelPlan>& plans, const GpOperatorMfmaArgs& a, hipStream_t s);
 void launch_table_gp_operator(std::vector<KernelPlan>& out);
+// K2 in float64 (kf_gp_operator_f64.hip): one grid per plan of gp_operator_f64_plan (a distinct NK each)
+hipError_t dev_gp_operator_f64(const std::vector<KernelPlan>& plans, const GpOperatorF64Args& a, hipStream_t s);
+void launch_table_gp_operator_f64(std::vector<KernelPlan>& out);
 hipError_t dev_unpack(int np, const RasterArgs& a, hipStream_t s);
 hipError_t dev_marginal(int np, const RasterArgs& a, hipStream_t s);       // a.kind: MARG_*
 hipError_t dev_product(int np, const ProductArgs& a, hipStream_t s);       // physical-unit planes, interval, QA byte

@@ -36,6 +36,7 @@ enum PlanFamily : int {
   PLAN_HESSIAN,              // pixel_kernel<NP, OpHessian>: K6, thread per pixel, the VALU record loop
   PLAN_HESSIAN_MFMA,         // hessian_mfma_kernel: K6 with the GP sums on the matrix cores, tables in global memory
   PLAN_GP_OPERATOR_MFMA,     // gp_operator_mfma_kernel: K2 on the matrix cores, one band's table per workgroup in LDS
+  PLAN_GP_OPERATOR_F64,      // gp_operator_f64_kernel: K2 in float64 on the FP64 matrix cores, tables in global memory
 };
 
 constexpr int PLAN_BLOCK = 256;   // kf_device.h BLOCK: every K1 / K1g kernel's workgroup
@@ -159,6 +160,7 @@ inline std::string plan_name(const KernelPlan& p) {
     case PLAN_HESSIAN: return "pixel_kernel<" + i(p.np) + ", kf::OpHessian>";
     case PLAN_HESSIAN_MFMA: return "hessian_mfma_kernel<" + i(p.np) + ", " + i(p.fd) + ">";
     case PLAN_GP_OPERATOR_MFMA: return "gp_operator_mfma_kernel<" + i(p.fd) + ">";
+    case PLAN_GP_OPERATOR_F64: return "gp_operator_f64_kernel<" + i(p.fd) + ">";
     default: return "NONE";
   }
 }
@@ -396,5 +398,32 @@ inline std::vector<KernelPlan> gp_operator_plan(int np, bool device, const BandD
 }
 // band b's table stays in LDS for the workgroup's whole walk (else: the two-half ring)
 inline bool gp_operator_resident(const BandDesc& q) { return q.gpm_nchunk <= gpo_resident_chunks(q.d); }
+
+// K2 in float64 (kf_gp_operator_f64.hip): fd is NK, the K steps of 4 inputs; 2 workgroups per compute unit by
+// the launch bound
+constexpr KernelPlan plan_gp_operator_f64_kernel(int nk) { return {PLAN_GP_OPERATOR_F64, 0, nk, 0, PLAN_BLOCK, 2}; }
+
+// The kernels of a float64 K2 launch: one plan per distinct NK = gpf_k_steps(d)
+// of the table, ascending, as gp_operator_plan has one per d.  groups[b]: the
+// 16-point groups of band b's float64 table (models/gp.py f64_tables; 0: the
+// band has none).  The family is taken when the tensors are on a device and
+// every band is an OP_GP with a table, 1 <= d <= 10, d <= np and its state map
+// inside the state; otherwise no kernel is planned.
+inline std::vector<KernelPlan> gp_operator_f64_plan(int np, bool device, const BandDesc* hb, const int32_t* groups,
+                                                    int nb) {
+  std::vector<KernelPlan> out;
+  if (!plan_np(np) || !device || !hb || !groups || nb < 1) return out;
+  bool has[gpf_k_steps(GPM_MAX_D) + 1] = {};
+  for (int b = 0; b < nb; ++b) {
+    const BandDesc& q = hb[b];
+    if (q.op != OP_GP || !gpf_d(q.d) || q.d > np || groups[b] <= 0) return out;
+    for (int k = 0; k < q.d; ++k)
+      if (q.map[k] < 0 || q.map[k] >= np) return out;
+    has[gpf_k_steps(q.d)] = true;
+  }
+  for (int nk = 1; nk <= gpf_k_steps(GPM_MAX_D); ++nk)
+    if (has[nk]) out.push_back(plan_gp_operator_f64_kernel(nk));
+  return out;
+}
 
 }  // namespace kf

@@ -39,8 +39,8 @@ HEADERS = ["kf_core.h", "kf_plan.h", "kf_launch.h", "kf_stream.h", "kf_device.h"
 # device translation units (compiled concurrently: the NP = 7 / 10 analysis
 # instantiations dominate the build)
 HIP_SOURCES = ["kf_kernels.hip", "kf_analysis7.hip", "kf_analysis10.hip", "kf_gain10.hip", "kf_innovation_mfma.hip",
-               "kf_hessian_mfma.hip", "kf_gp_variance.hip", "kf_gp_operator_mfma.hip", "kf_reg_tiled.hip",
-               "kf_deflate.hip", "kf_inflate.hip"]
+               "kf_hessian_mfma.hip", "kf_gp_variance.hip", "kf_gp_operator_mfma.hip", "kf_gp_operator_f64.hip",
+               "kf_reg_tiled.hip", "kf_deflate.hip", "kf_inflate.hip"]
 # per-unit device flags: the innovation unit is built with the packed f32 VALU
 # operations (v_pk_add/mul/fma_f32) off, so its per-lane statistics stay scalar FMAs
 HIP_EXTRA_FLAGS = {"kf_innovation_mfma.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}

@@ -14,7 +14,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 import torch
 
-from ..models.gp import mfma_tables
+from ..models.gp import f64_tables, mfma_tables
 from ..models.operators import OP_GP, OP_LINEAR, OP_PRECOMP, OP_SAR, OperatorSpec
 from ..ops import kernels as K
 
@@ -81,6 +81,22 @@ class RecordCache:
     def __init__(self):
         self._c = {}
         self._m = {}
+        self._f = {}
+
+    def get_f64(self, spec: OperatorSpec, device):
+        """(table tensor, n_groups) of the float64 GP operator (models/gp.py ``f64_tables``, built from the
+        float64 emulator the spec carries), or None: a spec with records only, or an emulator the kernel
+        cannot serve."""
+        if spec.emulator is None:
+            return None
+        key = (id(spec.emulator), str(device))
+        hit = self._f.get(key)
+        if hit is None:
+            built = f64_tables(spec.emulator)
+            if built is not None:
+                built = (torch.from_numpy(built[0]).to(device), int(built[1]))
+            hit = self._f[key] = (built, spec.emulator)   # the emulator is held so its id stays unique
+        return hit[0]
 
     def get_mfma(self, spec: OperatorSpec, device):
         """(table tensor, n_chunks, scale) of the matrix-core GP path, or None
@@ -242,7 +258,7 @@ def build_table(specs, obs_list, n_params, cache, device, h0_outs=None, pre=None
         dsc, kp = band_desc(spec, ob, n_params, cache, h0, ph0, ph)
         descs.append(dsc)
         keep += kp
-    return K.make_band_table(descs, device, keep, specs)
+    return K.make_band_table(descs, device, keep, specs, cache)
 
 
 def operator_table(specs, n_params, cache, device, aux=None) -> K.BandTable:

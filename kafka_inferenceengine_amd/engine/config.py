@@ -99,7 +99,11 @@ class EngineConfig:
     # table allows it (ops.kernels.gp_operator_mfma_supported: device, every band a GP of
     # 2, 3, 4, 7 or 10 inputs with a fragment table -- bands of different input counts and
     # (n, d) pairs without a VALU kernel included) and the VALU kernel otherwise
-    split_gp: str = "valu"                    # 'valu' | 'mfma'
+    # 'f64': in float64 on the FP64 matrix cores, rounded to float32 once on the store (the error is
+    # relative to the result, as in the reference's float64 emulators, not to the cancelling terms),
+    # where ops.kernels.gp_operator_f64_supported: device, every band a GP of 1..10 inputs built from
+    # a float64 emulator; the VALU kernel otherwise.  Slower than 'mfma' (BENCHMARKS.md).
+    split_gp: str = "valu"                    # 'valu' | 'mfma' | 'f64'
     gp_split_min_d: int = 99
     gp_split_min_bands: int = 13
     band_chunk: int = 0                       # bands per split chunk; 0 = as many as fit in half the free HBM
@@ -204,8 +208,8 @@ class EngineConfig:
             raise ValueError("innovation_gp must be 'valu' or 'mfma'")
         if self.hessian_gp not in ("valu", "mfma"):
             raise ValueError("hessian_gp must be 'valu' or 'mfma'")
-        if self.split_gp not in ("valu", "mfma"):
-            raise ValueError("split_gp must be 'valu' or 'mfma'")
+        if self.split_gp not in ("valu", "mfma", "f64"):
+            raise ValueError("split_gp must be 'valu', 'mfma' or 'f64'")
         if self.innovation_forecast not in ("materialised", "fused"):
             raise ValueError("innovation_forecast must be 'materialised' or 'fused'")
         if self.smoother_form not in ("dense", "rank_one"):

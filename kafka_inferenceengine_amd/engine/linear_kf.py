@@ -1323,6 +1323,10 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         mfma = (cfg.split_gp == "mfma" and on_dev and self.n_params in K.SUPPORTED_NP
                 and all(s.d in K.GP_OPERATOR_MFMA_D and s.d <= self.n_params
                         and self._cache.get_mfma(s, self.device) is not None for s in specs))
+        # split_gp = 'f64': the same, with a gp_operator_f64_kernel for every input count up to 10
+        mfma = mfma or (cfg.split_gp == "f64" and on_dev and self.n_params in K.SUPPORTED_NP
+                        and all(1 <= s.d <= min(K.GP_OPERATOR_F64_MAX_D, self.n_params)
+                                and self._cache.get_f64(s, self.device) is not None for s in specs))
         if len(ds) != 1 and not mfma:
             return None
         d = max(ds)
@@ -1388,6 +1392,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         for ci, (op_tab, an_tab, nb) in enumerate(chunks):
             if self.config.split_gp == "mfma" and K.gp_operator_mfma_supported(n, op_tab, self.device):
                 K.gp_operator(n, op_tab, x_prev, plan["h0"][:nb], plan["h"][:nb * n], N=N, gp="mfma")
+            elif self.config.split_gp == "f64" and K.gp_operator_f64_supported(n, op_tab, self.device):
+                K.gp_operator(n, op_tab, x_prev, plan["h0"][:nb], plan["h"][:nb * n], N=N, gp="f64")
             else:
                 K.gp_operator(n, op_tab, x_prev, plan["h0"][:nb], plan["h"][:nb * n], N=N, d=plan["d"])
             last = ci == len(chunks) - 1

@@ -895,3 +895,81 @@ def make_prosail_emulators(n_bands: int = 10, n_train: int = 250, seed: int = 0,
                                               n_train, seed + b, noise=noise,
                                               name=f"prosail_b{b}{'h' if hard else ''}")
             .set_center(mean[:n_params]) for b in range(n_bands)]
+
+
+# --------------------------------------------------------------------------
+# float64 tables (csrc/kf_gp_operator_f64.hip): the operands of the FP64 matrix
+# instruction v_mfma_f64_16x16x4_f64, one double per lane.  Lane l of an A
+# operand holds row l % 16 and K slot l // 16; register r of lane l of a result
+# holds row 4 r + l // 16 (column l % 16).
+
+F64_MAX_D = 12           # kf_core.h GPF_MAX_D: input slots of the header
+F64_HEADER = 32          # kf_core.h GPF_HEADER
+
+
+def f64_k_steps(d: int) -> int:
+    """K steps of 4 inputs of the exponent GEMM."""
+    return (d + 3) // 4
+
+
+def f64_group_doubles(nk: int) -> int:
+    return 64 * nk + 16 + 256
+
+
+def _f64_point(r, k):
+    """Point of a 16-point group whose exponent lands in accumulator register r
+    of lane block k: the result layout of the instruction."""
+    return 4 * r + k
+
+
+def f64_tables(em):
+    """Operands of the float64 GP operator kernel from the float64 emulator
+    ``em`` itself (``inputs``, ``alpha``, ``lam``, ``signal``, ``mean`` and its
+    centre, as ``predict`` uses them): ``(table float64 [F64_HEADER + n_groups *
+    f64_group_doubles(NK)], n_groups)``.
+
+    Header: ``signal``, ``mean``, then the centre and ``lam`` of F64_MAX_D input
+    slots (zero past D).  Then per group of 16 training points (weight-zero
+    padded), in the lane order of the kernel's loads: the exponent A operands
+    ``B_id = lam_d t_id log2e`` for each K step of 4 inputs (t: the centred
+    training inputs); the 16 row constants ``L'_i = -1/2 log2e sum lam_d
+    t_id^2`` at ``4 k + r`` for the point of register r, lane block k; the four
+    sums A operands, rows ``[alpha_i; alpha_i B_i1 .. alpha_i B_iD]`` (row f =
+    field f), column k of operand r the same point.  None where the emulator
+    does not expose those parameters, D is outside 1..10 or a value is not
+    finite."""
+    if not all(hasattr(em, a) for a in ("inputs", "alpha", "lam", "signal", "mean", "center")):
+        return None
+    X = np.asarray(em.inputs, dtype=np.float64)
+    alpha = np.asarray(em.alpha, dtype=np.float64)
+    lam = np.asarray(em.lam, dtype=np.float64)
+    if X.ndim != 2 or not 1 <= X.shape[1] <= GPM_MAX_D or X.shape[0] < 1:
+        return None
+    T, D = X.shape
+    cen = np.asarray(em.center(), dtype=np.float64)
+    t = X - cen[None, :]
+    NK = f64_k_steps(D)
+    ng = -(-T // 16)
+    B = np.zeros((16 * ng, 4 * NK))
+    B[:T, :D] = LOG2E * lam[None, :] * t
+    L = np.zeros(16 * ng)
+    L[:T] = -0.5 * LOG2E * (t * t * lam[None, :]).sum(1)
+    F = np.zeros((16, 16 * ng))
+    F[0, :T] = alpha
+    F[1:1 + D] = F[0][None, :] * B[:, :D].T
+    head = np.zeros(F64_HEADER)
+    head[0], head[1] = float(em.signal), float(em.mean)
+    head[2:2 + D], head[2 + F64_MAX_D:2 + F64_MAX_D + D] = cen, lam
+    if not all(np.isfinite(a).all() for a in (B, L, F, head)):
+        return None
+    lane = np.arange(64)
+    row, k = lane % 16, lane // 16
+    base = 16 * np.arange(ng)[:, None]
+    out = np.zeros((ng, f64_group_doubles(NK)))
+    for kk in range(NK):
+        out[:, 64 * kk:64 * kk + 64] = B[base + row[None, :], (4 * kk + k)[None, :]]
+    o = 64 * NK
+    for r in range(4):
+        out[:, o + 4 * np.arange(4) + r] = L[base + _f64_point(r, np.arange(4))[None, :]]
+        out[:, o + 16 + 64 * r:o + 16 + 64 * r + 64] = F[row[None, :], base + _f64_point(r, k)[None, :]]
+    return np.concatenate([head, out.reshape(-1)]), ng

@@ -139,6 +139,7 @@ class BandTable:
     specs: tuple = ()       # the bands' OperatorSpecs (line tables of the first iteration at the forecast)
     tip_maps: bool = False  # exactly two 4-input GP bands with the JRC-TIP VIS then NIR state maps
     descs: tuple = ()       # host copies of the descriptors (the straight-line JRC-TIP kernel's constants)
+    cache: object = None    # the RecordCache the table was built through (gp_operator(gp="f64"): get_f64)
 
     @property
     def ptr(self) -> int:
@@ -245,7 +246,7 @@ def small_h2d(cpu: torch.Tensor, device) -> torch.Tensor:
     return cpu.pin_memory().to(device, non_blocking=True)
 
 
-def make_band_table(descs: list, device, keepalive=(), specs=()) -> BandTable:
+def make_band_table(descs: list, device, keepalive=(), specs=(), cache=None) -> BandTable:
     raw = ext().pack_band_descs(descs)
     cpu = torch.frombuffer(bytearray(raw), dtype=torch.uint8) if raw else torch.zeros(8, dtype=torch.uint8)
     buf = small_h2d(cpu, device)
@@ -276,7 +277,7 @@ def make_band_table(descs: list, device, keepalive=(), specs=()) -> BandTable:
     tip_maps = len(descs) == 2 and all(d.op == OP_GP and d.d == 4 for d in descs) and \
         [d.map_kind for d in descs] == [2, 3]
     return BandTable(buf, len(descs), tuple(keepalive), fast_d, fast_obs, gpm_frags, gpm_global, layout,
-                     _state_domain(descs), tuple(specs), tip_maps, tuple(descs))
+                     _state_domain(descs), tuple(specs), tip_maps, tuple(descs), cache)
 
 
 def _state_domain(descs):
@@ -414,7 +415,7 @@ def tip_structure(n_params, bands: BandTable, prop, variant=None) -> int:
 
 
 # ------------------------------------------------------------------ ops
-GP_OPERATOR_GP = ("valu", "mfma")
+GP_OPERATOR_GP = ("valu", "mfma", "f64")
 GP_OPERATOR_MFMA_D = (2, 3, 4, 7, 10)   # kf_core.h gpo_d: input counts with a gp_operator_mfma_kernel
 GP_OPERATOR_MFMA_KERNEL = "gp_operator_mfma_kernel"
 # the kernels the last gp_operator(gp="mfma") launch took (ext().gp_operator_plan: family, one name per distinct
@@ -466,13 +467,15 @@ def gp_operator(n_params, bands: BandTable, x, h0, h, N=None, d=None, gp="valu")
     recorded in ``LAST_GP_OPERATOR_PLAN``."""
     check_np(n_params)
     if gp not in GP_OPERATOR_GP:
-        raise ValueError("gp must be 'valu' or 'mfma'")
+        raise ValueError("gp must be 'valu', 'mfma' or 'f64'")
     N = int(x.shape[1] if N is None else N)
     _check_soa(x, n_params, N, "x")
     nb = bands.n
     if h0.shape[0] != nb or h.shape[0] != nb * n_params or h0.shape[1] != h.shape[1] or h0.shape[1] < N:
         raise ValueError("h0 must be [nb, ldh] and h [nb*n_params, ldh]")
     global LAST_GP_OPERATOR_PLAN
+    if gp == "f64":    # float64 on the FP64 matrix cores: _gp_operator_f64, at the end of this file
+        return _gp_operator_f64(n_params, bands, x, h0, h, N)
     if gp == "mfma":
         why = gp_operator_mfma_unsupported(n_params, bands, x.device)
         if why is not None:
@@ -2260,3 +2263,69 @@ def lut_nearest(lut, x, out=None, N=None):
         out = torch.empty(N, dtype=torch.int32, device=x.device)
     ext().lut_nearest(_ptr(lut), M, D, _ptr(x), N, x.shape[1], _ptr(out), _dev(x), _stream(x))
     return out
+
+
+# ------------------------------------------------ K2 in float64 (csrc/kf_gp_operator_f64.hip)
+GP_OPERATOR_F64_MAX_D = 10   # kf_core.h gpf_d: 1..10 inputs, NK = ceil(d / 4) K steps
+GP_OPERATOR_F64_KERNEL = "gp_operator_f64_kernel"
+
+
+def _gp_operator_f64_tables(bands: BandTable, device):
+    """Per band the float64 table ``(tensor, n_groups)`` or None (engine/bands.py ``RecordCache.get_f64``: built
+    from the float64 emulator the band's spec carries, uploaded once per emulator and device)."""
+    if bands.cache is None or len(bands.specs) != bands.n:
+        return [None] * bands.n
+    return [bands.cache.get_f64(sp, device) if getattr(sp, "kind", None) == OP_GP else None for sp in bands.specs]
+
+
+def gp_operator_f64_plan(n_params, bands: BandTable, device):
+    """The kernels ``gp_operator(gp="f64")`` takes for ``bands`` on ``device`` (kf_plan.h ``gp_operator_f64_plan``)."""
+    on = torch.device(device).type == "cuda" and len(bands.descs) == bands.n
+    groups = [0 if t is None else t[1] for t in _gp_operator_f64_tables(bands, device)] if on else []
+    return ext().gp_operator_f64_plan(int(n_params), list(bands.descs) if on else [], groups, on)
+
+
+def gp_operator_f64_unsupported(n_params, bands: BandTable, device):
+    """Why ``gp_operator(gp="f64")`` cannot serve this table on this device, or None where it can."""
+    if torch.device(device).type != "cuda":
+        return "the float64 operator kernel has no host twin (device tensors only)"
+    if n_params not in SUPPORTED_NP:
+        return f"n_params={n_params} has no compiled kernel"
+    if len(bands.descs) != bands.n or bands.n < 1:
+        return "the table carries no host copies of its descriptors"
+    tabs = _gp_operator_f64_tables(bands, device)
+    for b, q in enumerate(bands.descs):
+        if q.op != OP_GP:
+            return f"band {b} is not a GP emulator (operator kind {q.op})"
+        if not 1 <= q.d <= min(GP_OPERATOR_F64_MAX_D, n_params):
+            return f"band {b} has {q.d} inputs: the kernels take 1..{GP_OPERATOR_F64_MAX_D}, at most n_params"
+        if tabs[b] is None:
+            return (f"band {b} has no float64 table (models/gp.py f64_tables): its spec carries no float64 emulator, "
+                    "or the table was not built through a RecordCache")
+    if gp_operator_f64_plan(n_params, bands, device)["family"] != GP_OPERATOR_F64_KERNEL:
+        return "no float64 operator kernel is planned for this table"
+    return None
+
+
+def gp_operator_f64_supported(n_params, bands: BandTable, device) -> bool:
+    return gp_operator_f64_unsupported(n_params, bands, device) is None
+
+
+def _gp_operator_f64(n_params, bands: BandTable, x, h0, h, N):
+    """``gp_operator(gp="f64")`` after its shape checks: the emulator's value and Jacobian in float64 on the FP64
+    matrix cores from the float64 emulator's own parameters, rounded to float32 once on the store.  Bands of
+    different input counts (1..10) may share the call; a table the kernels cannot serve raises ValueError with
+    the reason (:func:`gp_operator_f64_supported` asks without raising); never the VALU loop instead.  The
+    kernels taken are recorded in ``LAST_GP_OPERATOR_PLAN``."""
+    global LAST_GP_OPERATOR_PLAN
+    why = gp_operator_f64_unsupported(n_params, bands, x.device)
+    if why is not None:
+        raise ValueError(f"gp_operator(gp='f64'): {why}")
+    for t, name in ((h0, "h0"), (h, "h")):
+        if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 tensor on {x.device}")
+    tabs = _gp_operator_f64_tables(bands, x.device)
+    LAST_GP_OPERATOR_PLAN = gp_operator_f64_plan(n_params, bands, x.device)
+    ext().gp_operator_f64(int(n_params), bands.ptr, list(bands.descs), [_ptr(t[0]) for t in tabs],
+                          [t[1] for t in tabs], [t[0].numel() for t in tabs], _ptr(x), N, x.shape[1], _ptr(h0),
+                          _ptr(h), h0.shape[1], _stream(x))

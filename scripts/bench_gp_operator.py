@@ -12,7 +12,8 @@ for 10 inputs, make_tip_emulators for 4, one seed per band pair) on the JRC-TIP 
 under cloud (both kernels skip a wave no lane of which observes), the state drawn from the
 training inputs, ``--size``^2 pixels.  The child warms both kernels up, then times
 ``K.gp_operator(gp="valu")`` and ``gp="mfma"`` alternating with device events (median, minimum
-and maximum of ``--reps`` calls each) and records the largest difference of the two results.
+and maximum of ``--reps`` calls each) and records the largest difference of the two results.  ``--f64`` adds ``gp="f64"``
+(csrc/kf_gp_operator_f64.hip) as a third alternating arm, with its ratio to the matrix-core kernel.
 
 ``engine:CONFIG``: ``bench.py --config CONFIG --set gp_split=always --set convergence_chunk=tile``
 (the per-chunk exit test keeps a date fused) under ``--set split_gp=valu`` and ``--set split_gp=mfma``, a fresh process per run, the two settings alternating twice,
@@ -40,7 +41,7 @@ def stats(rec, key, v):
         round(statistics.median(v), 3), round(min(v), 3), round(max(v), 3)
 
 
-def kernel_config(config, size, reps):
+def kernel_config(config, size, reps, f64=False):
     import numpy as np
     import torch
 
@@ -73,10 +74,16 @@ def kernel_config(config, size, reps):
     xd = torch.from_numpy(x).to(dev)
     h0, h = torch.empty((nb, N), device=dev), torch.empty((nb * n, N), device=dev)
     ms, out = {"valu": [], "mfma": []}, {}
+    if f64:                                  # the float64 kernel (csrc/kf_gp_operator_f64.hip) as a third arm
+        why = K.gp_operator_f64_unsupported(n, table, dev)
+        if why is not None:
+            raise SystemExit(f"{config}: {why}")
+        ms["f64"] = []
     for gp in ms:                            # warm-up of this shape, and the results to compare
         K.gp_operator(n, table, xd, h0, h, N=N, d=d, gp=gp)
         out[gp] = (h0.clone(), h.clone())
-    plan = K.LAST_GP_OPERATOR_PLAN
+        if gp == "mfma":
+            plan = K.LAST_GP_OPERATOR_PLAN
     torch.cuda.synchronize()
     for _ in range(reps):
         for gp in ms:
@@ -94,6 +101,10 @@ def kernel_config(config, size, reps):
     for gp, v in ms.items():
         stats(rec, gp, v)
     rec["valu_over_mfma"] = round(rec["valu_ms_median"] / rec["mfma_ms_median"], 3)
+    if f64:
+        rec["f64_over_mfma"] = round(rec["f64_ms_median"] / rec["mfma_ms_median"], 3)
+        rec["max_diff_value_f64_mfma"] = float((out["f64"][0] - out["mfma"][0]).abs().max().item())
+        rec["max_diff_gradient_f64_mfma"] = float((out["f64"][1] - out["mfma"][1]).abs().max().item())
     print(json.dumps(rec))
 
 
@@ -123,6 +134,7 @@ def main():
     ap.add_argument("--steps", type=int, default=4, help="dates of an engine run")
     ap.add_argument("--limit", type=int, default=400, help="seconds each configuration may take")
     ap.add_argument("--record", default=os.path.join(ROOT, "profiles", "gp_operator_kernels.jsonl"))
+    ap.add_argument("--f64", action="store_true", help="kernel configurations: time gp='f64' as a third arm")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.reps < 7:
@@ -130,11 +142,11 @@ def main():
     if a.child:
         if a.child.startswith("engine:"):
             return engine_config(a.child.split(":", 1)[1], a.size, a.steps, a.limit)
-        return kernel_config(a.child, a.size, a.reps)
+        return kernel_config(a.child, a.size, a.reps, a.f64)
     for config in a.configs:
         engine = config.startswith("engine:")
         cmd = [sys.executable, os.path.abspath(__file__), "--child", config, "--size", str(a.size), "--reps",
-               str(a.reps), "--steps", str(a.steps)]
+               str(a.reps), "--steps", str(a.steps)] + (["--f64"] if a.f64 else [])
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=(5 if engine else 1) * a.limit, cwd=ROOT,
                                env=dict(os.environ, PYTHONPATH=ROOT))
