@@ -621,6 +621,63 @@ PYBIND11_MODULE(KF_MODULE_NAME, m) {
     if (device) check_hip(dev_gp_variance(a, grid, (hipStream_t)stream), "gp_variance");
     else check_host(host_gp_variance(a, P<const float>(etab), P<const float>(wtab), T), "gp_variance");
   });
+  // Observation weights inflated by the predictive variance (kf_launch.h GpObsWeightArgs), GPW_MAX_BANDS bands
+  // at a time.  bands[b]: the observation fields decode_obs reads, d, map, center and coef (= lambda) of GP band
+  // b; the other lists carry gp_variance's table arguments and the output planes per band (var_out[b] may be 0).
+  m.def("gp_obs_weight", [](int np, const std::vector<BandDesc>& bands, const std::vector<float>& signal,
+                            const std::vector<float>& inv_scale2, const std::vector<uintptr_t>& etab,
+                            const std::vector<uintptr_t>& wtab, const std::vector<int>& nchunk,
+                            const std::vector<int>& T, uintptr_t x, const std::vector<uintptr_t>& y_out,
+                            const std::vector<uintptr_t>& w_out, const std::vector<uintptr_t>& var_out, int64_t N,
+                            int64_t ld, int grid, bool device, uintptr_t stream) {
+    const size_t nb = bands.size();
+    if (nb < 1 || signal.size() != nb || inv_scale2.size() != nb || etab.size() != nb || wtab.size() != nb ||
+        nchunk.size() != nb || T.size() != nb || y_out.size() != nb || w_out.size() != nb || var_out.size() != nb)
+      throw std::invalid_argument("gp_obs_weight: one entry per band in every list");
+    for (size_t b0 = 0; b0 < nb; b0 += GPW_MAX_BANDS) {
+      GpObsWeightArgs a{};
+      a.x = P<const float>(x);
+      a.N = N;
+      a.ld = ld;
+      a.nb = (int)std::min<size_t>(GPW_MAX_BANDS, nb - b0);
+      const float* t[GPW_MAX_BANDS];
+      const float* w[GPW_MAX_BANDS];
+      for (int i = 0; i < a.nb; ++i) {
+        const size_t b = b0 + i;
+        const BandDesc& bd = bands[b];
+        GpObsWeightBand& g = a.band[i];
+        if (bd.op != OP_GP || bd.d < 1 || bd.d > GPM_MAX_D)
+          throw std::invalid_argument("gp_obs_weight: a GP band of at most 10 inputs per entry");
+        for (int k = 0; k < bd.d; ++k) {
+          if (bd.map[k] < 0 || bd.map[k] >= np) throw std::invalid_argument("gp_obs_weight: state map outside the state");
+          g.map[k] = bd.map[k];
+          g.center[k] = bd.center[k];
+          g.lam[k] = bd.coef[k];
+        }
+        g.d = bd.d;
+        g.etab = P<const void>(etab[b]);
+        g.wtab = P<const void>(wtab[b]);
+        g.nchunk = nchunk[b];
+        g.signal = signal[b];
+        g.inv_scale2 = inv_scale2[b];
+        g.obs = bd.obs;
+        g.scale = bd.scale;
+        g.rel_unc = bd.rel_unc;
+        g.unc_floor = bd.unc_floor;
+        g.y = bd.y;
+        g.w = bd.w;
+        g.mask = bd.mask;
+        g.dn = bd.dn;
+        g.y_out = P<float>(y_out[b]);
+        g.w_out = P<float>(w_out[b]);
+        g.var_out = P<float>(var_out[b]);
+        t[i] = P<const float>(etab[b]);
+        w[i] = P<const float>(wtab[b]);
+      }
+      if (device) check_hip(dev_gp_obs_weight(a, grid, (hipStream_t)stream), "gp_obs_weight");
+      else check_host(host_gp_obs_weight(a, t, w, T.data() + b0), "gp_obs_weight");
+    }
+  });
   m.attr("GPV_MAX_CHUNKS") = GPV_MAX_CHUNKS;
   m.def("gp_variance_table", []() {
     std::vector<std::string> names;

@@ -386,6 +386,35 @@ int host_innovation(int np, const InnovationArgs& a) {
 }
 // The predictive variance of kf_gp_variance.hip as a plain float32 loop: k^ from the squared
 // distances, u = W^ k^ over the lower triangle, var = s max(0, 1 - sum u^2).
+// One pixel of it; B: GpVarArgs or GpObsWeightBand (map, center, lam, signal), kh: T floats of scratch.
+// NaN where a GP input is not finite.
+template <typename B>
+static float gpv_host_pixel(const B& b, int D, const float* x, int64_t ld, int64_t p, const float* t, const float* w,
+                            int T, float* kh) {
+  float xi[GPM_MAX_D];
+  bool fin = true;
+  for (int d = 0; d < D; ++d) {
+    xi[d] = x[(int64_t)b.map[d] * ld + p] - b.center[d];
+    fin = fin && finitef(xi[d]);
+  }
+  if (!fin) return nanf("");
+  for (int i = 0; i < T; ++i) {
+    float q = 0.f;
+    for (int d = 0; d < D; ++d) {
+      const float dx = xi[d] - t[(size_t)i * D + d];
+      q += b.lam[d] * dx * dx;
+    }
+    kh[i] = expf(-0.5f * q);
+  }
+  float su = 0.f;
+  for (int r = 0; r < T; ++r) {
+    const float* wr = w + (size_t)r * T;
+    float u = 0.f;
+    for (int i = 0; i <= r; ++i) u += wr[i] * kh[i];
+    su += u * u;
+  }
+  return b.signal * fmaxf(1.f - su, 0.f);
+}
 int host_gp_variance(const GpVarArgs& a, const float* t, const float* w, int T) {
   const int D = a.d;
   if (D < 1 || D > GPM_MAX_D || T < 1 || a.N > a.ld || !a.x || !a.out || !t || !w) return -1;
@@ -393,33 +422,34 @@ int host_gp_variance(const GpVarArgs& a, const float* t, const float* w, int T) 
   {
     std::vector<float> kh((size_t)T);
 #pragma omp for schedule(static)
-    for (int64_t p = 0; p < a.N; ++p) {
-      float xi[GPM_MAX_D];
-      bool fin = true;
-      for (int d = 0; d < D; ++d) {
-        xi[d] = a.x[(int64_t)a.map[d] * a.ld + p] - a.center[d];
-        fin = fin && finitef(xi[d]);
+    for (int64_t p = 0; p < a.N; ++p) a.out[p] = gpv_host_pixel(a, D, a.x, a.ld, p, t, w, T, kh.data());
+  }
+  return 0;
+}
+// gp_obs_weight_kernel's outputs from the same loop: decode_obs, the variance where the pixel is observed
+// (the kernel also evaluates the unobserved pixels of an observed tile; their var_out reads 0 here), and
+// the kernel's epilogue (gpw_weight)
+int host_gp_obs_weight(const GpObsWeightArgs& a, const float* const* t, const float* const* w, const int* T) {
+  if (a.nb < 1 || a.nb > GPW_MAX_BANDS || a.N > a.ld || !a.x || !t || !w || !T) return -1;
+  for (int i = 0; i < a.nb; ++i) {
+    const GpObsWeightBand& b = a.band[i];
+    if (b.d < 1 || b.d > GPM_MAX_D || T[i] < 1 || !t[i] || !w[i] || !b.y_out || !b.w_out) return -1;
+  }
+  for (int i = 0; i < a.nb; ++i) {
+    const GpObsWeightBand& b = a.band[i];
+#pragma omp parallel
+    {
+      std::vector<float> kh((size_t)T[i]);
+#pragma omp for schedule(static)
+      for (int64_t p = 0; p < a.N; ++p) {
+        float y, wt;
+        gpw_decode(b, p, y, wt);
+        const float v = wt > 0.f ? gpv_host_pixel(b, b.d, a.x, a.ld, p, t[i], w[i], T[i], kh.data()) : 0.f;
+        const bool fin = finitef(v);
+        b.y_out[p] = y;
+        b.w_out[p] = gpw_weight(wt, v, fin);
+        if (b.var_out) b.var_out[p] = v;
       }
-      if (!fin) {
-        a.out[p] = nanf("");
-        continue;
-      }
-      for (int i = 0; i < T; ++i) {
-        float q = 0.f;
-        for (int d = 0; d < D; ++d) {
-          const float dx = xi[d] - t[(size_t)i * D + d];
-          q += a.lam[d] * dx * dx;
-        }
-        kh[i] = expf(-0.5f * q);
-      }
-      float su = 0.f;
-      for (int r = 0; r < T; ++r) {
-        const float* wr = w + (size_t)r * T;
-        float u = 0.f;
-        for (int i = 0; i <= r; ++i) u += wr[i] * kh[i];
-        su += u * u;
-      }
-      a.out[p] = a.signal * fmaxf(1.f - su, 0.f);
     }
   }
   return 0;

@@ -72,6 +72,57 @@ hipError_t dev_gp_variance(const GpVarArgs& a, int grid, hipStream_t s);
 std::vector<const char*> gp_variance_table();
 // the same whitened form as a float32 loop: t [T][d] centred training inputs, w [T][T] the unsplit W^
 int host_gp_variance(const GpVarArgs& a, const float* t, const float* w, int T);
+// Observation error inflated by the emulator's predictive variance (kf_gp_variance.hip gp_obs_weight_kernel):
+// for every band b of the launch and pixel p, with (y, w) = decode_obs(band, p) and var = the band's
+// predictive variance at x_p, y_out[p] = y and w_out[p] = w / (1 + w var) = 1 / (sigma_obs^2 + var) -- the
+// (y, w) planes of an OBS_F32 band -- and var_out[p] = var (may be null).  A 64-pixel tile without an
+// observation reads (y, 0, var 0) and costs no GP work; a pixel whose GP input is not finite keeps its w.
+constexpr int GPW_MAX_BANDS = 8;   // bands per launch (the caller slices longer tables)
+struct GpObsWeightBand {
+  const void* etab;   // GpVarArgs' table fields
+  const void* wtab;
+  int32_t nchunk, d;
+  float signal, inv_scale2;
+  int32_t map[GPM_MAX_D];
+  float center[GPM_MAX_D];
+  float lam[GPM_MAX_D];
+  int32_t obs;        // what decode_obs reads of a BandDesc
+  float scale, rel_unc, unc_floor;
+  const float* y;
+  const float* w;
+  const uint8_t* mask;
+  const uint16_t* dn;
+  float* y_out;       // [N]
+  float* w_out;       // [N]
+  float* var_out;     // [N] or null
+};
+struct GpObsWeightArgs {
+  const float* x;     // SoA state rows [n_params][ld] (read only)
+  int64_t N, ld;
+  int32_t nb, pad0;
+  GpObsWeightBand band[GPW_MAX_BANDS];
+};
+// B: GpObsWeightBand, in the kernel behind the kernarg pointer
+template <typename B>
+KF_HD void gpw_decode(const B& b, int64_t p, float& y, float& w) {
+  BandDesc bd{};   // decode_obs' fields only; the rest folds away
+  bd.obs = b.obs;
+  bd.scale = b.scale;
+  bd.rel_unc = b.rel_unc;
+  bd.unc_floor = b.unc_floor;
+  bd.y = b.y;
+  bd.w = b.w;
+  bd.mask = b.mask;
+  bd.dn = b.dn;
+  decode_obs<0>(bd, p, y, w);
+}
+// the inflated weight: a true division (w var is no small term where the emulator extrapolates); w = 0 stays
+// +0, and a variance that could not be evaluated (fin false) leaves w as decoded
+KF_HD float gpw_weight(float w, float var, bool fin) { return fin ? w / __builtin_fmaf(w, var, 1.f) : w; }
+// grid <= 0: one workgroup per compute unit and band.  One launch per distinct d of the bands.
+hipError_t dev_gp_obs_weight(const GpObsWeightArgs& a, int grid, hipStream_t s);
+// t[b] [T[b]][d] centred training inputs, w[b] [T[b]][T[b]] the unsplit W^ of band b
+int host_gp_obs_weight(const GpObsWeightArgs& a, const float* const* t, const float* const* w, const int* T);
 hipError_t dev_gp_operator(int np, int d, const GpOperatorArgs& a, hipStream_t s);
 bool gp_operator_supported(int np, int d);
 // K2 on the matrix cores (kf_gp_operator_mfma.hip): one grid per plan of gp_operator_plan (a distinct input

@@ -170,8 +170,13 @@ class EngineConfig:
     # emulator_uncertainty: 'report' evaluates the predictive std of every GP band's emulator at
     # each date's analysis (ops.kernels.gp_variance; LinearKalman.last_emulator_std) and adds its
     # max and mean over the finite pixels to the date's metrics record ("emulator").  The analysis
-    # itself does not read it.  'off': nothing launches (--emulator-uncertainty)
-    emulator_uncertainty: str = "off"         # 'off' | 'report'
+    # itself does not read it.  'off': nothing launches (--emulator-uncertainty).  'inflate' adds the
+    # predictive variance at each date's forecast to the observation error of every GP band, per pixel
+    # (w' = 1 / (sigma_obs^2 + var_emu); LinearKalman._inflate_date, gp_obs_weight_kernel): the analysis
+    # runs on engine-owned OBS_F32 planes, the weights fixed over the date's Gauss-Newton iterations, and
+    # the record of 'report' (the std at the forecast) gains the mean w'/w per band.  It raises with
+    # band_sequential, band_parallel > 1, the innovation options and host-evaluated operators
+    emulator_uncertainty: str = "off"         # 'off' | 'report' | 'inflate'
     metrics_path: str | None = None           # JSONL metrics (per date / timestep)
     checkpoint_dir: str | None = None
     checkpoint_every: int = 0                 # timesteps between checkpoints (0: off)
@@ -214,8 +219,8 @@ class EngineConfig:
             raise ValueError("innovation_forecast must be 'materialised' or 'fused'")
         if self.smoother_form not in ("dense", "rank_one"):
             raise ValueError("smoother_form must be 'dense' or 'rank_one'")
-        if self.emulator_uncertainty not in ("off", "report"):
-            raise ValueError("emulator_uncertainty must be 'off' or 'report'")
+        if self.emulator_uncertainty not in ("off", "report", "inflate"):
+            raise ValueError("emulator_uncertainty must be 'off', 'report' or 'inflate'")
         if self.store_precision not in ("auto", "always"):
             raise ValueError("store_precision must be 'auto' or 'always'")
         if isinstance(self.convergence_chunk, str) and self.convergence_chunk.strip().lower() in ("", "0", "tile",

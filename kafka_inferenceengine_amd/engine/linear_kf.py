@@ -166,6 +166,12 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         self.last_innovation = None       # config.innovation_*: the last date's {"chi2", "nobs", "nrej"}
         self._innov_forecast = None       # the last screened date's check: "fused" | "materialised"
         self.last_emulator_std = None     # config.emulator_uncertainty: the last date's [n_gp_bands, N] std
+        # emulator_uncertainty = 'inflate', the last date: its source (spec, band) pairs, the forecast states
+        # x [n_params, ld] the variance was taken at (a copy) and the (spec, band) pairs the analysis ran on
+        self.last_inflate_source = None
+        self.last_inflate_x = None
+        self.last_inflate_bands = None
+        self._inflate = None              # its planes [3 (y, w, var), n_gp_bands, width], engine-owned
         self._last_date = None            # (date, band specs, analysis state) of the last date assimilated
         self.gate_history = None          # config.innovation_gate: dates with a rejection, per pixel (int32)
         self.evidence = None              # config.innovation_evidence: the run's per-pixel accumulators
@@ -560,6 +566,9 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             if LOG.isEnabledFor(logging.INFO):
                 LOG.info("Assimilating %s..." % step.strftime("%Y-%m-%d"))
             t0 = time.perf_counter()
+            inflate = self.config.emulator_uncertainty == "inflate"
+            if inflate:
+                self._check_inflate()
             if self.config.band_sequential:
                 res = self._assimilate_sequential(step, self._materialize(forecast))
             else:
@@ -584,6 +593,11 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                         # background check of the date's observations against the materialised
                         # forecast; under a gate the analysis runs on the screened bands
                         forecast, run_bands = self._screen_date(step, bands, forecast)
+                        ready = ready and run_bands is bands
+                        bands = run_bands
+                    if inflate:
+                        # the GP bands' observation error inflated by the emulators' variance at the forecast
+                        forecast, run_bands = self._inflate_date(step, bands, forecast)
                         ready = ready and run_bands is bands
                         bands = run_bands
                     res = self.do_all_bands_state(step, bands, forecast, table=prep[2] if ready else None,
@@ -613,6 +627,8 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
                 rec["spatial"] = self._spatial_record()
             if self.config.emulator_uncertainty == "report":
                 rec["emulator"] = self._emulator_report()
+            elif inflate:
+                rec["emulator"] = self._inflate_report()
             if self.metrics.enabled:
                 rec.update(self._health_metrics(rec["wall_s"]))
                 if self._screening() and not self.config.band_sequential and self.last_innovation is not None:
@@ -632,8 +648,10 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         specs = [sp for sp, _ in bands]
         cfg = self.config
         order = None
-        # (a gated date runs on screened copies of its bands: its table and order follow the check)
+        # (a gated date runs on screened copies of its bands: its table and order follow the check; a
+        # date under emulator_uncertainty = 'inflate' on engine-owned planes likewise)
         if not (cfg.return_innovations or cfg.spatial_gamma > 0 or cfg.innovation_gate > 0 or
+                cfg.emulator_uncertainty == "inflate" or
                 self.band_comm is not None or any(sp.kind == OP_PRECOMP for sp in specs)) and \
                 self._split_plan_kind(specs) is None:
             table = self._band_table(bands, specs, [d for _, d in bands])
@@ -728,12 +746,14 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
             K.gp_variance(self.n_params, sp, x, out[i], N=self.N)
         return out.sqrt_()
 
-    def _emulator_report(self):
+    def _emulator_report(self, std=None):
         """config.emulator_uncertainty = 'report': the date's std planes (``last_emulator_std``)
-        and, per GP band, their max and mean over the finite pixels (one read-back)."""
+        and, per GP band, their max and mean over the finite pixels (one read-back).  ``std``:
+        planes already evaluated ('inflate': at the forecast)."""
         if self.config.band_sequential:
             raise ValueError("emulator_uncertainty='report' does not run with band_sequential")
-        std = self.last_emulator_std = self.emulator_variance()
+        if std is None:
+            std = self.last_emulator_std = self.emulator_variance()
         names = [getattr(sp.emulator, "name", "gp") for sp in self._last_date[1] if sp.kind == OP_GP]
         if not std.numel():
             return [{"band": n, "max": None, "mean": None} for n in names]
@@ -741,6 +761,88 @@ class LinearKalman(GaussNewtonMixin, SpatialPriorMixin, SmootherMixin):
         s0 = torch.where(fin, std, torch.zeros_like(std))
         stats = torch.stack([s0.max(1).values, s0.sum(1) / fin.sum(1).clamp(min=1)]).cpu().numpy()
         return [{"band": n, "max": float(stats[0, i]), "mean": float(stats[1, i])} for i, n in enumerate(names)]
+
+    def _check_inflate(self):
+        """config.emulator_uncertainty = 'inflate' changes the statistics the user asked for: what it
+        does not run with raises, nothing falls back to the uninflated analysis."""
+        cfg = self.config
+        if cfg.band_sequential:
+            raise ValueError("emulator_uncertainty='inflate' does not run with band_sequential")
+        if cfg.band_parallel > 1 or self.band_comm is not None:
+            raise ValueError("emulator_uncertainty='inflate' with band_parallel > 1: a rank does not hold every "
+                             "band's planes")
+        if self._screening():
+            raise ValueError("emulator_uncertainty='inflate' with innovation_gate / innovation_stats / "
+                             "innovation_evidence: the check would screen against the uninflated observation error")
+
+    def _inflate_date(self, timestep, bands, forecast):
+        """config.emulator_uncertainty = 'inflate': the observation error of every GP band of one date
+        inflated by its emulator's predictive variance, w' = w / (1 + w var) = 1 / (sigma_obs^2 + var_emu)
+        per pixel (``ops.kernels.gp_variance(obs=...)``, all GP bands in one launch per input count).
+        Returns the forecast, materialised as :meth:`_screen_date` materialises it, and the bands to
+        assimilate: every GP band replaced by an ``OBS_F32`` band over engine-owned ``(y, w')`` planes
+        (``metadata``, ``emulator`` and ``aux`` carried over; the mask is folded into ``w'``), every
+        other band (SAR, linear) as it was.  The source's planes are never written.
+
+        The variance is taken once per date, at the forecast state, and the weights then stay fixed
+        over the date's Gauss-Newton iterations: the iteration minimises one fixed cost function (a
+        variance that followed the linearisation point would change the cost between iterations, and
+        its gradient would be missing from the normal equations).  ``last_emulator_std`` holds the
+        std at the forecast; ``last_inflate_source`` / ``last_inflate_x`` / ``last_inflate_bands`` what
+        the launch read and what the analysis ran on."""
+        specs = [s for s, _ in bands]
+        dbs = [d for _, d in bands]
+        if any(s.kind == OP_PRECOMP for s in specs):
+            raise ValueError("emulator_uncertainty='inflate' needs every band's operator on the device: a "
+                             "host-evaluated (reference-protocol) observation operator carries no emulator")
+        gp = [b for b, s in enumerate(specs) if s.kind == OP_GP]
+        for b in gp:
+            ok, why = K.gp_variance_supported(specs[b], self.device)
+            if not ok:
+                raise ValueError(f"emulator_uncertainty='inflate': band {b}: {why}")
+        if not gp:
+            self.last_emulator_std = torch.empty((0, self.N), dtype=torch.float32, device=self.device)
+            self.last_inflate_source = self.last_inflate_x = self.last_inflate_bands = None
+            return forecast, bands
+        fc = self._as_kind(forecast, self._analysis_kind())
+        fc.require_full("the observation-error inflation")
+        N = self.N
+        # the planes as wide as the widest source plane: what the analysis may read of a band it reads of these
+        width = max([N, 1] + [t.numel() for b in gp for t in (dbs[b].dn, dbs[b].y, dbs[b].w) if t is not None])
+        buf = self._inflate
+        if buf is None or buf.shape[1] < len(gp) or buf.shape[2] < width:
+            buf = self._inflate = torch.zeros((3, len(gp), width), dtype=torch.float32, device=self.device)
+        y, w, var = buf[0], buf[1], buf[2]
+        if N:
+            with self.timer.phase("inflate"):
+                K.gp_variance(self.n_params, [specs[b] for b in gp], fc.x, [var[i] for i in range(len(gp))], N=N,
+                              obs=[dbs[b] for b in gp], y_out=[y[i] for i in range(len(gp))],
+                              w_out=[w[i] for i in range(len(gp))])
+        self.last_emulator_std = var[:len(gp), :N].sqrt()
+        run_bands = list(bands)
+        for i, b in enumerate(gp):
+            run_bands[b] = (specs[b], DeviceBand(kind=K.OBS_F32, y=y[i], w=w[i], metadata=dbs[b].metadata,
+                                                 emulator=dbs[b].emulator, aux=dbs[b].aux))
+        self.last_inflate_source, self.last_inflate_x, self.last_inflate_bands = list(bands), fc.x.clone(), run_bands
+        return fc, run_bands
+
+    def _inflate_report(self):
+        """The 'report' entries from the std at the forecast, plus per GP band the mean of w'/w over
+        the observed pixels: w'/w = 1 / (1 + w var) = 1 - w' var (one read-back)."""
+        rec = self._emulator_report(self.last_emulator_std)
+        if self.last_inflate_bands is None or not self.N:
+            return rec
+        N = self.N
+        gp = [db for sp, db in self.last_inflate_bands if sp.kind == OP_GP]
+        w = torch.stack([db.w[:N] for db in gp])
+        var = self.last_emulator_std ** 2
+        seen = w > 0
+        ratio = torch.where(seen & torch.isfinite(var), 1.0 - w * var, seen.to(w.dtype))
+        mean = (ratio.sum(1) / seen.sum(1).clamp(min=1)).cpu().numpy()
+        nobs = seen.sum(1).cpu().numpy()
+        for i, r in enumerate(rec):
+            r["weight_ratio"] = float(mean[i]) if nobs[i] else None
+        return rec
 
     def _hessian_gp(self, table) -> str:
         """config.hessian_gp where the date's table and the device allow it, else the VALU kernel."""

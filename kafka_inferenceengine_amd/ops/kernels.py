@@ -1520,30 +1520,92 @@ def gp_variance_supported(spec_or_emulator, device="cuda"):
     return True, ""
 
 
-def gp_variance(n_params, spec_or_emulator, x, out, N=None, stream=None, grid=None):
-    """Predictive variance of one GP band's emulator at the states ``x`` ``[n_params, ld]``, written to the
-    float32 plane ``out`` ``[>= N]``: ``s - k(x)^T (K + nugget)^-1 k(x)`` with the GP inputs gathered through
-    the band's state map.  On a device the triangular GEMM runs on the matrix cores
-    (csrc/kf_gp_variance.hip); CPU tensors take the float32 host loop.  A pixel with a non-finite input
-    reads NaN.  Raises ValueError with :func:`gp_variance_supported`'s reason where there is no kernel.
-    ``stream``: a raw stream handle (default: the current one); ``grid``: workgroups (default: one per
-    compute unit)."""
-    N = int(x.shape[1] if N is None else N)
-    _check_soa(x, int(n_params), N, "x")
-    _check_vec(out, N, "out", torch.float32, x.device)
-    ok, why = gp_variance_supported(spec_or_emulator, x.device)
+def _gpv_checked(n_params, spec_or_emulator, device):
+    """(emulator, state map) of a band :func:`gp_variance` serves on ``device``; raises with the reason."""
+    ok, why = gp_variance_supported(spec_or_emulator, device)
     if not ok:
         raise ValueError(f"gp_variance: {why}")
     em, smap = _gpv_emulator(spec_or_emulator)
     if len(smap) != em.n_inputs or any(j < 0 or j >= int(n_params) for j in smap):
         raise ValueError(f"gp_variance: state map {smap} does not fit {em.n_inputs} GP inputs of a "
                          f"{n_params}-parameter state")
+    return em, smap
+
+
+def gp_variance(n_params, spec_or_emulator, x, out, N=None, stream=None, grid=None, obs=None, y_out=None,
+                w_out=None):
+    """Predictive variance of one GP band's emulator at the states ``x`` ``[n_params, ld]``, written to the
+    float32 plane ``out`` ``[>= N]``: ``s - k(x)^T (K + nugget)^-1 k(x)`` with the GP inputs gathered through
+    the band's state map.  On a device the triangular GEMM runs on the matrix cores
+    (csrc/kf_gp_variance.hip); CPU tensors take the float32 host loop.  A pixel with a non-finite input
+    reads NaN.  Raises ValueError with :func:`gp_variance_supported`'s reason where there is no kernel.
+    ``stream``: a raw stream handle (default: the current one); ``grid``: workgroups (default: one per
+    compute unit).
+
+    ``obs`` (the band's observation, an object with :class:`engine.bands.DeviceBand`'s fields) selects the
+    observation-weight launch (``gp_obs_weight_kernel``): ``y_out`` / ``w_out``, float32 ``[>= N]``, receive
+    the decoded observation and its weight inflated by the variance, ``w / (1 + w var) = 1 / (sigma_obs^2 +
+    var)`` -- the planes of an ``OBS_F32`` band -- and ``out`` (may be None) the variance.  A 64-pixel tile
+    with no observation reads ``(y, 0)`` and variance 0 without any GP work (on the CPU: every unobserved
+    pixel); a pixel with a non-finite GP input keeps its decoded weight and reads variance NaN.  ``grid``
+    then counts the workgroups per band.  ``spec_or_emulator``, ``obs``, ``out``, ``y_out`` and ``w_out``
+    may be equal-length lists: one call runs a date's GP bands in one launch per distinct input count."""
+    N = int(x.shape[1] if N is None else N)
+    _check_soa(x, int(n_params), N, "x")
+    raw_stream = _stream(x) if stream is None else int(stream)
+    if obs is None:
+        if y_out is not None or w_out is not None:
+            raise ValueError("gp_variance: y_out / w_out go with obs")
+        _check_vec(out, N, "out", torch.float32, x.device)
+        em, smap = _gpv_checked(n_params, spec_or_emulator, x.device)
+        if N <= 0:
+            return
+        f = _gpv_fields(em, x.device)
+        ext().gp_variance(int(n_params), smap, [float(v) for v in em.center()], [float(v) for v in em.lam],
+                          float(em.signal), f[3], _ptr(f[0]), _ptr(f[1]), f[2], int(em.n_train), _ptr(x), _ptr(out),
+                          N, x.shape[1], int(grid or 0), _dev(x), raw_stream)
+        return
+    many = isinstance(obs, (list, tuple))
+    specs, obs, y_out, w_out = (list(v) if many else [v] for v in (spec_or_emulator, obs, y_out, w_out))
+    out = [None] * len(obs) if out is None else list(out) if many else [out]
+    if not obs or any(len(v) != len(obs) for v in (specs, out, y_out, w_out)):
+        raise ValueError("gp_variance: spec, obs, out, y_out and w_out need one entry per band")
+    descs, fields, ems = [], [], []
+    for sp, ob, o, yo, wo in zip(specs, obs, out, y_out, w_out):
+        if yo is None or wo is None:
+            raise ValueError("gp_variance: obs needs y_out and w_out")
+        for t, name in ((o, "out"), (yo, "y_out"), (wo, "w_out")):
+            _check_vec(t, N, name, torch.float32, x.device)
+        em, smap = _gpv_checked(n_params, sp, x.device)
+        d = ext().BandDesc()
+        d.op, d.obs, d.d = OP_GP, int(ob.kind), int(em.n_inputs)
+        d.map, d.center, d.coef = smap, [float(v) for v in em.center()], [float(v) for v in em.lam]
+        d.scale, d.rel_unc, d.unc_floor = float(ob.scale), float(ob.rel_unc), float(ob.unc_floor)
+        # the planes the encoding reads (kf_core.h decode_obs): DN16 dn; F32 / BF16 y, w; BF16Y y
+        need = {OBS_DN16: ("dn",), OBS_F32: ("y", "w"), OBS_BF16: ("y", "w"), OBS_BF16Y: ("y",)}.get(d.obs)
+        if need is None:
+            raise ValueError(f"gp_variance: obs.kind {ob.kind} is no observation encoding")
+        for name in need:
+            t = getattr(ob, name)
+            if t is None:
+                raise ValueError(f"gp_variance: obs.{name} is missing")
+            # float32 planes, or 16-bit patterns in whichever 2-byte dtype the source keeps them
+            _check_vec(t, N, f"obs.{name}", torch.float32 if d.obs == OBS_F32 else t.dtype, x.device)
+            if d.obs != OBS_F32 and t.element_size() != 2:
+                raise ValueError(f"gp_variance: obs.{name}: expected 16-bit samples, got {t.dtype}")
+            setattr(d, name, t.data_ptr())
+        if ob.mask is not None and d.obs != OBS_DN16:
+            _check_vec(ob.mask, N, "obs.mask", torch.uint8, x.device)
+            d.mask = ob.mask.data_ptr()
+        descs.append(d)
+        fields.append(_gpv_fields(em, x.device))
+        ems.append(em)
     if N <= 0:
         return
-    f = _gpv_fields(em, x.device)
-    ext().gp_variance(int(n_params), smap, [float(v) for v in em.center()], [float(v) for v in em.lam],
-                      float(em.signal), f[3], _ptr(f[0]), _ptr(f[1]), f[2], int(em.n_train), _ptr(x), _ptr(out), N,
-                      x.shape[1], int(grid or 0), _dev(x), _stream(x) if stream is None else int(stream))
+    ext().gp_obs_weight(int(n_params), descs, [float(em.signal) for em in ems], [f[3] for f in fields],
+                        [_ptr(f[0]) for f in fields], [_ptr(f[1]) for f in fields], [f[2] for f in fields],
+                        [int(em.n_train) for em in ems], _ptr(x), [_ptr(t) for t in y_out], [_ptr(t) for t in w_out],
+                        [_ptr(t) for t in out], N, x.shape[1], int(grid or 0), _dev(x), raw_stream)
 
 
 class TileEncoder:
